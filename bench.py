@@ -9,9 +9,14 @@ orthonormal POD basis r = 80, 100 000 samples per GPU, fp64.  With --gpus N > 1 
 runs its own 100k-sample shard (weak scaling, no data-path collective) and the QoIs are
 gathered on rank 0 with one RCCL all_gather per step (the "gather at the end" of north_star).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and
+prints the line; beside the headline it carries what the timed steps themselves yield:
   roofline      dominant kernel, measured live with HIP events on the launch stream
-  cpu_baseline  the NumPy/SciPy oracle (oracle/fin_oracle.py, kind="port") timed on one host core
+With --full it also runs the passes of their own (null in a plain run):
+  cpu_baseline  the NumPy/SciPy oracle (oracle/fin_oracle.py, kind="port") timed on one host core, and on all cores
+  kernels_serial_ms, host_io_pairs_per_s, other_projection, sampler_ms_per_step (see their comments in main)
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float64; at most 64 MB = 64e6
+bytes in all, a fixed seeded row sample beyond that), so that two builds can be compared output for output on the same inputs.
 """
 from __future__ import annotations
 
@@ -40,16 +45,23 @@ def parse():
     ap.add_argument("--m", type=int, default=12, help="lattice divisor (12 -> 1597 DoF)")
     ap.add_argument("--r", type=int, default=80)
     ap.add_argument("--params", default="five", choices=["five", "nine", "field"])
-    ap.add_argument("--cpu-samples", type=int, default=2000, help="oracle samples for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baselines, the serialised per-kernel pass, the host-buffer "
+                         "pass, the other --projection, the field sampler's cost (pairs); the stream-order kernel pass, the "
+                         "single-chain latency and the CPU baseline (hmc)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float64, at "
+                         "most 64 MB in all: a fixed seeded row sample of larger outputs)")
+    ap.add_argument("--cpu-samples", type=int, default=2000, help="oracle samples for cpu_baseline (--full; 0 = skip)")
     ap.add_argument("--projection", default="direct", choices=["direct", "offline_online"],
                     help="how the timed region forms A_r: 'direct' = per-sample psi^T psi on MFMA (what the reference executes, the "
                          "headline); 'offline_online' = precomputed Gram blocks (same results, ~50x fewer ROM flops)")
     ap.add_argument("--stream", choices=("default", "own"), default="own",
                     help="pairs workload: the steps on a torch stream of their own (non-blocking; the ROM half of finrom_solve_pairs "
                          "then stays on it, no cross-stream wait per step) or on torch's default (null) stream")
-    ap.add_argument("--no-other", action="store_true", help="skip the extra (untimed) pass with the other --projection")
+    ap.add_argument("--no-other", action="store_true", help="--full: skip the extra (untimed) pass with the other --projection")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-host-io", action="store_true", help="skip the extra (untimed) host-buffer pass")
+    ap.add_argument("--no-host-io", action="store_true", help="--full: skip the extra (untimed) host-buffer pass")
     ap.add_argument("--workload", default="pairs", choices=["pairs", "hmc"],
                     help="pairs: the FOM+ROM dataset loop (BASELINE metric, configs[1..3]); hmc: BASELINE configs[4], chains of "
                          "sequential dependent one-sample ROM + learned-error value-and-gradient calls (steps = calls per chain)")
@@ -136,6 +148,43 @@ def flops_per_pair(ops, plan, rom, n_obs, P, field=False):
     }
 
 
+DUMP_LIMIT_BYTES = 64_000_000        # 64 MB (decimal) for all files of a dump, .npy headers included
+NPY_HEADER_BYTES = 4096              # per file, an upper bound of np.save's header (128 bytes for these shapes)
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes each array of `arrays` (name -> array-like, None skipped) as outdir/<name>.npy in float64, all files together at
+    most `limit` bytes.  If the arrays do not fit, every array of two or more rows keeps the same fraction of its rows, chosen by
+    default_rng(seed) (sorted), and the kept row indices go beside it as <name>_rows.npy: the sample is the same from run to run.
+    Arrays of fewer than two rows are written whole and counted first."""
+    os.makedirs(outdir, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        if v is None:
+            continue
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        arrs[k] = np.asarray(v, dtype=np.float64)
+    whole = {k for k, a in arrs.items() if a.ndim == 0 or len(a) < 2}
+    fixed = sum(arrs[k].nbytes for k in whole) + NPY_HEADER_BYTES * len(arrs)
+    rest = sum(a.nbytes for k, a in arrs.items() if k not in whole)
+    if fixed > limit:
+        raise ValueError(f"dump_outputs: {fixed} bytes of unsampled arrays and headers exceed the limit of {limit}")
+    frac = 1.0
+    if fixed + rest > limit:
+        # sampled: each kept row costs its bytes + 8 for its index, and each sampled array one more header (the index file)
+        n_rows = sum(len(a) for k, a in arrs.items() if k not in whole)
+        frac = (limit - fixed - NPY_HEADER_BYTES * (len(arrs) - len(whole))) / (rest + 8 * n_rows)
+        if int(max(len(a) for k, a in arrs.items() if k not in whole) * frac) < 1:
+            raise ValueError(f"dump_outputs: a limit of {limit} bytes leaves no room for a row sample")
+    for k, a in arrs.items():
+        if frac < 1.0 and k not in whole:
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(outdir, f"{k}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(outdir, f"{k}.npy"), np.ascontiguousarray(a))
+
+
 # ---- all-core CPU baseline (BASELINE.md 3(ii)): worker processes, started BEFORE anything touches the GPU ----------------
 _W = {}
 
@@ -201,7 +250,7 @@ def main():
     if args.workload == "hmc":
         return run_hmc(args, rank, local_rank, world)
     cpu_all = None
-    if world == 1 and args.cpu_samples > 0 and args.params != "field":
+    if args.full and world == 1 and args.cpu_samples > 0 and args.params != "field":
         try:
             cpu_all = cpu_baseline_all_cores(args)        # worker processes must be gone before the GPU is initialised
         except Exception as e:                             # context only: never fail the bench for it
@@ -297,7 +346,7 @@ def main():
     # context only (NOT the timed region): one pass with the two halves serialised on one stream gives
     # each kernel's stand-alone duration; in the timed region the FOM and ROM kernels overlap
     serial_ms = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         L.finrom_profile_reset(); L.finrom_profile_enable(1)
         L.finrom_set_overlap(0)
         step(); fence()
@@ -307,7 +356,7 @@ def main():
     # context only: the same step fed from / returned to HOST memory through the library's own copies (the NumPy-facing
     # boundary; parameters in, QoI pairs + errors + w_r + theta + info out), i.e. the PCIe-inclusive rate.  Never `value`.
     host_io = None
-    if not args.no_profile and not args.no_host_io and world == 1:
+    if args.full and not args.no_profile and not args.no_host_io and world == 1:
         Xh = X.cpu().numpy()
         pairs.solve_pairs(Xh)
         t0 = time.perf_counter()
@@ -336,10 +385,13 @@ def main():
     full = res["gathered"] if use_pg else torch.cat([res["qoi"], res["qoi_r"]], dim=1)
     gathered_sha = hashlib.sha256(full.cpu().numpy().tobytes()).hexdigest() if rank == 0 else None
     del full
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (rank 0's shard; with a process group also the gathered rows)
+        dump_outputs(args.dump_outputs, {k: res.get(k) for k in ("qoi", "qoi_r", "err", "theta", "info", "gathered")})
 
     # context only, after the timed region: the same steps with the OTHER form of the reduced operator (see --projection)
     other = None
-    if not args.no_profile and not args.no_other:
+    if args.full and not args.no_profile and not args.no_other:
         other_mode = "offline_online" if args.projection == "direct" else "direct"
         solver_r.set_projection(other_mode)
         step(); fence()
@@ -366,7 +418,7 @@ def main():
     # context only (Gaussian-field inputs): what drawing a fresh shard costs on top of the pair step -- xi by Philox on the device
     # + k = exp(0.5 xi U) (finrom_sampler_draw_seeded); the timed region above works on a resident shard, as the contract asks
     sampler_ms = None
-    if args.params == "field" and not args.no_profile:
+    if args.full and args.params == "field" and not args.no_profile:
         like = torch.empty(0, device=dev, dtype=torch.float64)
         sampler.draw(5, rank * S, S, like=like)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -395,7 +447,7 @@ def main():
         roof = roofline(dom, ms, launches, S, args, ops, plan, solver, solver_r, pairs, fl)
 
         cpu = None
-        if world == 1 and args.cpu_samples > 0:
+        if args.full and world == 1 and args.cpu_samples > 0:
             cpu = cpu_baseline(args, phi, X[: args.cpu_samples].cpu().numpy(), res, pairs)
 
         out = {
@@ -420,6 +472,7 @@ def main():
             "value_incl_sampler": None if sampler_ms is None else world * S / (dt / args.steps + sampler_ms * 1e-3),
             "cpu_baseline_all_cores": cpu_all,
             "other_projection": other,
+            "full": args.full,
         }
         print(json.dumps(out), flush=True)
     if use_pg:
@@ -494,7 +547,11 @@ def run_hmc(args, rank, local_rank, world):
     fence()
     dt = time.perf_counter() - t0
     Lb.finrom_profile_enable(0)
-    if args.hmc_mode != "host" and not args.no_profile and mine:
+    if args.dump_outputs and rank == 0 and res:
+        # what the timed chains return to their caller on rank 0: end states, accept counts (and the per-proposal trace)
+        dump_outputs(args.dump_outputs, {"K": res["K"], "accept": res["accept"], "trace": res.get("trace")})
+    stream_pass = args.full and args.hmc_mode != "host" and not args.no_profile and bool(mine)
+    if stream_pass:
         # kernels replayed from a HIP graph cannot be bracketed with events: per-kernel times come from a short pass of the same
         # chains with the launches in stream order (not timed)
         Lb.finrom_profile_reset(); Lb.finrom_profile_enable(1)
@@ -513,7 +570,7 @@ def run_hmc(args, rank, local_rank, world):
     chains = gather_chains(res, mine, world, dist if world > 1 else None)
     # one chain alone, one sample per call: the per-call latency a single PyMC chain would see (not timed above)
     lat = None
-    if rank == 0 and mine:
+    if args.full and rank == 0 and mine:
         n1 = 1 + min(1000, steps) // L * L
         run(1 + L, K0[:1], seeds[:1])
         torch.cuda.synchronize()
@@ -529,7 +586,9 @@ def run_hmc(args, rank, local_rank, world):
         # a chain of DEPENDENT one-sample calls has no throughput roofline: what bounds it is the critical path of a leapfrog step --
         # the step's launches in order, each waiting for the previous one (durations from the stream-order pass above)
         lib_order = ["rom_proj_mfma", "rom_reduced_solve", "misc"]
-        crit = {k: round(ms[k] * 1e3 * (prof[k][0] / max(prof["rom_proj_mfma"][0], 1)), 2) for k in lib_order if ms.get(k, 0) > 0} if prof.get("rom_proj_mfma", (0, 0))[0] else None
+        # (graph replays are not bracketed: without the stream-order pass (--full) only the host mode's timed region has the durations)
+        crit = {k: round(ms[k] * 1e3 * (prof[k][0] / max(prof["rom_proj_mfma"][0], 1)), 2) for k in lib_order if ms.get(k, 0) > 0} \
+            if prof.get("rom_proj_mfma", (0, 0))[0] and (stream_pass or args.hmc_mode == "host") else None
         critical_path = None if not crit else {
             "bound": "latency", "per_step_us": crit, "sum_us": round(sum(crit.values()), 2),
             "measured_step_us": round(1e6 * dt / n_evals, 2),
@@ -538,7 +597,7 @@ def run_hmc(args, rank, local_rank, world):
                     "momentum update (misc: also the proposal's begin / end kernels); kernel durations from a stream-order pass, "
                     "the measured step adds the graph's per-node launch gaps"}
         cpu = None
-        if world == 1 and args.cpu_samples > 0:
+        if args.full and world == 1 and args.cpu_samples > 0:
             cpu = hmc_cpu_baseline(args, phi, model, solver_r.data, K0, res)
         print(json.dumps({
             "metric": "ROM+DL value-and-gradient evaluations/sec (HMC chains, BASELINE configs[4])",
@@ -557,7 +616,7 @@ def run_hmc(args, rank, local_rank, world):
             "roofline": roof, "critical_path": critical_path, "cpu_baseline": cpu,
             "chains_sha256": chains["sha256"], "chains_gathered": chains["n"], "trace_sha256": chains["trace_sha256"],
             "single_chain_latency_ms_per_call": None if lat is None else 1e3 * lat,
-            "kernels_avg_ms": {k: round(v, 4) for k, v in ms.items() if v > 0}}), flush=True)
+            "kernels_avg_ms": {k: round(v, 4) for k, v in ms.items() if v > 0}, "full": args.full}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

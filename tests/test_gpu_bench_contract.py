@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--samples", "4096", "--steps", "2", "--warmup", "1",
-                        "--cpu-samples", "8"], capture_output=True, text=True, timeout=600)
+                        "--cpu-samples", "8", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -32,6 +32,29 @@ def test_bench_json_contract():
     assert d["config"]["failed_samples"] == 0
     _flops_below_peak(d)
     assert rf["traffic"] is None or (rf["traffic_source"] and rf["traffic_source"]["file"].startswith("profiles/"))
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) runs none of the extra passes, and --dump-outputs writes what the last timed step returned: the
+    dumped QoI pairs are the rows behind the line's checksum."""
+    import hashlib
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--samples", "4096", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["config"]["failed_samples"] == 0
+    for key in ("cpu_baseline", "cpu_baseline_all_cores", "kernels_serial_ms", "host_io_pairs_per_s", "other_projection"):
+        assert d[key] is None, key
+    assert d["value"] > 0 and abs(d["value"] - 4096 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(got) == {"qoi", "qoi_r", "err", "theta", "info"}
+    assert all(a.dtype == np.float64 and a.shape[0] == 4096 for a in got.values())
+    assert (got["info"] == 0).all() and np.isfinite(got["qoi"]).all() and np.isfinite(got["qoi_r"]).all()
+    assert hashlib.sha256(np.concatenate([got["qoi"], got["qoi_r"]], axis=1).tobytes()).hexdigest() == d["gathered_sha256"]
 
 
 def _flops_below_peak(d):

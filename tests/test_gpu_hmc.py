@@ -121,7 +121,7 @@ def test_device_chains_without_host_round_trips_reproduce_the_host_chains(setup,
 
 def test_bench_hmc_mode_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "hmc", "--steps", "40", "--warmup", "10",
-                        "--cpu-samples", "4"], capture_output=True, text=True, timeout=900)
+                        "--cpu-samples", "4", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -132,3 +132,32 @@ def test_bench_hmc_mode_contract():
     assert d["roofline"] is None and d["critical_path"]["bound"] == "latency" and d["critical_path"]["sum_us"] > 0
     assert d["config"]["fused_leapfrog"] is True and d["config"]["hip_graph"] is True and d["chains_gathered"] == 4 and len(d["chains_sha256"]) == 64
     assert abs(d["value"] - 4 * 41 / (d["ms_per_step"] * 41e-3)) < 1e-6 * d["value"]
+
+
+def test_bench_hmc_dump_outputs_reproduce_the_chain_checksums(tmp_path):
+    """`--workload hmc --dump-outputs DIR` writes what the timed chains returned on rank 0 (end states K, accept counts, the
+    per-proposal trace): hashed the way the line's checksums are (chain order; K row + int64 accept count; trace column), the
+    dumped arrays give chains_sha256 and trace_sha256, and the accept counts are the line's."""
+    import hashlib
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "hmc", "--steps", "20", "--warmup", "10",
+                        "--cpu-samples", "0", "--hmc-trace", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["single_chain_latency_ms_per_call"] is None and d["cpu_baseline"] is None
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(got) == {"K", "accept", "trace"} and all(a.dtype == np.float64 for a in got.values())
+    K, acc, trace = got["K"], got["accept"].astype(np.int64), got["trace"]
+    C = d["config"]["chains"]
+    assert K.shape[0] == C == len(acc) and trace.shape == (d["config"]["proposals"] + 1, C, K.shape[1])
+    assert acc.tolist() == d["config"]["accepted_all_chains"]
+    h = hashlib.sha256()
+    for c in range(C):
+        h.update(np.ascontiguousarray(K[c]).tobytes()); h.update(np.int64(acc[c]).tobytes())
+    assert h.hexdigest() == d["chains_sha256"]
+    ht = hashlib.sha256()
+    for c in range(C):
+        ht.update(np.ascontiguousarray(trace[:, c]).tobytes())
+    assert ht.hexdigest() == d["trace_sha256"]

@@ -234,6 +234,35 @@ def test_global_input_streams_do_not_depend_on_the_shard_cut():
         assert gen(3, 500, 500, dim).shape == (0, dim)
 
 
+def test_bench_dump_outputs_caps_the_size_with_a_fixed_row_sample(tmp_path):
+    """bench.dump_outputs: float64 .npy files; beyond the byte limit every array keeps the same seeded row sample (indices beside
+    it), the same from call to call, and the files on disk -- headers, index files and unsampled one-row arrays included -- stay
+    within the limit.  The default limit is 64 MB in the decimal sense."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    assert b.DUMP_LIMIT_BYTES <= 64_000_000
+    rng = np.random.default_rng(0)
+    arrays = {"qoi": rng.standard_normal((1000, 9)), "info": np.zeros(1000, np.int32), "one": np.ones((1, 300)),
+              "scalar": np.float64(3.0), "none": None}
+    b.dump_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["info.npy", "one.npy", "qoi.npy", "scalar.npy"]
+    q = np.load(tmp_path / "all" / "qoi.npy")
+    assert q.dtype == np.float64 and np.array_equal(q, arrays["qoi"]) and np.load(tmp_path / "all" / "info.npy").dtype == np.float64
+    limit = 40000
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), arrays, limit=limit)
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").glob("*.npy")) <= limit
+    rows = np.load(tmp_path / "a" / "qoi_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "qoi.npy"), arrays["qoi"][rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "one.npy"), arrays["one"]) and not (tmp_path / "a" / "one_rows.npy").exists()
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    with pytest.raises(ValueError):
+        b.dump_outputs(str(tmp_path / "c"), arrays, limit=4 * b.NPY_HEADER_BYTES)
+
+
 def test_reference_import_paths_resolve():
     """`from fom.forward_solve import Fin` etc. (the reference's import paths) resolve to the HIP-backed classes."""
     from fom.forward_solve import Fin

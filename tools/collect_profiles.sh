@@ -10,7 +10,7 @@ tag=${1:-run}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-B="bench.py --steps 3 --warmup 1 --cpu-samples 0 --no-host-io --no-other"
+B="bench.py --steps 3 --warmup 1 --full --cpu-samples 0 --no-host-io --no-other"
 B1="bench.py --steps 1 --warmup 1 --cpu-samples 0 --no-profile"
 C3="--params nine --r 120"
 C4="--params field --m 20 --r 200 --samples 20000"
@@ -44,13 +44,13 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
 done
 echo "[6] offline/online form, HMC rehearsal, full cfg4 shard"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/oo_overlapped -o run -- python $B --projection offline_online > $out/bench_oo_overlapped.log 2>&1 || exit 1
-python bench.py --workload hmc --steps 10000 --warmup 100 --hmc-trace > $out/bench_hmc.log 2>&1 || exit 1      # (with cpu_baseline: default --cpu-samples)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/hmc -o run -- python bench.py --workload hmc --steps 1000 --warmup 50 --cpu-samples 0 > $out/bench_hmc_traced.log 2>&1 || exit 1
+python bench.py --workload hmc --steps 10000 --warmup 100 --hmc-trace --full > $out/bench_hmc.log 2>&1 || exit 1      # (with cpu_baseline: default --cpu-samples)
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/hmc -o run -- python bench.py --workload hmc --steps 1000 --warmup 50 --full --cpu-samples 0 > $out/bench_hmc_traced.log 2>&1 || exit 1
 python tools/hmc_timeline.py $out/hmc/run_kernel_trace.csv > $out/hmc_timeline.txt 2>&1; rm -f $out/hmc/run_kernel_trace.csv
-python bench.py --steps 2 --warmup 1 --cpu-samples 0 --no-host-io --no-other --params field --m 20 --r 200 --samples 125000 > $out/bench_c4_full.log 2>&1 || exit 1
-FINROM_NO_OVERLAP=1 python bench.py --steps 2 --warmup 1 --cpu-samples 0 --no-host-io --no-other --params field --m 20 --r 200 --samples 125000 > $out/bench_c4_full_in_turn.log 2>&1 || exit 1
-echo "[7] the driver's own command"
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_final.log 2>&1 || exit 1
-python bench.py --gpus 1 --steps 20 --warmup 5 --stream default --cpu-samples 0 --no-other > $out/bench_final_default_stream.log 2>&1 || exit 1
+python bench.py --steps 2 --warmup 1 --full --cpu-samples 0 --no-host-io --no-other --params field --m 20 --r 200 --samples 125000 > $out/bench_c4_full.log 2>&1 || exit 1
+FINROM_NO_OVERLAP=1 python bench.py --steps 2 --warmup 1 --full --cpu-samples 0 --no-host-io --no-other --params field --m 20 --r 200 --samples 125000 > $out/bench_c4_full_in_turn.log 2>&1 || exit 1
+echo "[7] the driver's own command, with the extra passes (--full)"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_final.log 2>&1 || exit 1
+python bench.py --gpus 1 --steps 20 --warmup 5 --stream default --full --cpu-samples 0 --no-other > $out/bench_final_default_stream.log 2>&1 || exit 1
 python tools/pmc_summary.py $out > $out/summary.log 2>&1
 cat $out/summary.log

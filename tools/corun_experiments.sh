@@ -8,7 +8,7 @@ out=${1:-gpurun_out/corun}
 mkdir -p $out
 run() {
   tag=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --steps 5 --warmup 2 --cpu-samples 0 --no-host-io --no-other > $out/$tag.json 2> $out/$tag.err || { echo "$tag failed"; tail -3 $out/$tag.err; return 1; }
+  env "$@" timeout -k 10 200 python bench.py --steps 5 --warmup 2 --full --cpu-samples 0 --no-host-io --no-other > $out/$tag.json 2> $out/$tag.err || { echo "$tag failed"; tail -3 $out/$tag.err; return 1; }
   python - $out/$tag.json $tag <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
