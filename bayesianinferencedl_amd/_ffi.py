@@ -133,6 +133,8 @@ SIGNATURES = {
     "finrom_sampler_destroy": (None, [C.c_void_p]),
     "finrom_sampler_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_sampler_draw_seeded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_sampler_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "finrom_sampler_pullback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_mlp_create": (C.c_int, [C.POINTER(MlpDesc), C.POINTER(C.c_void_p)]),
     "finrom_mlp_destroy": (None, [C.c_void_p]),
     "finrom_mlp_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -141,6 +143,8 @@ SIGNATURES = {
     "finrom_hmc_leapfrog": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_end": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p]),
+    "finrom_hmc_leapfrog_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_solve_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8),
     "finrom_sub": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_comm_unique_id": (C.c_int, [C.c_void_p]),

@@ -5,9 +5,15 @@ drives through the reference's Theano op (bayesian_inference/pymc_func_bayes_inv
 
 PyMC3 / Theano are control plane and out of scope; what the hot path needs from them is the leapfrog recursion
 that makes every evaluation's input depend on the previous evaluation's gradient.  This module is that recursion and
-nothing more: fixed-length leapfrog trajectories with a Metropolis test, an i.i.d. Gaussian prior around a mean field (the
-reference's Matern-5/2 latent GP would add a dense n x n triangular solve per step on the HOST, which is not the path
-measured here), independent chains seeded `seed + chain`.
+nothing more: fixed-length leapfrog trajectories with a Metropolis test, independent chains seeded `seed + chain`, and one of
+two priors:
+  * default: an i.i.d. Gaussian prior N(mean, tau^2) per node (the form BASELINE configs[4] measures);
+  * `prior=GaussianFieldPrior(V)` (gaussian_field.py): the reference's own prior, a latent Matern-5/2 Gaussian field
+    (`pm.gp.Latent(Matern52(2, ls=1.2)).prior`, :191-201), sampled as PyMC3 samples it -- non-centred, in whitened coordinates:
+    the chains move v ~ N(0, I), the field is k = mean + U^T v (U the upper Cholesky factor of the covariance), the potential is
+    misfit(k) / sigma^2 + |v|^2 / 2 and its gradient v + U grad_k / sigma^2.  The value-and-gradient call still receives fields
+    and returns field-space gradients; on the device the two dense triangular products around it are library kernels
+    (finrom_sampler_field / _pullback; fused: finrom_hmc_leapfrog_field).
 
 Chains are independent, so C chains may advance in LOCKSTEP: one device call evaluates the current leapfrog point of every
 chain (a batch of C samples), each chain keeping its own momentum, random stream and accept/reject decision.  On N GPUs a
@@ -29,18 +35,49 @@ def potential(loss, grad, K, mean, sigma, tau):
     return U, np.asarray(grad, dtype=np.float64) / sigma ** 2 + d / tau ** 2
 
 
+def whitened_potential(value_and_grad, prior, sigma):
+    """The potential of chains in whitened coordinates under a GaussianFieldPrior, row-wise for a batch V [C, n]:
+    U(v) = loss(k) / sigma^2 + |v|^2 / 2 and grad U = v + prior.pullback(grad_k) / sigma^2, k = prior.field(v).
+    value_and_grad receives the fields k and returns (loss, field-space gradient, bad) as for run_chains.
+    Returns f(V) -> (U, dU, K, loss, grad_k, bad)."""
+    def f(V):
+        K = prior.field(V)
+        loss, grad, bad = value_and_grad(K)
+        U, dU = potential(loss, prior.pullback(grad), V, 0.0, sigma, 1.0)
+        return U, dU, K, loss, grad, bad
+    return f
+
+
+def _check_prior(prior, mean, who):
+    if prior is not None and mean is not None:
+        raise ValueError(f"{who}: with a prior the chains start from whitened points and the field's mean is the prior's (mean=None)")
+
+
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False):
+               keep_trace=False, prior=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
     samples whose reduced operator was not positive definite (treated as infinite potential: the proposal is rejected).
     record: optional set of evaluation indices whose (input, loss, gradient) are kept for parity checks.
-    Returns HmcResult(K [C, n] final states, accept [C] accepted proposals, proposals, n_evals (per chain),
-    trace [proposals + 1, C, n] if keep_trace, recorded = list of (eval index, K copy, loss, grad) for parity checks)."""
+    prior: None (i.i.d. N(mean, tau^2) per node; mean None: the start points) or a GaussianFieldPrior: then K0 holds WHITENED
+    start points v (prior.whiten of a field), mean must be None (the prior carries it) and tau is unused; value_and_grad still
+    receives fields, and `recorded` still holds (field, loss, field gradient).
+    Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
+    trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
+    with a prior also V [C, n], the whitened final states)."""
+    _check_prior(prior, mean, "run_chains")
     K = np.array(K0, dtype=np.float64, copy=True)
     C, n = K.shape
-    mean = K.copy() if mean is None else np.broadcast_to(np.asarray(mean, dtype=np.float64), K.shape)
+    if prior is None:
+        mean = K.copy() if mean is None else np.broadcast_to(np.asarray(mean, dtype=np.float64), K.shape)
+
+        def pot(Kq):
+            loss, grad, bad = value_and_grad(Kq)
+            U, dU = potential(loss, grad, Kq, mean, sigma, tau)
+            return U, dU, Kq, loss, grad, bad
+    else:
+        pot = whitened_potential(value_and_grad, prior, sigma)
     rngs = [np.random.default_rng(s) for s in seeds]
     assert len(rngs) == C
     recorded = []
@@ -48,11 +85,10 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
 
     def evaluate(Kq):
         nonlocal evals
-        loss, grad, bad = value_and_grad(Kq)
+        U, dU, Fq, loss, grad, bad = pot(Kq)
         if record is not None and evals in record:
-            recorded.append((evals, Kq.copy(), np.array(loss, copy=True), np.array(grad, copy=True)))
+            recorded.append((evals, Fq.copy(), np.array(loss, copy=True), np.array(grad, copy=True)))
         evals += 1
-        U, dU = potential(loss, grad, Kq, mean, sigma, tau)
         bad = np.asarray(bad, dtype=bool) | ~np.isfinite(U)
         U = np.where(bad, np.inf, U)
         dU = np.where(bad[:, None], 0.0, dU)
@@ -82,6 +118,9 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         proposals += 1
         if keep_trace:
             trace.append(K.copy())
+    if prior is not None:                                            # the states are v: report fields, and v beside them
+        return HmcResult(K=prior.field(K), V=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
+                         trace=prior.field(np.stack(trace)) if keep_trace else None)
     return HmcResult(K=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
                      trace=np.stack(trace) if keep_trace else None)
 
@@ -95,14 +134,17 @@ def romml_value_and_grad(solver_r):
 
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                     keep_trace=False, graph=True, data=None, block=32):
+                     keep_trace=False, graph=True, data=None, block=32, prior=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
     1 + 4 n_leapfrog + 2 launches, captured once and replayed.  Same random numbers, same order of evaluations and the same chains
     as `run_chains` (the host recursion) up to the rounding of fused multiply-adds; same return value as `run_chains_device`.
     Raises _ffi.FinromError (FINROM_ERR_UNSUPPORTED) where the library has no one-sample form for the model -- callers fall back to
-    `run_chains_device(..., fused=False)`."""
+    `run_chains_device(..., fused=False)`.
+    prior: a GaussianFieldPrior -- the state is whitened (K0 = v, mean None, tau unused) and a leapfrog step is
+    finrom_hmc_leapfrog_field: field kernel, the plain finrom_romml_grad launches at the field, pullback kernel with the momentum
+    update; finrom_hmc_begin / _end unchanged (mean 0, c_pri 1).  The trace is mapped to fields after the run."""
     import ctypes as C
     import torch
     from .. import _ffi
@@ -114,9 +156,16 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     dev = torch.device("cuda", torch.cuda.current_device())
     f64 = dict(dtype=torch.float64, device=dev)
     i64 = dict(dtype=torch.int64, device=dev)
+    _check_prior(prior, mean, "run_chains_fused")
     K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
     Cn, n = K.shape
-    mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (Cn, n)).copy(), **f64)
+    if prior is not None:                                            # whitened: N(0, I), c_pri = 1
+        mean_t, tau = torch.zeros_like(K), 1.0
+        fs = prior.device()
+        fmean = torch.as_tensor(prior.mean, **f64)
+        F, grad_f = torch.zeros_like(K), torch.zeros_like(K)         # the step's field and misfit gradient
+    else:
+        mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (Cn, n)).copy(), **f64)
     data_np = np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64)
     data_t = torch.as_tensor(data_np, **f64)
     per_sample = 1 if data_np.ndim == 2 else 0
@@ -145,6 +194,12 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         return torch.cuda.current_stream().cuda_stream
 
     def leap(state, step, want_grad=False):
+        if prior is not None:
+            _ffi.check(L.finrom_hmc_leapfrog_field(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
+                                                   C.byref(state), step, data_t.data_ptr(), per_sample, None, None, stream()),
+                       "finrom_hmc_leapfrog_field")
+            Sop.used_on(stream())
+            return
         _ffi.check(L.finrom_hmc_leapfrog(rom._h, mlp._h, Sop.ptr, C.byref(state), step, data_t.data_ptr(), per_sample,
                                          grad_rec.data_ptr() if want_grad else None, None, None, stream()), "finrom_hmc_leapfrog")
         Sop.used_on(stream())
@@ -154,7 +209,10 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     def note(step):
         nonlocal evals
         if record is not None and evals in record:
-            recorded.append((evals, Kq[(step + 1) & 1].cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_rec.cpu().numpy().copy()))
+            if prior is not None:
+                recorded.append((evals, F.cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_f.cpu().numpy().copy()))
+            else:
+                recorded.append((evals, Kq[(step + 1) & 1].cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_rec.cpu().numpy().copy()))
         evals += 1
 
     def proposal(rec=False):
@@ -212,12 +270,24 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                 g.replay() if g is not None else proposal()
                 evals += n_leapfrog
         done += nb
+    if prior is not None:
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
                      trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True)
 
 
+def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
+    """Device chains under a prior: the whitened end states V and trace mapped to fields by the library, after the run (outside
+    any replayed graph)."""
+    n = V.shape[1]
+    K = fs.field(V, mean=fmean)
+    tr = fs.field(trace.reshape(-1, n), mean=fmean).reshape(trace.shape) if trace is not None else None
+    return HmcResult(K=K.cpu().numpy(), V=V.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals,
+                     recorded=recorded, trace=tr.cpu().numpy() if tr is not None else None, **kw)
+
+
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                      keep_trace=False, graph=True, data=None, block=32, fused=None):
+                      keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -232,6 +302,9 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     Proposals that contain an evaluation index listed in `record` run the same operations in stream order, step by step, so that
     the evaluation's input, loss and gradient can be copied out.  graph=False: everything in stream order.
 
+    prior: a GaussianFieldPrior (run_chains: K0 whitened, mean None, tau unused); every evaluation is FieldSampler.field, the
+    romml call at the field, FieldSampler.pullback of its gradient (fused: finrom_hmc_leapfrog_field); K and trace are fields, V the
+    whitened end states.
     Same chains as run_chains(romml_value_and_grad(solver_r), ...) up to the rounding of the elementwise updates.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     import torch
@@ -241,15 +314,22 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         from .. import _ffi
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
-                                    mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block)
+                                    mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
+                                    prior=prior)
         except _ffi.FinromError:
             if fused:
                 raise
+    _check_prior(prior, mean, "run_chains_device")
     dev = torch.device("cuda", torch.cuda.current_device())
     f64 = dict(dtype=torch.float64, device=dev)
     K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
     C, n = K.shape
-    mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
+    if prior is not None:                                            # whitened: N(0, I), c_pri = 1
+        mean_t, tau = torch.zeros_like(K), 1.0
+        fs = prior.device()
+        fmean = torch.as_tensor(prior.mean, **f64)
+    else:
+        mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
     data_t = torch.as_tensor(np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64), **f64)
     rngs = [np.random.default_rng(s) for s in seeds]
     assert len(rngs) == C
@@ -269,11 +349,13 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
 
     def evaluate():
         """dUq (= grad U / c_pri), out <- value and gradient at Kq (all static tensors: the same buffers at every call once captured)."""
-        res = solver_r.grad_romml_batch(Kq, data=data_t)
+        Fq = fs.field(Kq, mean=fmean) if prior is not None else Kq  # (with a prior, Kq is v and the misfit is taken at its field)
+        res = solver_r.grad_romml_batch(Fq, data=data_t)
+        gq = fs.pullback(res["grad"]) if prior is not None else res["grad"]
         torch.sub(Kq, mean_t, out=D)
-        torch.add(D, res["grad"], alpha=c_lik / c_pri, out=dUq)     # dU / c_pri (one kernel; c_pri rides in the momentum updates' alpha)
+        torch.add(D, gq, alpha=c_lik / c_pri, out=dUq)              # dU / c_pri (one kernel; c_pri rides in the momentum updates' alpha)
         dUq.masked_fill_(res["info"].ne(0)[:, None], 0.0)           # an indefinite reduced operator: no force, rejected below
-        out["loss"], out["grad"], out["info"] = res["loss"], res["grad"], res["info"]
+        out["loss"], out["grad"], out["info"], out["field"] = res["loss"], res["grad"], res["info"], Fq
 
     def step():
         Kq.add_(Pq, alpha=eps)
@@ -292,7 +374,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     def note():
         nonlocal evals
         if record is not None and evals in record:
-            recorded.append((evals, Kq.cpu().numpy().copy(), out["loss"].cpu().numpy().copy(), out["grad"].cpu().numpy().copy()))
+            recorded.append((evals, out["field"].cpu().numpy().copy(), out["loss"].cpu().numpy().copy(), out["grad"].cpu().numpy().copy()))
         evals += 1
 
     def proposal(hook=None):
@@ -365,5 +447,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
                 g.replay() if g is not None else proposal()
                 evals += n_leapfrog
         done += nb
+    if prior is not None:
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
                      trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False)

@@ -221,7 +221,10 @@ struct finrom_rom_s {
   const MlpBackFuse* back = nullptr;   // (same path) its walk back through the hidden layers as a workgroup of the gradient contraction
   bool info_store = false;             // (same path) the solve kernel stores info instead of or-ing into it
 };
-struct finrom_sampler_s { double* U = nullptr; int n = 0; Scratch xi; };
+struct finrom_sampler_s {
+  double* U = nullptr; int n = 0; Scratch xi;
+  Scratch fpart, ftick;                // finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field: partial sums, arrival counters
+};
 struct finrom_mlp_s {
   MlpDev d{}; std::vector<void*> owned; Scratch tape, theta, gth, shift, qtmp, etmp, g0, y0p, thp;
   // finrom_hmc_leapfrog: the partial sums of theta the last step left in thp, and the field they belong to (position buffer,
@@ -1811,7 +1814,7 @@ int finrom_sampler_create(const double* U, int32_t n, finrom_sampler_t* out) {
   *out = h;
   return 0;
 }
-void finrom_sampler_destroy(finrom_sampler_t h) { if (!h) return; dev_free(h->U); h->xi.release(); delete h; }
+void finrom_sampler_destroy(finrom_sampler_t h) { if (!h) return; dev_free(h->U); h->xi.release(); h->fpart.release(); h->ftick.release(); delete h; }
 int finrom_sampler_draw(finrom_sampler_t h, const double* xi, int64_t S, double* k, void* stream) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!xi || !k))) { set_error("sampler_draw: bad argument"); return FINROM_ERR_ARG; }
@@ -1834,6 +1837,31 @@ int finrom_sampler_draw_seeded(finrom_sampler_t h, uint64_t seed, int64_t first_
     if (rc) return rc;
   }
   return 0;
+}
+
+// the two triangular products' workspace on the handle (field_prior.hip): grown outside a capture only (Scratch::reserve refuses
+// it inside one, with a message); the arrival counters are zeroed once, the kernels leave them zero
+static int field_prior_ws(finrom_sampler_t h, int64_t S) {
+  const bool fresh = h->ftick.p == nullptr;
+  if (int rc = h->ftick.reserve(field_prior_tick_bytes(h->n))) return rc;
+  if (fresh) FR_HIP(hipMemset(h->ftick.p, 0, field_prior_tick_bytes(h->n)));
+  return h->fpart.reserve(field_prior_part_bytes(h->n, S));
+}
+int finrom_sampler_field(finrom_sampler_t h, const double* mean, const double* v, int64_t S, double* k, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (!h || S < 0 || (S > 0 && (!v || !k))) { set_error("sampler_field: bad argument (null handle, v or k, or S < 0)"); return FINROM_ERR_ARG; }
+  if (S == 0) return 0;
+  if (int rc = field_prior_ws(h, S)) return rc;
+  return launch_field_prior(h->U, h->n, 0, v, nullptr, 0.0, mean, k, nullptr, nullptr, S, (double*)h->fpart.p, (int*)h->ftick.p,
+                            (hipStream_t)stream);
+}
+int finrom_sampler_pullback(finrom_sampler_t h, const double* g, int64_t S, double* out, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (!h || S < 0 || (S > 0 && (!g || !out))) { set_error("sampler_pullback: bad argument (null handle, g or out, or S < 0)"); return FINROM_ERR_ARG; }
+  if (S == 0) return 0;
+  if (int rc = field_prior_ws(h, S)) return rc;
+  return launch_field_prior(h->U, h->n, 1, g, nullptr, 0.0, nullptr, out, nullptr, nullptr, S, (double*)h->fpart.p, (int*)h->ftick.p,
+                            (hipStream_t)stream);
 }
 
 int finrom_mlp_create(const finrom_mlp_desc* a, finrom_mlp_t* out) {
@@ -1996,6 +2024,38 @@ int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, c
   const int rc = romml_grad_impl(rom, mlp, Sop, a->Kq[step & 1], data, data_per_sample, a->C, grad_out, a->loss, qoi_r, e_nn, a->info, stream, &hs);
   if (rc == 0 && hs.tail.theta_parts != nullptr) { mlp->carry_k = hs.k_out; mlp->carry_mom = a->P; mlp->carry_eps = a->eps; mlp->carry_S = a->C; }
   return rc;
+}
+
+// the leapfrog step in whitened coordinates: field kernel (position update in front), the plain romml value and gradient at the
+// field, pullback kernel (momentum update behind); no theta carry (the field is not the position)
+int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior, const double* field_mean,
+                              double* field, double* grad_field, const finrom_hmc_state* a, int32_t step, const double* data,
+                              int32_t data_per_sample, double* qoi_r, double* e_nn, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_leapfrog_field")) return rc;
+  if (a->c_pri != 1.0) { set_error("hmc_leapfrog_field: c_pri must be 1 (whitened coordinates: the prior of v is N(0, I))"); return FINROM_ERR_ARG; }
+  if (step < 0) { set_error("hmc_leapfrog_field: step < 0"); return FINROM_ERR_ARG; }
+  if (!rom || !mlp || !Sop || !prior) { set_error("hmc_leapfrog_field: null rom, mlp, Sop or prior handle"); return FINROM_ERR_ARG; }
+  if (!field || !grad_field || !data) { set_error("hmc_leapfrog_field: null field, grad_field or data"); return FINROM_ERR_ARG; }
+  if (a->n != prior->n || a->n != mlp->d.n_in) {
+    set_error("hmc_leapfrog_field: n = " + std::to_string(a->n) + " is not the prior's (" + std::to_string(prior->n) +
+              ") or the error model's input size (" + std::to_string(mlp->d.n_in) + ")");
+    return FINROM_ERR_ARG;
+  }
+  mlp->carry_k = nullptr;                  // (a theta carry of finrom_hmc_leapfrog does not survive a step of this form)
+  if (a->C == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = field_prior_ws(prior, a->C)) return rc;
+  double* vq = a->Kq[(step + 1) & 1];
+  int rc = launch_field_prior(prior->U, prior->n, 0, a->Kq[step & 1], a->P, a->eps, field_mean, field, vq, nullptr, a->C,
+                              (double*)prior->fpart.p, (int*)prior->ftick.p, st);
+  if (!rc) rc = romml_grad_impl(rom, mlp, Sop, field, data, data_per_sample, a->C, grad_field, a->loss, qoi_r, e_nn, a->info, stream, nullptr);
+  if (rc) return rc;
+  FieldPriorTail tl;
+  tl.vq = vq; tl.c_lik = a->c_lik; tl.info = a->info; tl.mom = a->P; tl.dU = a->dUq; tl.eps = a->eps;
+  return launch_field_prior(prior->U, prior->n, 1, grad_field, nullptr, 0.0, nullptr, nullptr, nullptr, &tl, a->C,
+                            (double*)prior->fpart.p, (int*)prior->ftick.p, st);
 }
 
 int finrom_sub(const double* a, const double* b, int64_t count, double* out, void* stream) {

@@ -74,6 +74,18 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
 
+// ---- latent Gaussian-field prior (field_prior.hip, finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field) --------------
+// the pullback's epilogue in a whitened leapfrog step (c_pri = 1):  dU = vq + c_lik g_v (0 for a flagged sample);  mom -= eps dU
+struct FieldPriorTail {
+  const double* vq = nullptr; double c_lik = 0.0; const int* info = nullptr; double* mom = nullptr; double* dU = nullptr;
+  double eps = 0.0;
+};
+size_t field_prior_part_bytes(int n, int64_t S);     // the partial-sum workspace of a call with S rows
+size_t field_prior_tick_bytes(int n);                // its arrival counters (zero between calls)
+// pull = 0: out = mean + U^T (x + eps p) (mean, p optional; v_out = x + eps p optional);  pull = 1: out = U x (out optional), tail
+int launch_field_prior(const double* U, int n, int pull, const double* x, const double* p, double eps, const double* mean,
+                       double* out, double* v_out, const FieldPriorTail* tail, int64_t S, double* part, int* tick, hipStream_t st);
+
 // ---- ROM ------------------------------------------------------------------------------
 constexpr int ROM_MAX_PHASES = 8;
 struct RomDev {

@@ -1,7 +1,8 @@
 // The trajectory bookkeeping of the HMC rehearsal (BASELINE configs[4]) on the device, so that a proposal is library launches
 // only: what PyMC3's sampler does around the reference's value-and-gradient op (bayesian_inference/pymc_func_bayes_inverse.py:
 // 148-167 `SqErrorOpROMML.perform` / `.grad`, model :186-203) -- draw a momentum, leapfrog, Metropolis test -- restated for the
-// i.i.d. Gaussian prior of bayesian_inference/hmc.py.  One workgroup per chain; sums over the field in a fixed order.
+// i.i.d. Gaussian prior of bayesian_inference/hmc.py (with mean 0 and c_pri = 1 also the whitened form of the latent Gaussian-field
+// prior, finrom_hmc_leapfrog_field).  One workgroup per chain; sums over the field in a fixed order.
 #include "finrom_internal.h"
 
 namespace finrom {

@@ -509,6 +509,33 @@ class FieldSampler:
         check(lib().finrom_sampler_draw(self._h, b.ptr, b.S, kp, b.stream), "finrom_sampler_draw")
         return b.out(k, (b.S, self.n))
 
+    def field(self, v, mean=None):
+        """k = mean + v @ U row-wise (finrom_sampler_field): the latent Gaussian field of the whitened variable v [S, n] without
+        the exp of __call__.  mean: [n] or None (zero).  NumPy in -> NumPy out; a float64 CUDA tensor in -> a tensor on its device,
+        launched on torch's current stream (mean then a tensor on that device, or anything torch.as_tensor takes)."""
+        b = _Batch(v, self.n)
+        mp, mb = None, None
+        if mean is not None:
+            if b.torch:
+                import torch
+                mean = torch.as_tensor(mean, dtype=torch.float64, device=b.device)
+            elif _is_torch(mean):
+                mean = mean.detach().cpu().numpy()
+            mb = _Batch(mean, self.n)
+            if mb.S != 1:
+                raise ValueError("field: mean must be one field of %d values" % self.n)
+            mp = mb.ptr
+        k, kp = b.new((b.S, self.n), zero=False)
+        check(lib().finrom_sampler_field(self._h, mp, b.ptr, b.S, kp, b.stream), "finrom_sampler_field")
+        return b.out(k, (b.S, self.n))
+
+    def pullback(self, g):
+        """U g row-wise (finrom_sampler_pullback): the gradient g [S, n] of a function of the field as a gradient in v."""
+        b = _Batch(g, self.n)
+        out, op = b.new((b.S, self.n), zero=False)
+        check(lib().finrom_sampler_pullback(self._h, b.ptr, b.S, op, b.stream), "finrom_sampler_pullback")
+        return b.out(out, (b.S, self.n))
+
     def draw(self, seed, first, S, like=None, want_xi=False):
         """S fields of the stream `seed` starting at GLOBAL sample index `first`, xi drawn on the device (Philox keyed by the
         global index: independent of how a dataset is sharded).  like: a torch CUDA tensor (-> torch outputs on its device /

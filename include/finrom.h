@@ -396,7 +396,9 @@ int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, con
  *                        behind the gradient; loss [C] and info [C] of the state are overwritten; grad_out [C x n] optional;
  *   finrom_hmc_end       after n_steps steps: last half step back, U(k) = c_lik loss + c_pri |k - mean|^2 / 2 (inf if flagged),
  *                        Metropolis test log u < H0 - H1, state update, accept counters, optional trace row, *jt += 1, *pt += 1.
- * Potential: i.i.d. Gaussian prior N(mean, 1 / c_pri) per node, likelihood scale c_lik = 1 / sigma^2.  All arrays are DEVICE
+ * Potential: i.i.d. Gaussian prior N(mean, 1 / c_pri) per node, likelihood scale c_lik = 1 / sigma^2.  (The reference's own prior,
+ * a latent Gaussian field k = mean + U^T v with v ~ N(0, I), is finrom_hmc_leapfrog_field below: the same state in whitened
+ * coordinates, mean = 0 and c_pri = 1, so that finrom_hmc_begin / _end compute its Hamiltonian unchanged.)  All arrays are DEVICE
  * pointers owned by the caller; C <= 64 chains advance in lockstep (one sample of the batch each); needs finrom_rom_set_gradient,
  * the direct projection, P <= 16 and a basis the one-sample pipeline serves (r <= 96) -- FINROM_ERR_UNSUPPORTED otherwise. */
 typedef struct {
@@ -415,6 +417,18 @@ int finrom_hmc_begin(const finrom_hmc_state* st, void* stream);
 int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const finrom_hmc_state* st, int32_t step,
                         const double* data, int32_t data_per_sample, double* grad_out, double* qoi_r, double* e_nn, void* stream);
 int finrom_hmc_end(const finrom_hmc_state* st, int32_t n_steps, void* stream);
+/* finrom_hmc_leapfrog in WHITENED coordinates under the latent Gaussian-field prior of the reference's model (pm.gp.Latent(Matern52)
+ * .prior, bayesian_inference/pymc_func_bayes_inverse.py:191-201; PyMC3 samples it non-centred): the state's K / Kq / P / dU are
+ * v-space, st->mean must be zeros and st->c_pri == 1; `prior` holds the upper factor U of the field's covariance.
+ *   field [C x n] (out): field_mean [n] (or NULL) + U^T v' of this step;  grad_field [C x n] (out): the misfit gradient at it.
+ * Three pieces in stream order: v' = v + eps p -> field (finrom_sampler_field's kernel, which also writes v' to Kq[(step + 1) & 1]);
+ * the value and gradient of finrom_romml_grad at the field (its plain four launches); dUq = v' + c_lik U grad_field (0 for a flagged
+ * sample) and p -= eps dUq behind the pullback (finrom_sampler_pullback's kernel).  The workspace lives on `prior`: run one step
+ * with the same C before a capture.  Needs the prior's n and the error model's n_in to be st->n (FINROM_ERR_ARG otherwise). */
+int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior,
+                              const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* st,
+                              int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
+                              void* stream);
 
 /* ---- sub-fin averages  theta = S k  (fom :466-480, rom :404-418) -------------------- *
  * Sop is the dense [P x n] averaging operator on the device (finrom_malloc + h2d). */
@@ -433,6 +447,15 @@ int finrom_sampler_draw(finrom_sampler_t h, const double* xi, int64_t S, double*
  * the stream `seed` is the same numbers whatever shard or GPU draws it.  k [S x n]; xi_out [S x n] or NULL. */
 int finrom_sampler_draw_seeded(finrom_sampler_t h, uint64_t seed, int64_t first_global_sample, int64_t S, double* k,
                                double* xi_out, void* stream);
+/* The latent Gaussian field's two triangular products with the same factor (HMC under the reference's prior, hmc.py), any S:
+ *   finrom_sampler_field     k = mean + U^T v   (mean [n] device or NULL; v, k [S x n] device) -- the map of finrom_sampler_draw
+ *                            without the exp;
+ *   finrom_sampler_pullback  out = U g          (g, out [S x n] device) -- the gradient of a field-space function pulled back to v.
+ * Deterministic: every output is summed in an order set by n alone, and row s does not depend on the other rows of the batch
+ * (a chain alone and the same chain in a batch are bit-identical).  Partial sums live in a workspace on the handle, grown outside
+ * a stream capture only; calls on one handle must be ordered (one stream, or events). */
+int finrom_sampler_field(finrom_sampler_t h, const double* mean, const double* v, int64_t S, double* k, void* stream);
+int finrom_sampler_pullback(finrom_sampler_t h, const double* g, int64_t S, double* out, void* stream);
 
 /* ---- the dataset-loop body for S samples in one call ---------------------------------- *
  * (deep_learning/generate_fin_dataset.py:93-100):  FOM solve + QoI on the caller's stream;
