@@ -156,7 +156,7 @@ SIGNATURES = {
 ABI_VERSION = 12
 # finrom_fom_last_path codes (include/finrom.h)
 FOM_PATHS = {0: "none", 1: "small_lds", 2: "small_global", 3: "interpreter", 4: "band_registers", 5: "band_lds_4wave",
-             6: "band_lds_1wave", 7: "band_registers_qoi", 8: "band_lds_4wave_qoi"}
+             7: "band_registers_qoi", 8: "band_lds_4wave_qoi"}
 
 _lib = None
 

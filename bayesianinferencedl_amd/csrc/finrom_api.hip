@@ -168,7 +168,7 @@ struct finrom_fom_s {
 struct finrom_rom_s {
   RomDev d{};
   std::vector<void*> owned;
-  Scratch Ar, Br, theta, qtmp, vw, ticket, grad_ticket, part, ext;
+  Scratch Ar, Br, theta, qtmp, vw, grad_ticket, part, ext;
   int g_npairs = 0; const int* g_pair_p = nullptr; const int* g_pair_i = nullptr; const double* g_Gt = nullptr;
   RomGramDev gram;                     // offline/online form (finrom_rom_set_gram); gram.h is filled at create
   int projection = FINROM_PROJECTION_DIRECT;
@@ -191,14 +191,7 @@ struct finrom_rom_s {
     if (cus < 0) cus = -cus * (ncu / 8);                 // (eight CUs per shader engine on gfx950)
     if (cus < 1 || cus > ncu) { set_error("FINROM_FOM_CUS out of range"); return FINROM_ERR_ARG; }
     std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    const int mode = getenv("FINROM_FOM_CUS_MODE") != nullptr ? atoi(getenv("FINROM_FOM_CUS_MODE")) : 1;
-    for (int t = 0; t < cus; ++t) {
-      int b = (int)((int64_t)t * ncu / cus);                                     // mode 0: spread evenly over the bit array
-      if (mode == 1) b = t;                                                       // mode 1: the first `cus` bits
-      if (mode == 2) b = (t % 8) * (ncu / 8) + t / 8;                            // mode 2: round robin over eight blocks of ncu / 8 bits
-      if (mode == 3) b = (t % 8) * 32 + t / 8;                                    // mode 3: round robin over 32-bit words (one per XCD?)
-      mask[b >> 5] |= 1u << (b & 31);
-    }
+    for (int b = 0; b < cus; ++b) mask[b >> 5] |= 1u << (b & 31);      // the first `cus` bits
     // (a runtime that refuses the mask is not an error of the call: the FOM half then stays on the caller's stream, as before)
     if (hipExtStreamCreateWithCUMask(&fom_side, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); fom_side = nullptr; fom_side_cus = want; return 0; }
     if (!ev_join_fom) FR_HIP(hipEventCreateWithFlags(&ev_join_fom, hipEventDisableTiming));
@@ -476,19 +469,17 @@ int finrom_fom_create(const finrom_fom_desc* a, finrom_fom_t* out) {
   d.gsize = gsize;
   d.fwd_chunk = a->fwd_chunk;
   d.nchunks_fwd = a->nops_fwd / a->fwd_chunk - 2; d.nchunks_bwd = a->nops_bwd / VM_CHUNK - 2;
-  d.debug_phases = 7; d.trace = nullptr;
+  d.trace = nullptr;
   d.has_grad = 0; d.nchunks_res = 0;
-  if (const char* ph = getenv("FINROM_FOM_PHASES")) d.debug_phases = atoi(ph);
   std::vector<int> fkb(a->nops_fwd), bkb(a->nops_bwd);
   // device encoding of the forward stream: load offsets in bytes, the common multiply-adds (FMA, FMALL) carry the LDS
   // byte offsets of their row-cache slots in kb and d, every other op kind | (b+1) << 8, and one bit mask per chunk flags
   // the slots that are NOT plain multiply-adds (bits 0..15) and the multiply-adds whose second operand is in LDS (bits 16..31)
   std::vector<int> fa2(a->nops_fwd), fd2(a->nops_fwd), fmask(a->nops_fwd / a->fwd_chunk, 0);
-  const bool noload = getenv("FINROM_FOM_NOLOAD") != nullptr;      // timing experiment: no operand fetches (results are garbage)
   for (int t = 0; t < a->nops_fwd; ++t) {
     // ops without a global operand (padding, fused-assembly ops) fetch from beyond the buffer's range: the hardware
     // bounds check returns 0 without touching memory (a real element could be uninitialised: 0 * NaN)
-    fa2[t] = (a->fwd_a[t] < 0 || noload) ? 0x7FFFFFF0 : a->fwd_a[t] * 512;
+    fa2[t] = a->fwd_a[t] < 0 ? 0x7FFFFFF0 : a->fwd_a[t] * 512;
     fd2[t] = a->fwd_d[t];
     // the common multiply-add is acc -= rc[b] * (G[a] + rc[d']): FMA reads the ZERO slot as d', FMALL an out-of-range G[a]
     // the common multiply-add is acc -= rc[b] * (G[a] + rc[d']): FMA reads the ZERO slot as d', FMALL an out-of-range G[a]
@@ -890,7 +881,7 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   if (!rc) rc = up(h->owned, &b.obs_ptr, a->obs_ptr, d.n_obs + 1);
   if (!rc) rc = up(h->owned, &b.obs_idx, a->obs_idx, nobsnz);
   if (!rc) rc = up(h->owned, &b.obs_w, a->obs_w, nobsnz);
-  if (a->qoi_FgQ != nullptr && getenv("FINROM_BAND_NO_QOI_ONLY") == nullptr) {
+  if (a->qoi_FgQ != nullptr) {
     const int nqz = a->qoi_obs_ptr[d.n_obs];
     if (!rc) rc = up(h->owned, &b.FgQ, a->qoi_FgQ, G);
     if (!rc) rc = up(h->owned, &b.row_fin, a->qoi_row_fin, d.n_obs);
@@ -901,8 +892,6 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   }
   if (rc) return rc;
   b.on = getenv("FINROM_BAND_TIMING") != nullptr ? 2 : 1;      // 2: block 0 reports its phase clocks in sample 0's QoI (diagnostic)
-  if (getenv("FINROM_BAND_NOMEM") != nullptr) b.on |= 4;       // timing experiment (m <= 12 kernel): no L / y / w traffic, garbage results
-  if (getenv("FINROM_BAND_PRIO") != nullptr) b.on |= 8 * (atoi(getenv("FINROM_BAND_PRIO")) & 3);      // experiment: s_setprio 1..3 for the sweep's waves (bits 3-4)
   h->band = b;
   return 0;
 }
@@ -1023,7 +1012,7 @@ int finrom_fom_gradient(finrom_fom_t h, const double* x, const double* data, int
   if (!h->d.has_grad && !h->band_grad.on) { set_error("fom_gradient: finrom_fom_set_gradient has not been called"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const FomDev& d = h->d;
-  static const bool env_no_band_grad = getenv("FINROM_NO_BAND_GRAD") != nullptr || getenv("FINROM_NO_BAND") != nullptr;
+  static const bool env_no_band_grad = getenv("FINROM_NO_BAND") != nullptr;
   const bool small = h->small.small_max > 0 && S <= h->small.small_max && d.n_obs <= 64 && d.has_grad;
   if (!small && h->band.on && h->band_grad.on && !env_no_band_grad) {
     // the full band sweep (the factor and w stay in the workspace), then the adjoint solve and the contraction on the same layout
@@ -1240,19 +1229,13 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
   const int r = a->r, NB = (r + 15) / 16, rp = 16 * NB;
   if (NB > 13) { set_error("rom_create: basis size > 208 not supported"); return FINROM_ERR_UNSUPPORTED; }
 
-  // rows sorted by term count (descending) so that the 4 rows of a k-step need the same number
-  // of slots and the k-steps fall into a few phases of constant term count NT
   auto cnt = [&](int row) { return a->row_ptr[row + 1] - a->row_ptr[row]; };
   const std::vector<int> order = rows_by_term_count(a);
-  const int nrows = (int)order.size();
-  const int nk = (nrows + 3) / 4;
   auto* h = new finrom_rom_s();
   RomDev& d = h->d;
   d.n = a->n; d.r = r; d.rp = rp; d.NB = NB; d.P = a->P; d.n_obs = a->n_obs;
   d.solve_in_lds = rp <= 176 ? 1 : 0;
-  d.clock_probe = getenv("FINROM_CLOCK_PROBE") != nullptr ? std::max(1, atoi(getenv("FINROM_CLOCK_PROBE"))) : 0; d.trace = nullptr;
-  d.n_phases = 0;
-  std::vector<double> tv; std::vector<int> pidx;
+  d.trace = nullptr;
   auto push_slot = [&](std::vector<double>& T, std::vector<int>& Pi, const std::vector<int>& rows4, int t) {
     for (int q = 0; q < 4; ++q) {
       const size_t base = T.size();
@@ -1265,28 +1248,8 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
       Pi.push_back(pi);
     }
   };
-  int nslots = 0;
-  for (int ks = 0; ks < nk; ++ks) {
-    std::vector<int> rows4;
-    int nt = 0;
-    for (int q = 0; q < 4; ++q) {
-      const int idx = ks * 4 + q;
-      rows4.push_back(idx < nrows ? order[idx] : -1);
-      if (idx < nrows) nt = std::max(nt, cnt(order[idx]));
-    }
-    if (nt > 4) { delete h; set_error("rom_create: a row of psi has more than 4 terms"); return FINROM_ERR_UNSUPPORTED; }
-    if (d.n_phases == 0 || d.phase_nt[d.n_phases - 1] != nt) {
-      if (d.n_phases == ROM_MAX_PHASES) { delete h; set_error("rom_create: too many phases"); return FINROM_ERR_UNSUPPORTED; }
-      d.phase_nt[d.n_phases] = nt; d.phase_ks0[d.n_phases] = ks; d.phase_slot0[d.n_phases] = nslots;
-      ++d.n_phases;
-    }
-    d.phase_ks1[d.n_phases - 1] = ks + 1;
-    for (int t = 0; t < nt; ++t) push_slot(tv, pidx, rows4, t);
-    nslots += nt;
-  }
   // ---- pattern-uniform k-steps for the single-wave kernels (see RomDev::tvu) ----------------------------------------------
-  std::vector<double> tvu; std::vector<int> kpat, kmeta;
-  d.n_uphases = 0;
+  std::vector<double> tvu; std::vector<int> kmeta;
   {
     std::vector<KStep> ksteps = uniform_ksteps(a, order);
     // every term-count group gets an even number of k-steps (a k-step of zero rows pads it): the multi-wave main loop is
@@ -1305,15 +1268,8 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
     for (size_t k = 0; k < ksteps.size(); ++k) {
       const int nt = (int)ksteps[k].pat.size();
       if (nt > 4) { delete h; set_error("rom_create: a row of psi has more than 4 terms"); return FINROM_ERR_UNSUPPORTED; }
-      if (d.n_uphases == 0 || d.uphase_nt[d.n_uphases - 1] != nt) {
-        if (d.n_uphases == ROM_MAX_PHASES) { delete h; set_error("rom_create: too many phases"); return FINROM_ERR_UNSUPPORTED; }
-        d.uphase_nt[d.n_uphases] = nt; d.uphase_ks0[d.n_uphases] = (int)k; d.uphase_slot0[d.n_uphases] = uslots;
-        ++d.n_uphases;
-      }
-      d.uphase_ks1[d.n_uphases - 1] = (int)k + 1;
       for (int t = 0; t < nt; ++t) {
         const int pp = ksteps[k].pat[t];
-        kpat.push_back(pp);
         for (int q = 0; q < 4; ++q) {
           const size_t base = tvu.size();
           tvu.resize(base + rp, 0.0);
@@ -1340,7 +1296,6 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
       for (int k = 0; k < 8; ++k) { int rec[8] = {uslots, 1, 0, 0, 0, 0, 0, 0}; kmeta.insert(kmeta.end(), rec, rec + 8); }
     }
     tvu.resize(tvu.size() + (size_t)4 * 4 * rp, 0.0);       // one k-step of padding for the prefetch
-    kpat.resize(kpat.size() + 16, 0);                        // the scalar pipeline reads up to two k-steps ahead
     d.tvu_bytes = (int)std::min<size_t>(tvu.size() * sizeof(double), (size_t)0x7FFFFFF0);
 
     // ---- the same k-steps grouped by their leading parameter (build_grouped_tables above; proj_main_grouped, NB <= 5) ------
@@ -1357,38 +1312,6 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
       }
     }
   }
-  // chunk images for the LDS-staged kernel: whole k-steps of one phase, <= 32 KiB, padded to 1 KiB
-  std::vector<int> ch_nt, ch_nks, ch_off, ch_bytes;
-  std::vector<double> tvc;
-  d.n_chunks = 0;
-  if (NB <= 5) {
-    const size_t cap = 24 * 1024;   // = ROM_CHUNK_BYTES (rom_kernels.hip): 2 buffers + theta = 50 KiB per workgroup
-    for (int ph = 0; ph < d.n_phases; ++ph) {
-      const int nt = d.phase_nt[ph];
-      if (nt == 0) continue;
-      const size_t per_ks = (size_t)nt * 4 * rp * 8 + (size_t)nt * 4 * 4;
-      const int max_ks = std::max<int>(1, (int)(cap / per_ks));
-      if (per_ks > cap) { d.n_chunks = 0; ch_nt.clear(); break; }
-      for (int ks = d.phase_ks0[ph]; ks < d.phase_ks1[ph]; ks += max_ks) {
-        const int nks = std::min(max_ks, d.phase_ks1[ph] - ks);
-        const int slot = d.phase_slot0[ph] + (ks - d.phase_ks0[ph]) * nt;
-        const size_t nrows = (size_t)nks * nt * 4;
-        const size_t off = tvc.size();
-        tvc.insert(tvc.end(), tv.begin() + (size_t)slot * 4 * rp, tv.begin() + (size_t)slot * 4 * rp + nrows * rp);
-        const size_t nint = nrows;                      // theta indices, two per double
-        tvc.resize(tvc.size() + (nint + 1) / 2, 0.0);
-        std::memcpy(reinterpret_cast<char*>(tvc.data()) + (off + nrows * rp) * 8, &pidx[(size_t)slot * 4], nint * 4);
-        size_t bytes = (tvc.size() - off) * 8;
-        bytes = (bytes + 1023) / 1024 * 1024;
-        tvc.resize(off + bytes / 8, 0.0);
-        ch_nt.push_back(nt); ch_nks.push_back(nks); ch_off.push_back((int)off); ch_bytes.push_back((int)bytes);
-      }
-    }
-    d.n_chunks = (int)ch_nt.size();
-  }
-  tv.resize(tv.size() + (size_t)4 * 4 * rp, 0.0);          // one k-step of padding for the prefetch
-  pidx.resize(pidx.size() + 16, 0);
-
   // root rows (F != 0) for B_r = psi^T F
   std::vector<int> frows;
   for (int i = 0; i < a->n; ++i) if (a->rhs[i] != 0.0 && cnt(i) > 0) frows.push_back(i);
@@ -1417,18 +1340,8 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
 
   int rc = 0;
   if (!rc) rc = up(h->owned, &h->gram.h, hp.data(), hp.size());
-  if (d.n_chunks > 0) {
-    if (!rc) rc = up(h->owned, &d.ch_nt, ch_nt.data(), ch_nt.size());
-    if (!rc) rc = up(h->owned, &d.ch_nks, ch_nks.data(), ch_nks.size());
-    if (!rc) rc = up(h->owned, &d.ch_off, ch_off.data(), ch_off.size());
-    if (!rc) rc = up(h->owned, &d.ch_bytes, ch_bytes.data(), ch_bytes.size());
-    if (!rc) rc = up(h->owned, &d.tvc, tvc.data(), tvc.size());
-  }
   if (!rc) rc = up(h->owned, &d.tvu, tvu.data(), tvu.size());
-  if (!rc) rc = up(h->owned, &d.kpat, kpat.data(), kpat.size());
   if (!rc) rc = up(h->owned, &d.kmeta, kmeta.data(), kmeta.size());
-  if (!rc) rc = up(h->owned, &d.tv, tv.data(), tv.size());
-  if (!rc) rc = up(h->owned, &d.pidx, pidx.data(), pidx.size());
   if (!rc) rc = up(h->owned, &d.rhs_tv, rtv.data(), rtv.size());
   if (!rc) rc = up(h->owned, &d.rhs_pidx, rpi.data(), rpi.size());
   if (!rc) rc = up(h->owned, &d.rhs_f, rf.data(), rf.size());
@@ -1441,7 +1354,7 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
 void finrom_rom_destroy(finrom_rom_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);
-  h->Ar.release(); h->Br.release(); h->theta.release(); h->qtmp.release(); h->vw.release(); h->ticket.release(); h->grad_ticket.release();
+  h->Ar.release(); h->Br.release(); h->theta.release(); h->qtmp.release(); h->vw.release(); h->grad_ticket.release();
   h->part.release(); h->ext.release();
   if (h->side) defer_or_run([](void* s) { (void)hipStreamDestroy((hipStream_t)s); }, h->side);
   if (h->fom_side) defer_or_run([](void* s) { (void)hipStreamDestroy((hipStream_t)s); }, h->fom_side);
@@ -1510,14 +1423,13 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
                        double* w_r = nullptr, double* qoi_r = nullptr) {
   if (h->projection == FINROM_PROJECTION_GRAM)
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
-  if (h->ticket.reserve(4096 * sizeof(int))) return FINROM_ERR_NOMEM;
   RomDev d = h->d;
   d.ext = nullptr;
   if (d.nkg > 0 && S > 0 && !rom_splitk_applies(d, S)) {      // the grouped main loop: room for the samples' scalars
     if (int rc = h->ext.reserve((size_t)S * d.n_ext * sizeof(double))) return rc;
     d.ext = (double*)h->ext.p;
   }
-  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, (int*)h->ticket.p);
+  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
 }
 
 int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
@@ -1534,8 +1446,7 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     int rc;
     // one-sample call patterns (MAP / HMC: a handful of samples, latency): contraction over several workgroups per sample, then
     // the MFMA-form factorisation + substitutions (rom_onesample.hip)
-    if (A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc) &&
-        getenv("FINROM_NO_FUSED_SOLVE") == nullptr && getenv("FINROM_NO_FUSED_CHOL") == nullptr) {
+    if (A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
       if ((rc = h->part.reserve(rom_onesample_scratch_bytes(d, Sc)))) return rc;
       if ((rc = launch_rom_onesample(d, theta + s0 * d.P, Sc, (double*)h->part.p, 0, RomGradArgs(), w_r ? w_r + s0 * d.r : nullptr,
                                      qoi_r ? qoi_r + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st))) return rc;
@@ -1545,17 +1456,16 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     if ((rc = h->Br.reserve((size_t)Sc * d.rp * sizeof(double)))) return rc;
     // A_r is factored inside the projection kernel (in registers, MFMA trailing updates) unless the caller
     // wants A_r itself back (the state the reference's gradients use) or the basis needs more than one wave
-    const bool want_factor = (A_r == nullptr || getenv("FINROM_DEBUG_RETURN_FACTOR") != nullptr) &&
-                             getenv("FINROM_NO_FUSED_CHOL") == nullptr;   // debug: A_r output then holds L
+    const bool want_factor = A_r == nullptr;
     int factor = (want_factor && d.NB <= 6) ? 1 : 0;                  // in-register, inside the projection kernel
     // ... and when neither A_r nor B_r is wanted back (r <= 80), the two substitutions and the reduced QoI happen there
     // as well: no packed factor in memory, no second kernel
-    if (factor && (d.NB <= 5 || (d.NB == 6 && h->projection == FINROM_PROJECTION_DIRECT && rom_splitk_applies(d, Sc))) && A_r == nullptr && B_r == nullptr && getenv("FINROM_NO_FUSED_SOLVE") == nullptr &&
-        getenv("FINROM_PROJ_LDS") == nullptr) factor = 2;
+    if (factor && (d.NB <= 5 || (d.NB == 6 && h->projection == FINROM_PROJECTION_DIRECT && rom_splitk_applies(d, Sc))) && A_r == nullptr && B_r == nullptr)
+      factor = 2;
     // wider bases, only the reduced QoI wanted (the sample-pair path): factorisation and QoI stay in the registers of the
     // projection kernel's waves (fused_solve_mw); A_r never reaches memory
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
-        qoi_r != nullptr && d.n_obs + 1 <= 16 * 3 && getenv("FINROM_NO_FUSED_SOLVE") == nullptr) factor = 3;
+        qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
                           w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr))) return rc;
     if (factor >= 2) continue;
@@ -1602,7 +1512,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
     if (!q) { if ((rc = h->qtmp.reserve((size_t)Sc * d.n_obs * sizeof(double)))) return rc; q = (double*)h->qtmp.p; }
     // one-sample call patterns (MAP / HMC), 48 < r <= 96, the per-sample contraction: projection split over four waves, both
     // solves in registers, the gradient contraction dealt over the same waves -- one kernel, nothing but the outputs written
-    if (h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc) && getenv("FINROM_OLD_SUBST") == nullptr) {
+    if (h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
       // contraction over several workgroups per sample, MFMA-form factorisation + forward / adjoint solves (rom_onesample.hip),
       // then the gradient contraction dealt over 36 workgroups per sample
       RomGradArgs ga;
@@ -1625,7 +1535,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
       if ((rc = launch_rom_grad_contract_small(d, Sc, ga, st, ga.defer_sum ? h->back : nullptr))) return rc;
       continue;
     }
-    if (h->projection == FINROM_PROJECTION_DIRECT && rom_splitk_applies(d, Sc) && d.n_obs <= 64 && getenv("FINROM_OLD_SUBST") == nullptr) {
+    if (h->projection == FINROM_PROJECTION_DIRECT && rom_splitk_applies(d, Sc) && d.n_obs <= 64) {
       RomGradArgs ga;
       ga.data = data + (data_per_sample ? s0 * d.n_obs : 0); ga.data_stride = data_per_sample ? d.n_obs : 0;
       ga.theta = theta + s0 * d.P; ga.J = J + s0; ga.g = g + s0 * d.P;
@@ -1654,7 +1564,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
     ga.npairs = h->g_npairs; ga.pair_p = h->g_pair_p; ga.pair_i = h->g_pair_i; ga.Gt = h->g_Gt;
     // batches: the contraction with the blocks G_pi runs on the matrix cores for 16 samples at a time; a handful of samples
     // (the one-sample call pattern) keep it inside the substitution kernel (one launch less)
-    const bool batched = Sc >= 64 && d.n_obs <= 64 && getenv("FINROM_OLD_SUBST") == nullptr && getenv("FINROM_GRAD_INLINE") == nullptr;
+    const bool batched = Sc >= 64 && d.n_obs <= 64;
     if (batched) {
       if ((rc = h->vw.reserve((size_t)Sc * 2 * d.rp * sizeof(double)))) return rc;
       ga.vw = (double*)h->vw.p;
@@ -1745,7 +1655,7 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   int fom_cus = env_fom_cus;
   if (fom_cus < 0)
     fom_cus = (rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !env_no_band2 &&
-               w == nullptr && S >= 16384 && getenv("FINROM_PROJ_LDS") == nullptr) ? -3 : 0;
+               w == nullptr && S >= 16384) ? -3 : 0;
   hipStream_t fst = st;
   if (overlap && fom_cus != 0) {
     if ((rc = rom->ensure_fom_side(fom_cus))) return rc;
@@ -1927,8 +1837,7 @@ static int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop
   // (Tried and removed: under stream capture, the error model's forward kernel on a side stream beside the ROM's contraction
   // kernel -- the solve kernel is the first to need its output.  One fork / join inside a replayed graph cost ~240 us per call
   // on this runtime: 113 -> 355 us, tools/graph_call_cost.py.)
-  const bool one = rom->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(rom->d, S) && getenv("FINROM_OLD_SUBST") == nullptr &&
-                   rom->g_npairs > 0;
+  const bool one = rom->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(rom->d, S) && rom->g_npairs > 0;
   if (hs != nullptr && !(one && P <= 16)) {
     set_error("hmc_leapfrog: needs the one-sample form of the reduced model (<= 64 chains, direct projection, r <= 96, <= 16 averages, finrom_rom_set_gradient)");
     return FINROM_ERR_UNSUPPORTED;
@@ -2015,7 +1924,7 @@ int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, c
   // trajectory: finrom_hmc_begin has no averaging operator at hand); and this step leaves the next one's
   if (int rc = mlp->thp.reserve((size_t)a->C * HMC_THETA_PARTS * 16 * sizeof(double))) return rc;
   const bool carried = step > 0 && mlp->carry_k == a->Kq[step & 1] && mlp->carry_mom == a->P && mlp->carry_eps == a->eps &&
-                       mlp->carry_S == a->C && getenv("FINROM_HMC_NO_CARRY") == nullptr;
+                       mlp->carry_S == a->C;
   hs.theta_parts_in = carried ? (const double*)mlp->thp.p : nullptr;
   hs.tail.eps = a->eps; hs.tail.theta_parts = rom->d.P <= HMC_THETA_MAXP ? (double*)mlp->thp.p : nullptr;
   mlp->carry_k = nullptr;

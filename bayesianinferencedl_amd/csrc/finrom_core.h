@@ -122,7 +122,6 @@ constexpr int FOM_MAX_FUSED_X = 16;   // longest parameter vector the interprete
 constexpr int VM_CHUNK = 8;        // ops whose global operands are fetched together, one chunk ahead
 struct FomDev {
   long long* trace;   // FINROM_TRACE: per-workgroup {start, end (10 ns ticks), HW_ID, XCC_ID, start, end (shader clock)}; nullptr = off
-  int debug_phases;   // bit 0 factor+forward, 1 backward, 2 QoI (FINROM_FOM_PHASES, timing experiments only; default 7)
   int n, nnzL, xdim, n_obs, n_alist, cache_slots, fwd_chunk;
   int gsize;                         // values per sample: nnzL + 2n  (L | 1/L_ii | y,w)
   int nchunks_fwd, nchunks_bwd;      // executed chunks (the streams carry 2 more chunks of NOP padding)

@@ -87,26 +87,14 @@ int launch_field_prior(const double* U, int n, int pull, const double* x, const 
                        double* out, double* v_out, const FieldPriorTail* tail, int64_t S, double* part, int* tick, hipStream_t st);
 
 // ---- ROM ------------------------------------------------------------------------------
-constexpr int ROM_MAX_PHASES = 8;
 struct RomDev {
   int n, r, rp, NB, P, n_obs;           // rp = 16*NB padded basis size
   int solve_in_lds;                     // packed factor fits in LDS (rp <= 176)
   long long* trace;                     // FINROM_TRACE (see FomDev::trace)
-  int clock_probe;                      // FINROM_CLOCK_PROBE: a few workgroups print their shader clock (diagnostic)
-  // psi tables, rows grouped 4 per k-step and sorted by term count into phases of constant NT
-  int n_phases;
-  int phase_nt[ROM_MAX_PHASES], phase_ks0[ROM_MAX_PHASES], phase_ks1[ROM_MAX_PHASES], phase_slot0[ROM_MAX_PHASES];
-  // the same tables cut into LDS-sized chunks of whole k-steps (LDS-staged kernel, NB <= 5)
-  int n_chunks;
-  const int* ch_nt; const int* ch_nks; const int* ch_off; const int* ch_bytes;   // [n_chunks]; ch_off in doubles
-  const double* tvc;                    // chunk images: values then theta indices, each padded to 1 KiB
-  // the same rows regrouped for the single-wave kernels so that the four rows of a k-step share ONE list of theta indices
+  // psi tables, rows grouped 4 per k-step so that the four rows of a k-step share ONE list of theta indices
   // (rows with the same term pattern together; leftovers merged under the union of their patterns, absent terms = zero
   // rows): theta then comes from SGPRs, and the k-step needs no theta-index loads, no LDS reads and no per-lane addresses
-  int n_uphases;
-  int uphase_nt[ROM_MAX_PHASES], uphase_ks0[ROM_MAX_PHASES], uphase_ks1[ROM_MAX_PHASES], uphase_slot0[ROM_MAX_PHASES];
   const double* tvu;                    // [(nuslots + 4) * 4 * rp]
-  const int* kpat;                      // [nuslots + 16] theta index of each slot (0 = the constant 1)
   int tvu_bytes;
   int nku;                              // number of pattern-uniform k-steps (even; sorted by term count, descending; every
                                         // term-count group holds an even number of k-steps, padded with a zero k-step)
@@ -121,9 +109,8 @@ struct RomDev {
   int n_ext, ext_final;                 // per-sample scalars (<= 64); ext index of the factor behind the last k-step
   const int* ext_def;                   // [n_ext * 3] ext[l] = (theta'[a] / theta'[b]) ^ (1 + sq), theta'[0] = 1
   double* ext;                          // [S x n_ext] workspace of the CALL (set by rom_project; nullptr: the ungrouped loop)
-  const double* tv;                     // [(nslots + 4) * 4 * rp]  padded r-vectors, slot-major
-  const int* pidx;                      // [(nslots + 4) * 4]       theta index of each r-vector (0 = constant 1)
-  // rows with a non-zero load F (root nodes), same slot format with a runtime term count
+  // rows with a non-zero load F (root nodes): slot-major padded r-vectors (4 per slot) with the theta index of each
+  // (0 = the constant 1), a runtime term count
   int rhs_nk, rhs_nt;
   const double* rhs_tv; const int* rhs_pidx; const double* rhs_f;
   const double* obs_phi;                // [n_obs x r]
@@ -155,7 +142,7 @@ int launch_rom_grad(const RomDev& p, const double* Ar, const double* Br, int64_t
 int launch_rom_grad_contract(const RomDev& p, int64_t S, const RomGradArgs& ga, hipStream_t st);
 int launch_rom_chol_blocked(const RomDev& p, double* Ar, int64_t S, int* info, hipStream_t st);
 int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info, hipStream_t st,
-                    double* w_r = nullptr, double* qoi_r = nullptr, int* cu_ticket = nullptr);
+                    double* w_r = nullptr, double* qoi_r = nullptr);
 constexpr int ROM_SPLITK_MAX_S = 64;      // batches up to this size take the split-K projection kernel (r = 49..96)
 // (r mod 16 in 1..8, NB >= 7: the HalfCover form of the multi-wave kernels, rom_proj_half.hip)
 int launch_rom_proj_half(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
@@ -173,7 +160,7 @@ int launch_rom_grad_contract_small(const RomDev& p, int64_t S, const RomGradArgs
 int launch_rom_proj_splitk(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
                            hipStream_t st, double* w_r, double* qoi_r, const RomGradArgs& ga);
 int launch_rom_proj_single(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                           hipStream_t st, double* w_r, double* qoi_r, int* cu_ticket);   // cu_ticket: 4096 ints of device scratch or nullptr
+                           hipStream_t st, double* w_r, double* qoi_r);
 int launch_rom_solve(const RomDev& p, const double* Ar, const double* Br, int64_t S, double* w_r,
                      double* qoi_r, double* Ar_out, double* Br_out, int* info, int factored, hipStream_t st);
 

@@ -147,11 +147,6 @@ __global__ __launch_bounds__(64, 5) void fom_vm_kernel(FomDev p, const int* __re
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), gres, lane8, e * 512, 0);
   };
   const char* rcb = reinterpret_cast<const char*>(rowc) + lane8;
-  // FINROM_FOM_PHASES bits 4 / 5 (timing experiments only, results are garbage): FINOFF does not store to global memory /
-  // every op takes the multiply-add path
-  const int xmask = (p.debug_phases & 32) ? 0 : -1;
-  const int nogroup = (p.debug_phases & 128) ? 0xFFFF : 0;      // bit 7: no group-of-four path (A/B)
-  const bool nostore = p.debug_phases & 16;
 
 #define VM_LOAD1(buf, c)                                                      \
   _Pragma("unroll") for (int u = 0; u < FCH; ++u) buf[u] = ldgb(A[(c) * FCH + u]);
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(64, 5) void fom_vm_kernel(FomDev p, const int* __re
   // ---- forward: numeric factorisation A = L L^T fused with L y = F -------------------
   // Instruction count per op matters: beside the projection kernel every instruction of this wave waits for a
   // gap in the MFMA stream.  Plain multiply-add: bit test + branch, LDS address, ds_read, fma.
-  if (p.debug_phases & 1) {
+  {
     const int* __restrict__ A = fA; const int* __restrict__ KB = fKB; const int* __restrict__ D = fD;
     double bufA[FCH], bufB[FCH];
 #define VM_STEP(buf, nxt, c)   /* execute chunk c from buf while the operands of chunk c+1 fly into nxt */ \
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(64, 5) void fom_vm_kernel(FomDev p, const int* __re
   const int msk = fM[c];                                                      \
   _Pragma("unroll") for (int u = 0; u < FCH; ++u) nxt[u] = ldgb(an[u]);       \
   _Pragma("unroll") for (int h4 = 0; h4 < FCH; h4 += 4)                       \
-  if ((((msk & xmask) | nogroup) & (0xF << h4)) == 0) {                       \
+  if ((msk & (0xF << h4)) == 0) {                                            \
     /* four multiply-adds in a row (42 % of the groups): one test, the LDS operands requested together; when none of them */ \
     /* has its second operand in LDS (bits 16.. of the mask word; 32 % of the groups) that half of the work is skipped */ \
     if (((msk >> 16) & (0xF << h4)) == 0) {                                   \
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(64, 5) void fom_vm_kernel(FomDev p, const int* __re
   } else                                                                      \
   _Pragma("unroll") for (int u = h4; u < h4 + 4; ++u) {                       \
     const double ld = buf[u];                                                 \
-    if (__builtin_expect(!(msk & xmask & (1 << u)), 1)) {                     \
+    if (__builtin_expect(!(msk & (1 << u)), 1)) {                             \
       /* acc -= rc[b] * (G[a] + rc[d]): one of the two is exactly zero (FMA: d = the ZERO slot; FMALL: a out of range); */ \
       /* also "acc = A_e" (b = NEG1) and padding (b = ZERO) */                 \
       acc = fma(-*reinterpret_cast<const double*>(rcb + kbv[u]), ld + *reinterpret_cast<const double*>(rcb + dv[u]), acc); \
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(64, 5) void fom_vm_kernel(FomDev p, const int* __re
       /* tested in order of frequency; stores are buffer stores (descriptor + SGPR element offset, like the loads) */ \
       if (kind == F_FINOFF) {                                                 \
         const double l = acc * ld;                                            \
-        if (!nostore) stg(l, d);                                              \
+        stg(l, d);                                                            \
         if (b >= 0) rc[b * 64] = l;                                           \
         acc = 0.0;                                                            \
       } else if (kind == F_XFMA) {                                            \
@@ -272,7 +267,7 @@ __global__ __launch_bounds__(64) void fom_bwd_kernel(FomDev p, const int* __rest
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), gres, lane8, e * 512, 0);
   };
   double acc = 0.0;
-  if (p.debug_phases & 2) {
+  {
     // The operands of chunk c+1 are in flight while chunk c executes; the descriptors of a step -- kinds of chunk c, operand
     // offsets of chunk c+1 -- are requested a whole step before they are used.  (Two chunks ahead measured slower, 3.29 vs
     // 3.04 ms per 100k samples: this kernel moves 196 KB per sample at 6.4 TB/s, it is bandwidth-bound.)
@@ -305,7 +300,6 @@ __global__ __launch_bounds__(64) void fom_bwd_kernel(FomDev p, const int* __rest
   }
   const int64_t s = blk * 64 + lane;
   const double* wv = G + (int64_t)(p.nnzL + p.n) * 64;
-  if (p.debug_phases & 4)
   for (int o = 0; o < p.n_obs; ++o) {      // loads batched by 8
     double q0 = 0.0, q1 = 0.0;
     const int t0 = obs_ptr[o], t1 = obs_ptr[o + 1];

@@ -136,177 +136,11 @@ int launch_rom_chol_blocked(const RomDev& p, double* Ar, int64_t S, int* info, h
 // rom_proj_kernel<NB, NW> (rom_proj_device.h); the eight-wave instantiations (r > 144) live in rom_proj_wide.hip so that the two
 // halves compile side by side
 
-// ---------------------------------------------------------------------------------------
-// LDS-staged projection (bases up to r = 96, one wave per sample, 8 samples per workgroup).
-// The Psi tables are cut into chunks of whole k-steps (<= 24 KiB, constant term count); a chunk is
-// copied global -> LDS ONCE per workgroup with global_load_lds_dwordx4 (no VGPR round trip) while the
-// previous chunk is being consumed, so the 8 waves share one table fetch and the fetch has a whole
-// chunk of MFMA time (>10 us) to land -- which keeps this kernel MFMA-bound even while the FOM kernel
-// saturates the CU's vector-memory pipeline on the other stream.
-// LDS image of a chunk = its global bytes: [nks*NT*4 rows][rp] doubles, then nks*NT*4 theta indices.
-// With rp = 80 the 4 row-groups of a ds_read_b64 wave access fall on disjoint banks (640 B row pitch).
-// ---------------------------------------------------------------------------------------
-constexpr int ROM_CHUNK_BYTES = 24 * 1024;
-
-template <int NB>
-__device__ __forceinline__ void lds_chunk_compute(const double* __restrict__ buf, int nks, int nt, int rp, const double* thw,
-                                                  int q, int c, d4 (&acc)[NB * (NB + 1) / 2]) {
-  // ONE copy of the MFMA group (runtime term count): several unrolled copies make hipcc spill the
-  // inline-asm accumulators around every copy
-  const int* pidx = reinterpret_cast<const int*>(buf + (size_t)nks * nt * 4 * rp);
-  const int nrow = nks * nt;
-  double v[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) v[b] = 0.0;
-  int t = 0;
-#pragma unroll 1
-  for (int rowi = 0; rowi < nrow; ++rowi) {
-    const int row = rowi * 4 + q;
-    const double thp = thw[pidx[row]];
-    const double* src = buf + (size_t)row * rp + c;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) v[b] = fma(thp, src[16 * b], v[b]);
-    if (++t == nt) {               // the slab of this k-step is complete
-      mfma_tiles<NB, 1, 0>(v, acc);
-      t = 0;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) v[b] = 0.0;
-    }
-  }
-}
-
-template <int NB, int WPB>      // WPB waves (= samples) per workgroup share each staged chunk
-__global__ __launch_bounds__(64 * WPB, WPB == 4 ? 3 : 1) void rom_proj_lds_kernel(RomDev p, const int* __restrict__ ch_nt,
-                                                              const int* __restrict__ ch_nks,
-                                                              const int* __restrict__ ch_off,
-                                                              const int* __restrict__ ch_bytes,
-                                                              const double* __restrict__ tvc,
-                                                              const double* __restrict__ theta, int64_t S,
-                                                              double* __restrict__ Ar, double* __restrict__ Br, int factor,
-                                                              int* __restrict__ info) {
-  constexpr int NT = NB * (NB + 1) / 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];     // [2][ROM_CHUNK_BYTES] + th[8][32]
-  double* th = reinterpret_cast<double*>(smem + 2 * ROM_CHUNK_BYTES);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * WPB + wave;
-  const bool live = s < S;
-  trace_begin(p.trace, blockIdx.x);
-  const long long probe_t0 = __builtin_amdgcn_s_memtime(), probe_r0 = __builtin_amdgcn_s_memrealtime();
-  __builtin_amdgcn_s_setprio(3);
-  double* thw = th + wave * 32;
-  if (lane == 0) thw[0] = 1.0;
-  if (live && lane < p.P) thw[lane + 1] = theta[s * p.P + lane];
-  const int q = lane >> 4, c = lane & 15;
-  d4 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
-
-  auto stage = [&](int g, int slot) {     // async copy of chunk g into LDS buffer `slot`, 1 KiB per wave-instruction
-    const char* src = reinterpret_cast<const char*>(tvc) + (size_t)ch_off[g] * 8;
-    char* dst = smem + slot * ROM_CHUNK_BYTES;
-    const int nb = ch_bytes[g];
-    for (int off = wave * 1024; off < nb; off += WPB * 1024)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(dst + off), 16, 0, 0);
-  };
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int g = 0; g < p.n_chunks; ++g) {
-    if (g + 1 < p.n_chunks) stage(g + 1, (g + 1) & 1);
-    const double* buf = reinterpret_cast<const double*>(smem + (g & 1) * ROM_CHUNK_BYTES);
-    const int nks = ch_nks[g];
-    lds_chunk_compute<NB>(buf, nks, ch_nt[g], p.rp, thw, q, c, acc);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // chunk g+1 has landed (this wave's share)
-    __syncthreads();                                    // ... and everybody is done reading chunk g
-  }
-  if (!live) return;
-  if (p.clock_probe && threadIdx.x == 0 && (blockIdx.x % 2500) == 7) {
-    const long long dt = __builtin_amdgcn_s_memtime() - probe_t0, dr = __builtin_amdgcn_s_memrealtime() - probe_r0;
-    printf("[proj probe] block %d: %lld shader ticks, %lld x10ns -> clock %.0f MHz, main loop %.1f us\n", (int)blockIdx.x, dt, dr,
-           (double)dt / (double)dr * 100.0, dr * 0.01);
-  }
-
-  mfma_drain(acc);
-  if (factor) {
-    const int bad = chol_tiles<NB>(acc, q, c, p.r);
-    if (bad && info != nullptr && lane == 0) atomicOr(&info[s], 2);
-  }
-  const int R = p.rp;
-  double* A = Ar + s * (int64_t)(R * (R + 1) / 2);
-  int idx = 0;
-#pragma unroll
-  for (int ti = 0; ti < NB; ++ti)
-#pragma unroll
-    for (int tj = ti; tj < NB; ++tj) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int row = 16 * ti + q + 4 * g, col = 16 * tj + c;
-        if (ti != tj || col >= row) A[row * R - (row * (row - 1)) / 2 + col - row] = acc[idx][g];
-      }
-      ++idx;
-    }
-  // B_r = psi^T F over the root rows (rebuilt from the global table: a handful of k-steps, VALU only)
-  double bacc[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) bacc[b] = 0.0;
-  for (int ks = 0; ks < p.rhs_nk; ++ks) {
-    double v[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) v[b] = 0.0;
-    for (int t = 0; t < p.rhs_nt; ++t) {
-      const int row = (ks * p.rhs_nt + t) * 4 + q;
-      const double thp = thw[p.rhs_pidx[row]];
-      const double* src = p.rhs_tv + (int64_t)row * p.rp + c;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) v[b] = fma(thp, src[16 * b], v[b]);
-    }
-    const double fk = p.rhs_f[ks * 4 + q];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) bacc[b] = fma(v[b], fk, bacc[b]);
-  }
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    double x = bacc[b];
-    x += __shfl_xor(x, 16);
-    x += __shfl_xor(x, 32);
-    if (q == 0) Br[s * p.rp + 16 * b + c] = x;
-  }
-  trace_end(p.trace, blockIdx.x);
-}
-
-template <int NB>
-static int launch_proj_lds(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                           hipStream_t st) {
-  const size_t lds = 2 * ROM_CHUNK_BYTES + 8 * 32 * sizeof(double);
-  static const int wpb = getenv("FINROM_PROJ_LDS") ? atoi(getenv("FINROM_PROJ_LDS")) : 4;
-  if (wpb == 8)
-    hipLaunchKernelGGL((rom_proj_lds_kernel<NB, 8>), dim3((unsigned)((S + 7) / 8)), dim3(512), lds, st, p, p.ch_nt, p.ch_nks,
-                       p.ch_off, p.ch_bytes, p.tvc, theta, S, Ar, Br, factor, info);
-  else
-    hipLaunchKernelGGL((rom_proj_lds_kernel<NB, 4>), dim3((unsigned)((S + 3) / 4)), dim3(256), lds, st, p, p.ch_nt, p.ch_nks,
-                       p.ch_off, p.ch_bytes, p.tvc, theta, S, Ar, Br, factor, info);
-  FR_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                    hipStream_t st, double* w_r, double* qoi_r, int* cu_ticket) {
+                    hipStream_t st, double* w_r, double* qoi_r) {
   // factor: 0 = write A_r, 1 = write its Cholesky factor (NB <= 6), 2 = also solve and write only w_r / qoi_r (NB <= 5)
   if (S == 0) return 0;
   ScopedKernelTimer t(K_ROM_PROJ, st);
-  // The LDS-staged variant shares each table fetch among the 4 waves of a workgroup; measured on MI355X it
-  // is 8 % slower stand-alone (barriers) and no faster beside the FOM kernel, so it is opt-in.
-  if (p.n_chunks > 0 && getenv("FINROM_PROJ_LDS") != nullptr) {
-    switch (p.NB) {
-      case 1: return launch_proj_lds<1>(p, theta, S, Ar, Br, factor, info, st);
-      case 2: return launch_proj_lds<2>(p, theta, S, Ar, Br, factor, info, st);
-      case 3: return launch_proj_lds<3>(p, theta, S, Ar, Br, factor, info, st);
-      case 4: return launch_proj_lds<4>(p, theta, S, Ar, Br, factor, info, st);
-      case 5: return launch_proj_lds<5>(p, theta, S, Ar, Br, factor, info, st);
-      default: break;
-    }
-  }
   // one-sample call patterns (MAP / HMC): a lone wave per sample is pure MFMA latency; split its k-steps over four waves
   if (rom_splitk_applies(p, S)) return launch_rom_proj_splitk(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r, RomGradArgs());
   dim3 block(256);
@@ -319,7 +153,7 @@ int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar,
   if (p.NB >= 7 && p.r <= 16 * p.NB - 8 && !no_half) return launch_rom_proj_half(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r);
   switch (p.NB) {
     case 1: case 2: case 3: case 4: case 5:      // own translation unit (-O2)
-      return launch_rom_proj_single(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r, cu_ticket);
+      return launch_rom_proj_single(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r);
     FR_CASE(6, 1)      // (r = 81..96 through the four-wave kernel with the fused solve: 28.6 vs 27.2 ms per 100k -- 21 tiles do not split evenly)
     FR_CASE(7, 4) FR_CASE(8, 4) FR_CASE(9, 4)
     case 10: case 11: case 12: case 13: return launch_rom_proj_wide(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r);
@@ -882,8 +716,7 @@ int launch_rom_grad(const RomDev& p, const double* Ar, const double* Br, int64_t
   if (S == 0) return 0;
   ScopedKernelTimer t(K_ROM_SOLVE, st);
   const int nset = (p.rp + 63) / 64;
-  static const bool old_subst = getenv("FINROM_OLD_SUBST") != nullptr;
-  if (!old_subst && p.n_obs <= 64) {      // blocked substitutions with the factor in global memory, both solves + the gradient
+  if (p.n_obs <= 64) {      // blocked substitutions with the factor in global memory, both solves + the gradient
     const dim3 grid((unsigned)S), block(64);
     switch (nset) {
       case 1: hipLaunchKernelGGL((rom_subst_blocked_kernel<1, true>), grid, block, 0, st, p, Ar, Br, S, w_r, qoi_r, ga); break;
@@ -909,8 +742,7 @@ int launch_rom_solve(const RomDev& p, const double* Ar, const double* Br, int64_
   const size_t lds = ((in_lds ? (size_t)p.rp * (p.rp + 1) / 2 : 0) + 2 * (size_t)p.rp) * sizeof(double);
   const int nset = (p.rp + 63) / 64;
 #define FR_SOLVE(L, N, F) return launch_solve_t<L, N, F>(p, lds, Ar, Br, S, w_r, qoi_r, Ar_out, Br_out, info, st)
-  static const bool old_subst = getenv("FINROM_OLD_SUBST") != nullptr;
-  if (factored && p.NB >= 6 && Ar_out == nullptr && Br_out == nullptr && !old_subst) {     // r > 80: blocked substitutions
+  if (factored && p.NB >= 6 && Ar_out == nullptr && Br_out == nullptr) {     // r > 80: blocked substitutions
     switch (nset) {
       case 2: hipLaunchKernelGGL((rom_subst_blocked_kernel<2, false>), dim3((unsigned)S), dim3(64), 0, st, p, Ar, Br, S, w_r, qoi_r, RomGradArgs()); break;
       case 3: hipLaunchKernelGGL((rom_subst_blocked_kernel<3, false>), dim3((unsigned)S), dim3(64), 0, st, p, Ar, Br, S, w_r, qoi_r, RomGradArgs()); break;

@@ -580,8 +580,6 @@ int launch_small(const RomDev& p, const double* theta, int64_t S, int NC, double
 // workgroups per sample of the contraction: as many as keep a part at >= 8 k-steps per wave, at most 8 (NC x 4 SIMDs of NC CUs).
 // NOT a function of the batch size: a sample's sums are split the same way alone and inside a batch of 64 (bit-identical results)
 int rom_onesample_parts(const RomDev& p, int64_t /*S*/) {
-  static const int forced = getenv("FINROM_ONESAMPLE_NC") != nullptr ? atoi(getenv("FINROM_ONESAMPLE_NC")) : 0;
-  if (forced > 0) return forced > 16 ? 16 : forced;
   int nc = p.nku / 32;
   if (nc > 8) nc = 8;
   return nc < 1 ? 1 : nc;
@@ -590,8 +588,7 @@ size_t rom_onesample_scratch_bytes(const RomDev& p, int64_t S) {
   return (size_t)S * rom_onesample_parts(p, S) * (p.NB * (p.NB + 1) / 2) * 256 * sizeof(double);
 }
 bool rom_onesample_applies(const RomDev& p, int64_t S) {
-  static const bool off = getenv("FINROM_NO_ONESAMPLE") != nullptr;
-  return !off && S <= ROM_SPLITK_MAX_S && p.NB >= 1 && p.NB <= 6 && p.nku >= 64 && p.n_obs <= 15;
+  return S <= ROM_SPLITK_MAX_S && p.NB >= 1 && p.NB <= 6 && p.nku >= 64 && p.n_obs <= 15;
 }
 
 // grad = 0: w_r (optional) and qoi_r; grad = 1 (ga.data, ga.vw, ga.J set): also v_r; v_r | w_r go to ga.vw for the contraction kernel

@@ -14,32 +14,9 @@ __device__ __forceinline__ void sfor(F&& f) {
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); sfor<I + 1, N>(f); }
 }
 
-// One k-step = 4 rows of psi.  Rows are sorted by their number of terms, so the k-steps form a
-// few PHASES with a constant term count nt (<= 4): slot t of k-step ks is 4 padded r-vectors at
-//   tv[((slot0 + (ks - ks0) * nt + t) * 4 + q) * rp + col],   theta index pidx[(slot) * 4 + q],
-// i.e. every address is a function of the loop counter (no dependent index loads), and the raw
-// table values of k-step ks+1 are fetched into registers while the MFMAs of k-step ks issue.
-// (These phase tables serve psi^T F on the root rows and the FINROM_CLOCK_PROBE=3 A/B loop; the main loops run on the
-// pattern-uniform tables RomDev::tvu / kmeta, see proj_main_uniform / proj_main_uniform_mw below.)
+// One k-step = 4 rows of psi with at most ROM_MAX_NT terms each; the main loops run on the pattern-uniform tables
+// RomDev::tvu / kmeta, see proj_main_uniform / proj_main_uniform_mw below.
 constexpr int ROM_MAX_NT = 4;
-
-template <int NB>
-__device__ __forceinline__ void load_kstep(const double* __restrict__ tv, const int* __restrict__ pidx, int slot, int nt,
-                                           int rp, int q, int c, double (&raw)[ROM_MAX_NT][NB], int (&pi)[ROM_MAX_NT]) {
-  // theta indices of ALL four possible terms first (slots beyond nt belong to the following k-steps or to the padding: valid
-  // indices, their theta is read and not used): the LDS reads of theta can then be issued together, ahead of the table values
-#pragma unroll
-  for (int t = 0; t < ROM_MAX_NT; ++t) pi[t] = pidx[(slot + t) * 4 + q];
-#pragma unroll
-  for (int t = 0; t < ROM_MAX_NT; ++t) {
-    if (t < nt) {                                  // wave-uniform
-      const int row = (slot + t) * 4 + q;
-      const double* src = tv + (int64_t)row * rp + c;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) raw[t][b] = src[16 * b];
-    }
-  }
-}
 
 // The accumulators MUST live in architectural VGPRs: measured on gfx950 (tools/mfma_f64_variants.hip),
 // v_mfma_f64_16x16x4_f64 issues every 64 cycles (77 TFLOP/s chip-wide) with VGPR accumulators but only
@@ -257,9 +234,7 @@ __device__ __forceinline__ void proj_main_uniform(const RomDev& p, const int* __
   const c_f64_p theta_s = (c_f64_p)(unsigned long long)theta_g;
   const __amdgpu_buffer_rsrc_t tres = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p.tvu), 0, p.tvu_bytes, 0x00020000);
   const int voff = (q * p.rp + c) * 8;
-  // bytes per slot (4 rows).  FINROM_CLOCK_PROBE=2 (timing experiment, results are garbage): every table fetch reads slot 0 --
-  // same instructions, no L2 / fabric traffic: what the kernel loses beside the FOM sweep with and without its table stream
-  const int rowb = p.clock_probe == 2 ? 0 : 4 * p.rp * 8;
+  const int rowb = 4 * p.rp * 8;      // bytes per slot (4 rows)
   auto ldt = [&](int slot, auto bc) -> double {
     constexpr int b = decltype(bc)::value;
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(tres, voff + 128 * b, slot * rowb, 0));
@@ -917,9 +892,7 @@ __device__ __forceinline__ void fused_solve_mw(const RomDev& p, d4 (&acc)[(NB * 
 // needs no backward substitution.  ~2.4 k vector instructions + 180 MFMAs per sample at r = 80.
 // ---------------------------------------------------------------------------------------
 constexpr int ROM_SW_LDS = 16 * 5;      // doubles of LDS per wave (B_r)
-#ifndef FINROM_SW_MFMA_DIAG_TILES
-#define FINROM_SW_MFMA_DIAG_TILES 6     // block rows with at most this many live tiles factor their diagonal tile on the matrix cores
-#endif
+constexpr int ROM_SW_MFMA_DIAG_TILES = 6;      // block rows with at most this many live tiles factor their diagonal tile on the matrix cores
 template <int NB>
 __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (NB + 1) / 2], const double (&bacc)[NB], int q, int c,
                                               double* __restrict__ mt, double& qout) {
@@ -973,11 +946,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
     // (the first block rows of a wide basis keep the shuffle steps: with 15 or 10 tiles live, diag_tile_inverse's working set does
     //  not fit beside them under the kernel's 200-register cap -- hipcc spills, and spill code beside inline-asm MFMAs is not
     //  hazard-safe; with <= 6 live tiles it does)
-#ifndef FINROM_SW_SHUFFLE_DIAG
-    constexpr bool kMfmaDiag = (NB - kb) * (NB - kb + 1) / 2 <= FINROM_SW_MFMA_DIAG_TILES;
-#else
-    constexpr bool kMfmaDiag = false;
-#endif
+    constexpr bool kMfmaDiag = (NB - kb) * (NB - kb + 1) / 2 <= ROM_SW_MFMA_DIAG_TILES;
     if constexpr (kMfmaDiag) {
       // Round 4: the diagonal tile 4 x 4-blocked on the matrix cores (diag_tile_inverse, as the other two epilogues since round 3)
       // instead of the 16 shuffle steps below.  It returns M in the C/D layout; the A operand of M T is M^T in that layout --
@@ -1094,60 +1063,19 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
 #pragma unroll
   for (int t = 0; t < NTL; ++t) acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
 
-  const int rp_ld = p.clock_probe == 2 ? 0 : p.rp;      // FINROM_CLOCK_PROBE=2 (timing experiment, results are garbage): every
-                                                       // table fetch hits the same four rows -> no L2 traffic, same instructions
   if constexpr (NW > 1) {
     // (round 1's loop -- per-lane theta indices, two slab buffers, __syncthreads() per k-step -- reached 0.50 of the MFMA peak
     // at r = 120 where this one reaches 0.7; it is gone: its run-time indexing of the phase tables inside RomDev made hipcc keep a
     // copy of the kernel arguments in scratch memory once the fused epilogue was added)
     proj_main_uniform_mw<NB, NW, W, HF>(p, kpat, theta_s, q, c, lane, slab, acc);
-  } else if ((p.clock_probe & 15) != 3) {      // (bits 4 / 5: timing experiments without table loads / without scalar loads)
+  } else {
     if constexpr (NW == 1 && GR) {
       if (ext_s != nullptr) proj_main_grouped<NB>(p, kpat, ext_s, q, c, acc);
       else proj_main_uniform<NB>(p, p.ext != nullptr ? p.kmeta : kpat, theta_s, q, c, acc, p.nku);      // (kpat is RomDev::kmg when the launch is a grouped one)
     } else if constexpr (NW == 1) {
       const int per = ((p.nku + kparts - 1) / kparts + 1) / 2 * 2, k0 = kpart * per;
       const int cnt = kparts == 1 ? p.nku : (k0 >= p.nku ? 0 : (p.nku - k0 < per ? p.nku - k0 : per));
-      if (cnt > 0) proj_main_uniform<NB>(p, kpat + 8 * k0, theta_s, q, c, acc, cnt);      // kpat = RomDev::kmeta as a kernel parameter  // (FINROM_CLOCK_PROBE=3: the per-lane-theta loop below, for A/B timing)
-    }
-  } else
-  // ONE copy of the MFMA group for all phases (runtime term count): several unrolled copies make hipcc
-  // spill the inline-asm accumulators around every copy
-  {
-    double raw[ROM_MAX_NT][NB];
-    int pi[ROM_MAX_NT];
-    int ph = 0;
-    while (ph < p.n_phases && p.phase_ks0[ph] >= p.phase_ks1[ph]) ++ph;
-    if (ph < p.n_phases) load_kstep<NB>(p.tv, p.pidx, p.phase_slot0[ph], p.phase_nt[ph], rp_ld, q, c, raw, pi);
-#pragma unroll 1
-    for (; ph < p.n_phases; ++ph) {
-      const int ks0 = p.phase_ks0[ph], ks1 = p.phase_ks1[ph], slot0 = p.phase_slot0[ph], nt = p.phase_nt[ph];
-      // what follows the last k-step of this phase: the first k-step of the next non-empty phase (or padding)
-      int nph = ph + 1;
-      while (nph < p.n_phases && p.phase_ks0[nph] >= p.phase_ks1[nph]) ++nph;
-      const int next_slot = nph < p.n_phases ? p.phase_slot0[nph] : slot0 + (ks1 - ks0) * nt;
-      const int next_nt = nph < p.n_phases ? p.phase_nt[nph] : 1;
-#pragma unroll 1
-      for (int ks = ks0; ks < ks1; ++ks) {
-        double v[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) v[b] = 0.0;
-        double thp[ROM_MAX_NT];
-#pragma unroll
-        for (int t = 0; t < ROM_MAX_NT; ++t) thp[t] = thw[pi[t]];      // four LDS reads in flight together
-#pragma unroll
-        for (int t = 0; t < ROM_MAX_NT; ++t) {
-          if (t < nt) {
-#pragma unroll
-            for (int b = 0; b < NB; ++b) v[b] = fma(thp[t], raw[t][b], v[b]);
-          }
-        }
-        // raw is dead now: fetch the next k-step into it; the loads fly while this k-step's MFMAs issue
-        // (the table is padded by one k-step of zeros, so the last prefetch stays inside it)
-        const bool last = ks + 1 == ks1;
-        load_kstep<NB>(p.tv, p.pidx, last ? next_slot : slot0 + (ks + 1 - ks0) * nt, last ? next_nt : nt, rp_ld, q, c, raw, pi);
-        mfma_tiles<NB, NW, W>(v, acc);
-      }
+      if (cnt > 0) proj_main_uniform<NB>(p, kpat + 8 * k0, theta_s, q, c, acc, cnt);      // kpat = RomDev::kmeta as a kernel parameter
     }
   }
 

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(100))) void 
                                                                  double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                                                  int* __restrict__ info, double* __restrict__ w_r,
                                                                  double* __restrict__ qoi_r, const int* __restrict__ kpat) {
-  // (kpat = p.kpat as a __restrict__ kernel parameter of its own: only then are its reads scalar loads)
+  // (kpat = p.kmeta as a __restrict__ kernel parameter of its own: only then are its reads scalar loads)
   // (with p.ext: the grouped main loop -- kpat is then p.kmg)
   rom_proj_entry<NB, 1, true>(p, theta, S, Ar, Br, factor, info, w_r, qoi_r, kpat);
 }
@@ -54,8 +54,7 @@ static int launch_splitk(const RomDev& p, const double* theta, int64_t S, double
 }
 
 bool rom_splitk_applies(const RomDev& p, int64_t S) {
-  static const bool no_splitk = getenv("FINROM_NO_SPLITK") != nullptr;
-  return S <= ROM_SPLITK_MAX_S && p.NB >= 4 && p.NB <= 6 && p.nku >= 64 && !no_splitk;
+  return S <= ROM_SPLITK_MAX_S && p.NB >= 4 && p.NB <= 6 && p.nku >= 64;
 }
 
 // factor 0 / 1 / 2 as in launch_rom_proj; 4 (with ga): the whole adjoint gradient (finrom_rom_grad) in this one kernel
@@ -71,15 +70,13 @@ int launch_rom_proj_splitk(const RomDev& p, const double* theta, int64_t S, doub
 }
 
 int launch_rom_proj_single(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                           hipStream_t st, double* w_r, double* qoi_r, int* /*cu_ticket: unused (stagger experiment)*/) {
+                           hipStream_t st, double* w_r, double* qoi_r) {
   const dim3 grid((unsigned)((S + 3) / 4)), block(256);
-  static const size_t pad_lds = getenv("FINROM_PROJ_PAD_LDS") != nullptr ? (size_t)atoi(getenv("FINROM_PROJ_PAD_LDS")) : 0;      // occupancy experiments
   if (p.ext != nullptr)
     hipLaunchKernelGGL(rom_ext_kernel, dim3((unsigned)((S * p.n_ext + 255) / 256)), dim3(256), 0, st, theta, p.P, S, p.ext_def, p.n_ext, p.ext);
   const int* kp = p.ext != nullptr ? p.kmg : p.kmeta;
   switch (p.NB) {
-#define FR_ONE(N) case N: if (pad_lds > 65536) (void)hipFuncSetAttribute((const void*)rom_proj_single_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds); \
-                       hipLaunchKernelGGL(rom_proj_single_kernel<N>, grid, block, pad_lds, st, p, theta, S, Ar, Br, factor, info, w_r, qoi_r, kp); break;
+#define FR_ONE(N) case N: hipLaunchKernelGGL(rom_proj_single_kernel<N>, grid, block, 0, st, p, theta, S, Ar, Br, factor, info, w_r, qoi_r, kp); break;
     FR_ONE(1) FR_ONE(2) FR_ONE(3) FR_ONE(4) FR_ONE(5)
 #undef FR_ONE
     default: set_error("rom_proj_single: basis size > 80"); return FINROM_ERR_UNSUPPORTED;

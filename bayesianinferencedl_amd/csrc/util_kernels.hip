@@ -190,7 +190,7 @@ constexpr int64_t SAMPLER_GEMM_MIN_S = 4096;      // below: the 64 x 64 kernel f
 
 template <int WM, int NT>      // NT = this wave's live column tiles (4; fewer only in the last column tile of a factor whose n is not a multiple of 128)
 __device__ __forceinline__ void sampler_tile(const double* __restrict__ U, int n, const double* __restrict__ xi, int64_t S,
-                                             double* __restrict__ kout, int64_t s0, int j0, int nch, double* lds, int xflags) {
+                                             double* __restrict__ kout, int64_t s0, int j0, int nch, double* lds) {
   typedef SGeo<WM> G;
   constexpr int SG_A_BUF = G::A_BUF, SG_B_BUF = G::B_BUF;
   double* Abuf = lds;
@@ -300,12 +300,12 @@ __device__ __forceinline__ void sampler_tile(const double* __restrict__ U, int n
 #pragma unroll
           for (int t = 0; t < NT; ++t) SG_MFMA(acc[i][t], av[ks & 1][i], bv[ks & 1][t]);
       }
-      if (ks == 1 && ch + 1 < nch && !(xflags & 2)) {    // chunk ch + 1 (requested an iteration ago) goes to the other buffer ...
+      if (ks == 1 && ch + 1 < nch) {    // chunk ch + 1 (requested an iteration ago) goes to the other buffer ...
         lwrite(cur ^ 1, ch + 1, std::integral_constant<int, cur ^ 1>{});
         if (ch + 3 < nch) gload(ch + 3, std::integral_constant<int, cur ^ 1>{});      // ... and its register set takes chunk ch + 3
       }
     }
-    if (!(xflags & 1)) exchange();                       // (xflags: timing experiments, results are garbage -- FINROM_SAMPLER_XFLAGS)
+    exchange();
   };
   int ch = 0;
   for (; ch + 1 < nch; ch += 2) {
@@ -337,7 +337,7 @@ __device__ __forceinline__ void sampler_tile(const double* __restrict__ U, int n
 template <int WM>
 __global__ __launch_bounds__(128 * WM) void sampler_gemm_kernel(const double* __restrict__ U, int n, const double* __restrict__ xi,
                                                               int64_t S, double* __restrict__ kout, int n_sgroups, int n_cgroups,
-                                                              int top_tile, int pad_k, int pad_min_k, int xflags) {
+                                                              int top_tile, int pad_k, int pad_min_k) {
   extern __shared__ __attribute__((aligned(16))) double sg_lds[];
   typedef SGeo<WM> G;
   constexpr int WGS = 8 * G::SM_PER_SUPER;               // workgroups of a super-tile = what one XCD runs together (32 CUs)
@@ -359,11 +359,11 @@ __global__ __launch_bounds__(128 * WM) void sampler_gemm_kernel(const double* __
   const int kend = min(n, ((cg < pad_k && (top + 1) * 128 >= pad_min_k ? top : jt) + 1) * 128);
   const int nch = (kend + 15) / 16;
   const int live = (n - j0 - 64 * ((int)(threadIdx.x >> 6) & 1) + 15) / 16;     // this wave's column tiles that hold columns < n
-  if (live >= 4) sampler_tile<WM, 4>(U, n, xi, S, kout, s0, j0, nch, sg_lds, xflags);
-  else if (live == 3) sampler_tile<WM, 3>(U, n, xi, S, kout, s0, j0, nch, sg_lds, xflags);
-  else if (live == 2) sampler_tile<WM, 2>(U, n, xi, S, kout, s0, j0, nch, sg_lds, xflags);
-  else if (live == 1) sampler_tile<WM, 1>(U, n, xi, S, kout, s0, j0, nch, sg_lds, xflags);
-  else sampler_tile<WM, 0>(U, n, xi, S, kout, s0, j0, nch, sg_lds, xflags);               // (stages and meets the barriers, no MFMAs)
+  if (live >= 4) sampler_tile<WM, 4>(U, n, xi, S, kout, s0, j0, nch, sg_lds);
+  else if (live == 3) sampler_tile<WM, 3>(U, n, xi, S, kout, s0, j0, nch, sg_lds);
+  else if (live == 2) sampler_tile<WM, 2>(U, n, xi, S, kout, s0, j0, nch, sg_lds);
+  else if (live == 1) sampler_tile<WM, 1>(U, n, xi, S, kout, s0, j0, nch, sg_lds);
+  else sampler_tile<WM, 0>(U, n, xi, S, kout, s0, j0, nch, sg_lds);               // (stages and meets the barriers, no MFMAs)
 }
 
 template <int WM>
@@ -378,9 +378,7 @@ static int launch_sampler_gemm(const double* U, int n, const double* xi, int64_t
   if (n_sgroups > (1 << 20)) { set_error("sampler: batch too large for one launch"); return FINROM_ERR_UNSUPPORTED; }
   const unsigned grid = (unsigned)((n_super + 7) / 8 * 8 * 8 * G::SM_PER_SUPER);
   hipLaunchKernelGGL(sampler_gemm_kernel<WM>, dim3(grid), dim3(G::THREADS), G::LDS_BYTES, st, U, n, xi, S, k, (int)n_sgroups, n_cgroups,
-                     ntn - 1, pad ? (getenv("FINROM_SAMPLER_PAD_GROUPS") ? atoi(getenv("FINROM_SAMPLER_PAD_GROUPS")) : 1 << 20) : 0,
-                     getenv("FINROM_SAMPLER_PAD_GROUPS") ? 0 : 2048,      // (A/B: the first N column groups in lockstep whatever their K)
-                     getenv("FINROM_SAMPLER_XFLAGS") ? atoi(getenv("FINROM_SAMPLER_XFLAGS")) : 0);
+                     ntn - 1, pad ? 1 << 20 : 0, 2048);
   FR_HIP(hipGetLastError());
   return 0;
 }

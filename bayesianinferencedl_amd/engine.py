@@ -261,7 +261,7 @@ class FomEngine:
         self.band = bp
         self._B_band = sp.csr_matrix(np.asarray(B_obs)[:, bp.perm]) if not sp.issparse(B_obs) else sp.csr_matrix(B_obs)[:, bp.perm]
         self.band_slots = nslots            # physical value slots per sample (bench: algorithmic bytes)
-        self.band_qoi_only = bool(d.qoi_FgQ) and _os.environ.get("FINROM_BAND_NO_QOI_ONLY") is None      # calls without w: QoI-only form
+        self.band_qoi_only = bool(d.qoi_FgQ)      # calls without w: QoI-only form
 
     def solve(self, X, want_w=False):
         b = _Batch(X, self.xdim)

@@ -282,7 +282,7 @@ int finrom_fom_solve_rhs(finrom_fom_t h, const double* x, int64_t S, const doubl
 #define FINROM_FOM_PATH_INTERPRETER 3      /* fom_vm_kernel + fom_bwd_kernel (schedule interpreter) */
 #define FINROM_FOM_PATH_BAND_REGISTERS 4   /* fom_band_kernel: frontal band sweep, front in registers (m <= 12) */
 #define FINROM_FOM_PATH_BAND_LDS_4WAVE 5   /* fom_band_ldsw_kernel: post's window over four waves + LDS exchange (m = 16 ... 28) */
-#define FINROM_FOM_PATH_BAND_LDS_1WAVE 6   /* fom_band_lds_kernel: one-wave LDS window (A/B builds only) */
+#define FINROM_FOM_PATH_BAND_LDS_1WAVE 6   /* retired, never returned */
 #define FINROM_FOM_PATH_BAND_REGISTERS_QOI 7   /* fom_band_kernel, QoI-only form: fins ride as functionals, no w */
 #define FINROM_FOM_PATH_BAND_LDS_4WAVE_QOI 8   /* fom_band_ldsw_kernel, QoI-only form */
 int finrom_fom_last_path(finrom_fom_t h);

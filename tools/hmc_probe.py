@@ -1,5 +1,5 @@
-"""One-sample grad_romml latency (BASELINE configs[4] call pattern) and, with FINROM_CLOCK_PROBE=7, the split-K kernel's phase clocks.
-usage (GPU box): [FINROM_CLOCK_PROBE=7] python tools/hmc_probe.py [r] [n_calls]"""
+"""One-sample grad_romml latency (BASELINE configs[4] call pattern).
+usage (GPU box): python tools/hmc_probe.py [r] [n_calls]"""
 import sys
 import time
 
