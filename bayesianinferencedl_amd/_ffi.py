@@ -79,6 +79,20 @@ class HmcState(C.Structure):
                 ("accept", C.c_void_p), ("trace", C.c_void_p), ("loss", C.c_void_p), ("info", C.c_void_p)]
 
 
+class LbfgsState(C.Structure):
+    _fields_ = [("S", C.c_int64), ("d", C.c_int32), ("m", C.c_int32), ("ftol", C.c_double), ("gtol", C.c_double),
+                ("maxiter", C.c_int64), ("maxfun", C.c_int64), ("maxls", C.c_int32), ("lo", C.c_void_p), ("hi", C.c_void_p),
+                ("x", C.c_void_p), ("f", C.c_void_p), ("g", C.c_void_p), ("xt", C.c_void_p), ("work", C.c_void_p),
+                ("status", C.c_void_p), ("nit", C.c_void_p), ("nfev", C.c_void_p), ("fhist", C.c_void_p), ("fhist_rows", C.c_int64),
+                ("G", C.c_void_p), ("gdim", C.c_int32), ("gamma", C.c_double), ("k1_ptr", C.c_void_p), ("k1_idx", C.c_void_p),
+                ("k1_val", C.c_void_p)]
+
+
+def lbfgs_work_doubles(S, d, m):
+    """FINROM_LBFGS_WORK_DOUBLES (include/finrom.h)."""
+    return int(S) * ((2 * int(m) + 1) * int(d) + 2 * int(m) + 8)
+
+
 class RomDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("r", C.c_int32), ("P", C.c_int32), ("n_obs", C.c_int32),
                 ("nterms", C.c_int32),
@@ -145,6 +159,9 @@ SIGNATURES = {
     "finrom_hmc_end": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p]),
     "finrom_hmc_leapfrog_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_lbfgs_begin": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
+    "finrom_lbfgs_propose": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
+    "finrom_lbfgs_accept": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_solve_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8),
     "finrom_sub": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_comm_unique_id": (C.c_int, [C.c_void_p]),

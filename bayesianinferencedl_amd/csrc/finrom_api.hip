@@ -1967,6 +1967,54 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
                             (double*)prior->fpart.p, (int*)prior->ftick.p, st);
 }
 
+// multi-start L-BFGS (lbfgs_kernels.hip): every check on the host, before the stream is looked at
+static int lbfgs_dev(const finrom_lbfgs_state* a, LbfgsDev* L, const char* who) {
+  auto bad = [&](const std::string& what) { set_error(std::string(who) + ": " + what); return FINROM_ERR_ARG; };
+  if (!a) return bad("null state");
+  if (a->S < 1) return bad("S = " + std::to_string(a->S) + " (need S >= 1)");
+  if (a->S > 0x7fffffff) return bad("S = " + std::to_string(a->S) + " (one workgroup per start: need S < 2^31)");
+  if (a->d < 1) return bad("d = " + std::to_string(a->d) + " (need d >= 1)");
+  if (a->m < 1 || a->m > LBFGS_MAX_M) return bad("m = " + std::to_string(a->m) + " (need 1 <= m <= 16)");
+  if (a->maxls < 1) return bad("maxls = " + std::to_string(a->maxls) + " (need maxls >= 1)");
+  if (a->G != nullptr && (a->gdim < 1 || a->gdim > LBFGS_MAX_GDIM)) return bad("gdim = " + std::to_string(a->gdim) + " (need 1 <= gdim <= 16 with G)");
+  if (a->G == nullptr && a->gdim != 0) return bad("gdim = " + std::to_string(a->gdim) + " without G (need 0)");
+  if (a->k1_ptr != nullptr && (!a->k1_idx || !a->k1_val)) return bad("null k1_idx or k1_val with k1_ptr");
+  if (a->fhist != nullptr && a->fhist_rows < 1) return bad("fhist_rows = " + std::to_string(a->fhist_rows) + " with fhist (need >= 1)");
+  const char* null_name = !a->x ? "x" : !a->f ? "f" : !a->g ? "g" : !a->xt ? "xt" : !a->work ? "work" : !a->status ? "status" :
+                          !a->nit ? "nit" : !a->nfev ? "nfev" : nullptr;
+  if (null_name) return bad(std::string("null ") + null_name);
+  if ((int64_t)a->d > (int64_t)LBFGS_MAX_E * 256) {
+    set_error(std::string(who) + ": d = " + std::to_string(a->d) + " > 4352 (the kernels hold a start's vectors in registers)");
+    return FINROM_ERR_UNSUPPORTED;
+  }
+  L->S = a->S; L->d = a->d; L->m = a->m; L->maxls = a->maxls; L->gdim = a->G ? a->gdim : 0;
+  L->ftol = a->ftol; L->gtol = a->gtol; L->gamma = a->gamma; L->maxiter = a->maxiter; L->maxfun = a->maxfun;
+  L->lo = a->lo; L->hi = a->hi; L->x = a->x; L->f = a->f; L->g = a->g; L->xt = a->xt; L->work = a->work;
+  L->status = a->status; L->nit = (long long*)a->nit; L->nfev = (long long*)a->nfev;
+  L->fhist = a->fhist; L->fhist_rows = a->fhist ? a->fhist_rows : 0; L->G = a->G;
+  L->k1_ptr = a->k1_ptr; L->k1_idx = a->k1_idx; L->k1_val = a->k1_val;
+  return 0;
+}
+int finrom_lbfgs_begin(const finrom_lbfgs_state* a, void* stream) {
+  LbfgsDev L;
+  if (int rc = lbfgs_dev(a, &L, "lbfgs_begin")) return rc;
+  CallGuard cg((hipStream_t)stream);
+  return launch_lbfgs_begin(L, (hipStream_t)stream);
+}
+int finrom_lbfgs_propose(const finrom_lbfgs_state* a, void* stream) {
+  LbfgsDev L;
+  if (int rc = lbfgs_dev(a, &L, "lbfgs_propose")) return rc;
+  CallGuard cg((hipStream_t)stream);
+  return launch_lbfgs_propose(L, (hipStream_t)stream);
+}
+int finrom_lbfgs_accept(const finrom_lbfgs_state* a, const double* f_in, const double* g_in, const int32_t* info, void* stream) {
+  LbfgsDev L;
+  if (int rc = lbfgs_dev(a, &L, "lbfgs_accept")) return rc;
+  if (!f_in || !g_in) { set_error(std::string("lbfgs_accept: null ") + (!f_in ? "f_in" : "g_in")); return FINROM_ERR_ARG; }
+  CallGuard cg((hipStream_t)stream);
+  return launch_lbfgs_accept(L, f_in, g_in, info, (hipStream_t)stream);
+}
+
 int finrom_sub(const double* a, const double* b, int64_t count, double* out, void* stream) {
   CallGuard cg((hipStream_t)stream);
   if (count < 0 || (count > 0 && (!a || !b || !out))) { set_error("sub: bad argument"); return FINROM_ERR_ARG; }

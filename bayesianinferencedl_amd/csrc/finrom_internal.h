@@ -74,6 +74,24 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
 
+// ---- batched multi-start L-BFGS bookkeeping (lbfgs_kernels.hip, finrom_lbfgs_*) ------------------------------------------
+struct LbfgsDev {                // finrom_lbfgs_state, validated
+  int64_t S; int d, m, maxls, gdim;
+  double ftol, gtol, gamma; long long maxiter, maxfun;
+  const double* lo; const double* hi;
+  double* x; double* f; double* g; double* xt; double* work;
+  int* status; long long* nit; long long* nfev; double* fhist; long long fhist_rows;
+  const double* G;
+  const int* k1_ptr; const int* k1_idx; const double* k1_val;
+};
+constexpr int LBFGS_MAX_M = 16;
+constexpr int LBFGS_MAX_E = 17;          // elements per thread in registers: d <= 17 * 256 = 4352 (the m = 20 field mesh has 4101)
+constexpr int LBFGS_MAX_GDIM = 16;
+__host__ __device__ inline int64_t lbfgs_work_stride(int d, int m) { return (2 * (int64_t)m + 1) * d + 2 * (int64_t)m + 8; }
+int launch_lbfgs_begin(const LbfgsDev& L, hipStream_t st);
+int launch_lbfgs_propose(const LbfgsDev& L, hipStream_t st);
+int launch_lbfgs_accept(const LbfgsDev& L, const double* f_in, const double* g_in, const int* info, hipStream_t st);
+
 // ---- latent Gaussian-field prior (field_prior.hip, finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field) --------------
 // the pullback's epilogue in a whitened leapfrog step (c_pri = 1):  dU = vq + c_lik g_v (0 for a flagged sample);  mom -= eps dU
 struct FieldPriorTail {

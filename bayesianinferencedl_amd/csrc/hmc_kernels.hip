@@ -4,19 +4,11 @@
 // i.i.d. Gaussian prior of bayesian_inference/hmc.py (with mean 0 and c_pri = 1 also the whitened form of the latent Gaussian-field
 // prior, finrom_hmc_leapfrog_field).  One workgroup per chain; sums over the field in a fixed order.
 #include "finrom_internal.h"
+#include "block_reduce.h"
 
 namespace finrom {
 
 namespace {
-
-__device__ __forceinline__ double block_sum_256(double v, double* red) {      // 256 threads, fixed order
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // proposal jt of the uploaded block: momentum P0, Hamiltonian at the start, first half step of the momentum
 __global__ __launch_bounds__(256) void hmc_begin_kernel(HmcDev h) {

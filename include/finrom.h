@@ -430,6 +430,46 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
                               int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
                               void* stream);
 
+/* ---- batched multi-start MAP estimation: a projected L-BFGS on the device ------------------------------------------------------- *
+ * The reference minimises 0.5 |y(k) - d|^2 + reg(k) with SciPy's L-BFGS-B, one start after another (bayesian_inference/
+ * estimate_MAP.py:246-281).  Here S starts advance in lockstep on device-resident state, and a ROUND is three pieces in stream
+ * order, the same launches every round (so it can be captured once in a HIP graph and replayed; bayesian_inference/lbfgs.py):
+ *   finrom_lbfgs_propose  per running start: the free set, the two-loop L-BFGS direction and the trial point xt = P(x + alpha d)
+ *                         (or the next backtracked trial on the stored direction); a stopped start copies x to xt;
+ *   (the caller's model)  f_in [S], g_in [S x d] -- or [S x gdim] when G is set -- and info [S] (non-zero: flagged) at xt;
+ *   finrom_lbfgs_accept   the pieces the library owns -- g = G^T g_in (G [gdim x d], gdim <= 16) and the Tikhonov term
+ *                         0.5 gamma x^T K1 x with gradient gamma K1 x (K1 as CSR) -- then the Armijo test, the backtrack, the
+ *                         history ring (m pairs), the stopping tests (SciPy's), the counters and an optional fhist row.
+ * finrom_lbfgs_begin projects x (set by the caller to the starts) into [lo, hi], copies it to xt and marks every start running;
+ * the first accept after it takes the model's values at x0.  Algorithm: lbfgs.py (minimize_host is its NumPy statement; a
+ * projected L-BFGS with Armijo backtracking on the projection arc, not Byrd et al.'s L-BFGS-B).  Every sum has a fixed order:
+ * results are the same bits run to run, and a start's result depends on its own row only.
+ * status [S]: -1 running, 0 converged (projected gradient or relative reduction), 1 iteration / evaluation limit, 2 line search
+ * failed with an empty history, 3 the start itself is flagged or not finite.  All arrays are DEVICE pointers owned by the caller;
+ * lo / hi [d] or NULL (unbounded side); the caller checks lo <= hi.  work holds FINROM_LBFGS_WORK_DOUBLES(S, d, m) doubles
+ * (per start: the s and y rings, the direction, s^T y, y^T y and 8 scalars; the reason of a start's stop is scalar 5:
+ * 0 projected gradient, 1 relative reduction, 2 iterations, 3 evaluations, 4 line search, 5 flagged).  fhist [fhist_rows x S]
+ * or NULL: row i = f after iteration i.  Tikhonov is on when k1_ptr is set (k1_ptr [d + 1], k1_idx, k1_val).
+ * Checks before any device call: S >= 1, d >= 1, 1 <= m <= 16, the required pointers, 1 <= gdim <= 16 when G is set (0
+ * otherwise), maxls >= 1 -- FINROM_ERR_ARG with a message naming the argument; d > 4352 is FINROM_ERR_UNSUPPORTED.  No
+ * allocation: the calls may be captured. */
+#define FINROM_LBFGS_WORK_DOUBLES(S, d, m) ((int64_t)(S) * ((2 * (int64_t)(m) + 1) * (int64_t)(d) + 2 * (int64_t)(m) + 8))
+typedef struct {
+  int64_t S; int32_t d, m;              /* starts, variables, history pairs */
+  double ftol, gtol;                    /* SciPy's: relative reduction, projected-gradient infinity norm */
+  int64_t maxiter, maxfun; int32_t maxls;
+  const double* lo; const double* hi;   /* [d] or NULL */
+  double* x; double* f; double* g; double* xt;   /* [S x d], [S], [S x d], [S x d] (trial point: the model's input) */
+  double* work;                         /* FINROM_LBFGS_WORK_DOUBLES(S, d, m) */
+  int32_t* status; int64_t* nit; int64_t* nfev;  /* [S] */
+  double* fhist; int64_t fhist_rows;    /* [fhist_rows x S] or NULL */
+  const double* G; int32_t gdim;        /* [gdim x d] or NULL (then gdim = 0) */
+  double gamma; const int32_t* k1_ptr; const int32_t* k1_idx; const double* k1_val;   /* Tikhonov, or k1_ptr = NULL */
+} finrom_lbfgs_state;
+int finrom_lbfgs_begin(const finrom_lbfgs_state* st, void* stream);
+int finrom_lbfgs_propose(const finrom_lbfgs_state* st, void* stream);
+int finrom_lbfgs_accept(const finrom_lbfgs_state* st, const double* f_in, const double* g_in, const int32_t* info, void* stream);
+
 /* ---- sub-fin averages  theta = S k  (fom :466-480, rom :404-418) -------------------- *
  * Sop is the dense [P x n] averaging operator on the device (finrom_malloc + h2d). */
 int finrom_subfin_avg(const double* Sop, int32_t P, int32_t n,
