@@ -10,13 +10,16 @@ The algorithm is a projected L-BFGS with Armijo backtracking along the projectio
 L-BFGS-B: there is no generalised Cauchy point, no subspace minimisation and no More-Thuente line search.  Per start, with
 P = clip(., lo, hi):
   0. x = P(x0); f, g at x.  Flagged / not finite: status 3.  |P(x - g) - x|_inf <= gtol: status 0, nit = 0.
+     A point is FLAGGED when the objective says so, when its value is NaN or +-inf, or when any component of its gradient is
+     (after the library's terms: G^T and Tikhonov) -- a model's info != 0 means the same elsewhere in the library.  A value
+     without a usable gradient is never accepted, so the stored g is always finite while a start runs.
   1. Free set: variables strictly inside the box, and those on a bound where -g points into the box (g < 0 at lo, g > 0 at hi);
      lo == hi is never free.  q = g on the free set, 0 elsewhere.
   2. d = -H q by the two-loop recursion over the stored pairs (newest first), H0 = (s^T y / y^T y) I from the newest pair, or I;
      d = 0 outside the free set.  If g^T d >= 0 (round-off only): drop the history, d = -q.
   3. alpha = min(1, 1 / |d|_2) with an empty history, else 1;  xt = P(x + alpha d), p = xt - x.
-  4. Accept if f(xt) is finite, not flagged and f(xt) <= f + 1e-4 g^T p; else alpha *= clip(t*, 0.1, 0.5),
-     t* = -g^T p / (2 (f(xt) - f - g^T p)) (0.1 if f(xt) is not finite), same d.  After maxls rejected trials: drop a non-empty
+  4. Accept if xt is not flagged and f(xt) <= f + 1e-4 g^T p; else alpha *= clip(t*, 0.1, 0.5),
+     t* = -g^T p / (2 (f(xt) - f - g^T p)) (0.1 if xt is flagged), same d.  After maxls rejected trials: drop a non-empty
      history and go to 1 (steepest descent); with an empty history, status 2.
   5. On accept: keep (s, y) = (p, g(xt) - g) in a ring of maxcor pairs if s^T y > eps y^T y; move; nit += 1.
   6. Status 0 when |P(x - g) - x|_inf <= gtol, or when f_old - f <= ftol max(|f_old|, |f|, 1) (SciPy's tests and messages);
@@ -43,7 +46,7 @@ MESSAGES = {0: "CONVERGENCE: NORM OF PROJECTED GRADIENT <= PGTOL",
             2: "STOP: TOTAL NO. OF ITERATIONS REACHED LIMIT",
             3: "STOP: TOTAL NO. OF F,G EVALUATIONS EXCEEDS LIMIT",
             4: "ABNORMAL_TERMINATION_IN_LNSRCH",
-            5: "the start point is flagged or its value is not finite"}
+            5: "the start point is flagged, or its value or gradient is not finite"}
 _STATUS_OF_REASON = {0: 0, 1: 0, 2: 1, 3: 1, 4: 2, 5: 3}
 _LANES, _WAVE = 256, 64
 
@@ -188,6 +191,67 @@ def _direction(st, x, g, lo, hi, m):
     st.dir, st.alpha, st.nls, st.phase = d, alpha, 0, "ls"
 
 
+def _first(s, x, g, bad, lo, hi, gtol, maxiter, maxfun):
+    """Step 0 for one start after the evaluation at x0 (bad: flagged, or a value or gradient component that is not finite)."""
+    s.nfev = 1
+    s.phase = "new"
+    if bad:
+        s.reason = 5
+    elif _pgnorm(x, g, lo, hi) <= gtol:
+        s.reason = 0
+    elif s.nfev >= maxfun:
+        s.reason = 3
+    elif maxiter <= 0:
+        s.reason = 2
+
+
+def _accept(s, x, f, g, xt, ft, gt, bt, lo, hi, m, ftol, gtol, maxiter, maxfun, maxls):
+    """Steps 4-6 for one running start with value ft, gradient gt and flag bt at its trial point xt: on acceptance x and g (rows,
+    written in place) move and the pair goes to the ring; otherwise the step shrinks, the history is dropped or the start stops.
+    -> (the start's value afterwards, whether it moved)."""
+    s.nfev += 1
+    p = xt - x
+    gtp = _dot(g, p)
+    flagged = bool(bt) or not np.isfinite(ft) or not bool(np.all(np.isfinite(gt)))
+    if not flagged and ft <= f + 1e-4 * gtp:
+        y = gt - g
+        sy, yy = _dot(p, y), _dot(y, y)
+        if sy > EPS * yy:
+            s.s[s.head], s.y[s.head], s.sy[s.head], s.yy[s.head] = p, y, sy, yy
+            s.head = (s.head + 1) % m
+            s.k = min(s.k + 1, m)
+        f_old = f
+        x[:], g[:] = xt, gt
+        f = float(ft)
+        s.nit += 1
+        s.phase = "new"
+        if _pgnorm(x, g, lo, hi) <= gtol:
+            s.reason = 0
+        elif f_old - f <= ftol * max(abs(f_old), abs(f), 1.0):
+            s.reason = 1
+        elif s.nit >= maxiter:
+            s.reason = 2
+        elif s.nfev >= maxfun:
+            s.reason = 3
+        return f, True
+    s.nls += 1
+    if s.nls >= maxls:
+        if s.k > 0:
+            s.k, s.phase = 0, "new"
+        else:
+            s.reason = 4
+    else:
+        tq = 0.1
+        if not flagged:
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                tq = float(-gtp / (2.0 * (ft - f - gtp)))
+        tq = (tq if tq < 0.5 else 0.5) if tq > 0.1 else 0.1      # (NaN: 0.1)
+        s.alpha = s.alpha * tq
+    if s.reason is None and s.nfev >= maxfun:
+        s.reason = 3
+    return f, False
+
+
 def minimize_host(value_and_grad, X0, *, bounds=None, maxcor=10, ftol=2.220446049250313e-09, gtol=1e-5, maxiter=15000,
                   maxfun=15000, maxls=20, keep_history=False):
     """Minimise S independent starts X0 [S, d] in lockstep on the host (NumPy): the specification of minimize_device.
@@ -203,20 +267,11 @@ def minimize_host(value_and_grad, X0, *, bounds=None, maxcor=10, ftol=2.22044604
     st = [_Start(m, d) for _ in range(S)]
     f, G, bad = value_and_grad(X.copy())
     f = np.array(f, dtype=np.float64).reshape(S); G = np.array(G, dtype=np.float64).reshape(S, d)
-    bad = np.asarray(bad, dtype=bool).reshape(S) | ~np.isfinite(f)
+    bad = np.asarray(bad, dtype=bool).reshape(S) | ~np.isfinite(f) | ~np.all(np.isfinite(G), axis=1)
     f = np.where(bad, np.inf, f)
     hist = [f.copy()] if keep_history else None
     for c in range(S):
-        s = st[c]
-        s.nfev = 1
-        if bad[c]:
-            s.reason = 5
-        elif _pgnorm(X[c], G[c], lo, hi) <= gtol:
-            s.reason = 0
-        elif s.nfev >= maxfun:
-            s.reason = 3
-        elif maxiter <= 0:
-            s.reason = 2
+        _first(st[c], X[c], G[c], bad[c], lo, hi, gtol, maxiter, maxfun)
     Xt = X.copy()
     while any(s.reason is None for s in st):
         for c in range(S):                                   # propose
@@ -235,47 +290,9 @@ def minimize_host(value_and_grad, X0, *, bounds=None, maxcor=10, ftol=2.22044604
             s = st[c]
             if s.reason is not None:
                 continue
-            s.nfev += 1
-            p = Xt[c] - X[c]
-            gtp = _dot(G[c], p)
-            flagged = bool(bt[c]) or not np.isfinite(ft[c])
-            if not flagged and ft[c] <= f[c] + 1e-4 * gtp:
-                y = Gt[c] - G[c]
-                sy, yy = _dot(p, y), _dot(y, y)
-                if sy > EPS * yy:
-                    s.s[s.head], s.y[s.head], s.sy[s.head], s.yy[s.head] = p, y, sy, yy
-                    s.head = (s.head + 1) % m
-                    s.k = min(s.k + 1, m)
-                f_old = f[c]
-                X[c], f[c], G[c] = Xt[c], ft[c], Gt[c]
-                s.nit += 1
-                s.phase = "new"
-                if row is not None:
-                    row[c] = f[c]
-                if _pgnorm(X[c], G[c], lo, hi) <= gtol:
-                    s.reason = 0
-                elif f_old - f[c] <= ftol * max(abs(f_old), abs(f[c]), 1.0):
-                    s.reason = 1
-                elif s.nit >= maxiter:
-                    s.reason = 2
-                elif s.nfev >= maxfun:
-                    s.reason = 3
-                continue
-            s.nls += 1
-            if s.nls >= maxls:
-                if s.k > 0:
-                    s.k, s.phase = 0, "new"
-                else:
-                    s.reason = 4
-            else:
-                tq = 0.1
-                if not flagged:
-                    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-                        tq = float(-gtp / (2.0 * (ft[c] - f[c] - gtp)))
-                tq = (tq if tq < 0.5 else 0.5) if tq > 0.1 else 0.1      # (NaN: 0.1)
-                s.alpha = s.alpha * tq
-            if s.reason is None and s.nfev >= maxfun:
-                s.reason = 3
+            f[c], moved = _accept(s, X[c], f[c], G[c], Xt[c], ft[c], Gt[c], bt[c], lo, hi, m, ftol, gtol, maxiter, maxfun, maxls)
+            if moved and row is not None:
+                row[c] = f[c]
         if keep_history and any(np.isfinite(row)):
             hist.append(row)
     fhist = None

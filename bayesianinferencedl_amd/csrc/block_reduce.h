@@ -27,6 +27,19 @@ __device__ __forceinline__ void block_sum2_256(double& a, double& b, double* red
   b = (red[4] + red[5]) + (red[6] + red[7]);
 }
 
+// block_sum2_256 and, in the same LDS exchange, whether `flag` is set on any thread (a wave vote: no shuffle).  red: 12 doubles.
+__device__ __forceinline__ bool block_sum2_any_256(double& a, double& b, bool flag, double* red) {
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+  const double fl = __any(flag) ? 1.0 : 0.0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[wave] = a; red[4 + wave] = b; red[8 + wave] = fl; }
+  __syncthreads();
+  a = (red[0] + red[1]) + (red[2] + red[3]);
+  b = (red[4] + red[5]) + (red[6] + red[7]);
+  return (red[8] + red[9]) + (red[10] + red[11]) != 0.0;
+}
+
 // the same pattern for a maximum (exact in any order; NaN-free inputs)
 __device__ __forceinline__ double block_max_256(double v, double* red) {
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));

@@ -160,10 +160,11 @@ __global__ __launch_bounds__(256) void lbfgs_propose_kernel(LbfgsDev L) {
 }
 
 // the objective pieces the library owns at xt, the Armijo test, the history and the stopping tests
+// (a trial is flagged when info says so or when its value or any component of its gradient is not finite: lbfgs.py, finrom.h)
 template <int E>
 __global__ __launch_bounds__(256) void lbfgs_accept_kernel(LbfgsDev L, const double* __restrict__ f_in, const double* __restrict__ g_in,
                                                            const int* __restrict__ info) {
-  __shared__ double red[8];
+  __shared__ double red[12];
   const int64_t c = blockIdx.x;
   const int t = threadIdx.x, d = L.d;
   const int running = L.status[c] == -1;
@@ -176,6 +177,7 @@ __global__ __launch_bounds__(256) void lbfgs_accept_kernel(LbfgsDev L, const dou
   const double* xt = L.xt + c * d;
   double xtv[E], gt[E];
   double preg = 0.0;
+  bool gnf = false;                                      // a component of the gradient at xt is NaN or +-inf
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int j = t + 256 * e;
@@ -196,6 +198,7 @@ __global__ __launch_bounds__(256) void lbfgs_accept_kernel(LbfgsDev L, const dou
         preg = preg + xtv[e] * kx;
       }
       gt[e] = gj;
+      gnf = gnf || !(fabs(gj) <= 1.7976931348623157e308);
     }
   }
   double* x = L.x + c * d; double* g = L.g + c * d;
@@ -207,11 +210,11 @@ __global__ __launch_bounds__(256) void lbfgs_accept_kernel(LbfgsDev L, const dou
     xv[e] = 0.0; gv[e] = 0.0;
     if (j < d) { xv[e] = x[j]; gv[e] = g[j]; p = p + gv[e] * (xtv[e] - xv[e]); }
   }
-  block_sum2_256(p, preg, red);                          // g^T p and x^T K1 x
+  gnf = block_sum2_any_256(p, preg, gnf, red);           // g^T p and x^T K1 x
   const double gtp = p;
   double ft = f_in[c];
   if (L.k1_ptr != nullptr) ft = ft + 0.5 * L.gamma * preg;
-  const bool bad = (info != nullptr && info[c] != 0) || !(ft == ft) || ft > 1.7976931348623157e308 || ft < -1.7976931348623157e308;
+  const bool bad = (info != nullptr && info[c] != 0) || gnf || !(ft == ft) || ft > 1.7976931348623157e308 || ft < -1.7976931348623157e308;
   if (phase == PH_INIT) {                                 // x0 (= xt): the first evaluation
     double pg = 0.0;
 #pragma unroll

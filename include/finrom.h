@@ -445,7 +445,9 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
  * projected L-BFGS with Armijo backtracking on the projection arc, not Byrd et al.'s L-BFGS-B).  Every sum has a fixed order:
  * results are the same bits run to run, and a start's result depends on its own row only.
  * status [S]: -1 running, 0 converged (projected gradient or relative reduction), 1 iteration / evaluation limit, 2 line search
- * failed with an empty history, 3 the start itself is flagged or not finite.  All arrays are DEVICE pointers owned by the caller;
+ * failed with an empty history, 3 the start itself is flagged or not finite.  A point counts as flagged when info is non-zero, when
+ * its value (with the Tikhonov term) is NaN or +-inf, or when any component of its gradient g (after G^T and the Tikhonov term) is:
+ * at x0 that is status 3, later a rejected trial.  All arrays are DEVICE pointers owned by the caller;
  * lo / hi [d] or NULL (unbounded side); the caller checks lo <= hi.  work holds FINROM_LBFGS_WORK_DOUBLES(S, d, m) doubles
  * (per start: the s and y rings, the direction, s^T y, y^T y and 8 scalars; the reason of a start's stop is scalar 5:
  * 0 projected gradient, 1 relative reduction, 2 iterations, 3 evaluations, 4 line search, 5 flagged).  fhist [fhist_rows x S]

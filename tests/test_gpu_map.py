@@ -91,9 +91,10 @@ def _as_host(f):
 
 @pytest.mark.parametrize("problem", ["quadratic", "rosenbrock"])
 def test_device_minimiser_matches_its_host_specification(setup, problem):
-    """minimize_device == minimize_host on torch objectives at S = 1, 6 and 64: fhist and x to 1e-12, the same nit / status;
-    graph and stream order bit-identical, two runs bit-identical, start i alone == start i inside the batch of 64.  (Both sides sum
-    in the same order without contraction; measured on MI355X: within these tolerances at every S.)"""
+    """minimize_device == minimize_host on torch objectives at S = 1, 6 and 64: fhist, x, fun and jac bit for bit, the same nit /
+    nfev / status; graph and stream order bit-identical, two runs bit-identical, start i alone == start i inside the batch of 64.
+    (Both sides sum in the same order without contraction and evaluate the objective with the same torch kernels on the same
+    inputs; tests/test_gpu_lbfgs_kernels.py holds the kernels to the same equality against an objective that stays on the host.)"""
     import torch
     from bayesianinferencedl_amd.bayesian_inference import lbfgs
     if problem == "quadratic":
@@ -121,8 +122,11 @@ def test_device_minimiser_matches_its_host_specification(setup, problem):
         assert fh_d.shape == fh_h.shape
         fin = np.isfinite(fh_h)
         assert np.array_equal(np.isfinite(fh_d), fin)
-        assert np.all(np.abs(fh_d[fin] - fh_h[fin]) <= 1e-12 * np.maximum(np.abs(fh_h[fin]), 1e-300))
-        assert np.linalg.norm(dev.x - host.x) <= 1e-12 * np.linalg.norm(host.x)
+        print(f"{problem}, S = {S}: max |fhist_dev - fhist_host| = {np.max(np.abs(fh_d[fin] - fh_h[fin])):.3e}, "
+              f"max |x_dev - x_host| = {np.max(np.abs(dev.x - host.x)):.3e}")
+        assert np.array_equal(fh_d, fh_h, equal_nan=True)
+        assert np.array_equal(dev.x, host.x) and np.array_equal(dev.fun, host.fun) and np.array_equal(dev.jac, host.jac)
+        assert np.array_equal(dev.nfev, host.nfev)
         assert np.all(dev.x >= lo) and np.all(dev.x <= hi)
         if S == 64:
             again = lbfgs.minimize_device(f, X0, bounds=bounds, **kw)

@@ -174,3 +174,127 @@ def test_lbfgs_entry_points_validate_their_state_before_any_device_call():
     assert L.finrom_lbfgs_accept(C.byref(state(S=-1)), None, None, None, None) == -1 and b"S = -1" in L.finrom_last_error()
     assert L.finrom_lbfgs_accept(C.byref(state()), None, None, None, None) == -1 and b"null x" in L.finrom_last_error()
     assert L.finrom_deferred_count() == 0
+
+
+# ---- the cases of tests/test_gpu_lbfgs_kernels.py: each takes, on the host alone, the branch it is named for ----------------------
+import lbfgs_cases as K  # noqa: E402
+
+
+def test_lbfgs_e_is_restated_from_the_kernel_source_and_the_ladder_covers_every_form():
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(lbfgs.__file__), "..", "csrc", "lbfgs_kernels.hip")).read()
+    assert re.search(r"n <= 1 \? 1 : n <= 2 \? 2 : n <= 4 \? 4 : n <= 8 \? 8 : n <= LBFGS_MAX_E \? LBFGS_MAX_E : 0", src)
+    hdr = open(os.path.join(os.path.dirname(lbfgs.__file__), "..", "csrc", "finrom_internal.h")).read()
+    assert re.search(r"LBFGS_MAX_E\s*=\s*17\b", hdr)
+    assert [K.lbfgs_e(d) for d in (1, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4352, 4353)] == [1, 1, 2, 2, 4, 4, 8, 8, 17, 17, 0]
+    assert [K.lbfgs_e(d) for d in K.FORM_D] == list(K.FORMS)
+    for e in K.FORMS:
+        ds = [d for d in K.LADDER if K.lbfgs_e(d) == e]
+        assert len(ds) >= 2 and (ds[0] == 1 or K.lbfgs_e(ds[0] - 1) != e) and K.lbfgs_e(ds[-1] + 1) != e, (e, ds)   # both ends of the form
+
+
+@pytest.mark.parametrize("d", K.LADDER)
+def test_ladder_cases_iterate(d):
+    res, tr = K.ladder_case(d).check()
+    assert np.all(res.nit >= 3) and tr["accepted"] == res.nit.sum()
+    if d >= 255:
+        assert tr["wrapped"] > 0 and np.all(res.nit == 24)
+
+
+@pytest.mark.parametrize("d,maxcor,mode", K.OPTION_GRID)
+def test_option_cases_wrap_the_ring_and_backtrack(d, maxcor, mode):
+    res, tr = K.option_case(d, maxcor, mode).check()
+    lo, hi = lbfgs._box(K.option_case(d, maxcor, mode).kw["bounds"], d)
+    assert np.all(res.x >= lo) and np.all(res.x <= hi)
+    if mode == "both":                                       # starts outside the box, fixed components, active bounds at the end
+        assert np.any(K.option_case(d, maxcor, mode).X0 > hi) and np.any(lo == hi) and np.any((res.x == lo) | (res.x == hi))
+
+
+@pytest.mark.parametrize("d", K.FORM_D)
+def test_batch_case_runs_past_three_rings(d):
+    K.batch_case(d, S=8).check()
+
+
+@pytest.mark.parametrize("which", K.TERMS)
+@pytest.mark.parametrize("d", K.FORM_D)
+def test_library_terms_cases_iterate(d, which):
+    case = K.terms_case(d, which)
+    res, tr = case.check()
+    assert (case.gmap is None or case.gmap.shape == ({"gmap1": 1, "gmap9": 9, "gmap16": 16, "both": 9}[which], d))
+    assert (case.tikhonov is not None) == (which in ("tikhonov", "both"))
+
+
+@pytest.mark.parametrize("name,d", K.STOP_GRID)
+def test_stop_cases_end_for_the_reason_they_are_named_for(name, d):
+    K.stop_case(name, d).check()
+
+
+def test_every_stop_reason_has_a_case():
+    seen = set()
+    for name in K.STOPS:
+        seen |= set(K._reasons(K.stop_case(name).host()))
+    assert seen == {0, 1, 2, 3, 4, 5}
+
+
+def test_a_finite_value_with_a_gradient_that_is_not_finite_is_flagged():
+    """The decision of step 0 / step 4: status 3 at x0 (the device used to stop with status 0 and a NaN in jac when every other
+    component was within gtol, the host ran on), a rejected trial later (never a NaN in the stored gradient or the history)."""
+    res = K.stop_case("gnan_at_rest").host()
+    assert res.status[0] == 3 and res.nit[0] == 0 and res.nfev[0] == 1 and "gradient" in res.message[0]
+    for kind in ("gnan", "ginf"):
+        res, tr = K.stop_case(kind).traced()
+        assert tr["flagged"] > 10 and np.all(np.isfinite(res.jac[1:])) and np.all(np.isfinite(res.fhist[0, 1:]))
+
+
+# ---- the kernels' resources, read from the build: registers without scratch ------------------------------------------------------
+def test_lbfgs_kernels_use_no_scratch_and_spill_nothing(tmp_path):
+    """All eleven kernels of csrc/lbfgs_kernels.hip, compiled for gfx950 with _build.py's flags: no private segment (scratch) and
+    no spilled VGPR -- the register forms are sized so that a start's vectors stay in registers up to d = 4352."""
+    import os
+    import re
+    import subprocess
+    from bayesianinferencedl_amd import _build
+    try:
+        hipcc = _build._hipcc()
+        subprocess.run([hipcc, "--version"], capture_output=True, check=True)
+    except (RuntimeError, OSError, subprocess.CalledProcessError) as exc:
+        pytest.skip(f"hipcc not found ({exc})")
+    asm = tmp_path / "lbfgs_kernels.s"
+    src = os.path.join(_build.CSRC, "lbfgs_kernels.hip")
+    r = subprocess.run([hipcc, *_build.FLAGS, _build.OPT.get("lbfgs_kernels.hip", "-O3"), "--cuda-device-only", "-S", src, "-o", str(asm)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    text = asm.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    kernels = {}
+    for blk in re.split(r"\n  - (?=\.)", meta)[1:]:
+        name = re.search(r"^\s*\.name:\s*(\S+)", blk, flags=re.M)
+        if name is None:
+            continue
+        kernels[name.group(1)] = {k: int(v) for k, v in re.findall(r"^\s*\.(private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count|sgpr_count):\s*(\d+)", blk, flags=re.M)}
+    want = [r"lbfgs_begin_kernel"] + [rf"lbfgs_{k}_kernelILi{e}E" for k in ("propose", "accept") for e in K.FORMS]
+    assert len(kernels) == len(want) == 11, sorted(kernels)
+    for pat in want:
+        hit = [n for n in kernels if re.search(pat, n)]
+        assert len(hit) == 1, (pat, sorted(kernels))
+        res = kernels[hit[0]]
+        print(f"{pat:32s} VGPRs {res['vgpr_count']:3d}  SGPRs {res['sgpr_count']:3d} ({res['sgpr_spill_count']} kept in VGPR lanes)  "
+              f"scratch {res['private_segment_fixed_size']}")
+        assert res["private_segment_fixed_size"] == 0 and res["vgpr_spill_count"] == 0, (pat, res)
+
+
+def test_d_above_4352_is_unsupported_by_all_three_entry_points():
+    """The size check comes after the null-pointer checks: the state carries non-null pointers (nothing is dereferenced: the call
+    returns before any device call).  d = 4352 passes the checks and runs: tests/test_gpu_lbfgs_kernels.py."""
+    from bayesianinferencedl_amd import _ffi
+    L = _ffi.lib()
+    buf = (C.c_double * 8)()
+    p = C.addressof(buf)
+    ptrs = dict(x=p, f=p, g=p, xt=p, work=p, status=p, nit=p, nfev=p)
+    st = _ffi.LbfgsState(S=1, d=4353, m=5, ftol=1e-9, gtol=1e-5, maxiter=10, maxfun=10, maxls=20, **ptrs)
+    unsupported = -4                                         # FINROM_ERR_UNSUPPORTED (include/finrom.h)
+    for call in (lambda: L.finrom_lbfgs_begin(C.byref(st), None), lambda: L.finrom_lbfgs_propose(C.byref(st), None),
+                 lambda: L.finrom_lbfgs_accept(C.byref(st), p, p, None, None)):
+        assert call() == unsupported and b"4352" in L.finrom_last_error() and b"d = 4353" in L.finrom_last_error()
+    assert L.finrom_deferred_count() == 0
