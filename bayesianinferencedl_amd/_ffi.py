@@ -71,6 +71,10 @@ class MlpDesc(C.Structure):
                 ("Wh", c_f32p), ("bh", c_f32p)]
 
 
+class MlpTrainDesc(C.Structure):
+    _fields_ = [("n_in", C.c_int32), ("n_w", C.c_int32), ("n_layers", C.c_int32), ("n_out", C.c_int32), ("max_batch", C.c_int32)]
+
+
 class HmcState(C.Structure):
     _fields_ = [("C", C.c_int64), ("n", C.c_int32), ("eps", C.c_double), ("c_lik", C.c_double), ("c_pri", C.c_double),
                 ("mean", C.c_void_p), ("K", C.c_void_p), ("U", C.c_void_p), ("dU", C.c_void_p),
@@ -168,6 +172,18 @@ SIGNATURES = {
     "finrom_comm_init": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p]),
     "finrom_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_comm_destroy": (C.c_int, [C.c_void_p]),
+    "finrom_mlp_train_create": (C.c_int, [C.POINTER(MlpTrainDesc), C.POINTER(C.c_void_p)]),
+    "finrom_mlp_train_destroy": (None, [C.c_void_p]),
+    "finrom_mlp_train_param_count": (C.c_int64, [C.c_void_p]),
+    "finrom_mlp_train_set_params": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int64]),
+    "finrom_mlp_train_get_params": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.POINTER(C.c_int64)]),
+    "finrom_mlp_train_set_lr": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "finrom_mlp_train_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "finrom_mlp_train_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "finrom_mlp_train_get_grads": (C.c_int, [C.c_void_p, c_f32p, c_f64p]),
+    "finrom_mlp_train_set_grads": (C.c_int, [C.c_void_p, c_f32p, c_f64p, C.c_int32]),
+    "finrom_mlp_train_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_f64p, C.c_void_p]),
+    "finrom_mlp_train_epoch_stats": (C.c_int, [C.c_void_p, c_f64p, C.c_int32, C.c_void_p]),
 }
 
 ABI_VERSION = 12

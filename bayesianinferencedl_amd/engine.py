@@ -600,6 +600,170 @@ class DeviceErrorModel:
             pass
 
 
+class DeviceTrainer:
+    """Training of the learned error model on the device (finrom_mlp_train_*, csrc/mlp_train.hip): the handle owns parameters,
+    Adam's state, moving statistics, tape and workspaces; the dataset stays resident as fp32 torch tensors; an epoch's steps are
+    captured once in a HIP graph and replayed (a linear chain of library launches on one stream; each step takes its rows by
+    index from the epoch's permutation, uploaded into the same device buffer before each replay).  The host statement is
+    ResBnFcModel.fit_host; ResBnFcModel.fit is the front door."""
+
+    def __init__(self, model, max_batch=500):
+        self.model = model
+        d = _ffi.MlpTrainDesc(n_in=model.n_in, n_w=model.n_weights, n_layers=model.n_layers, n_out=model.n_out, max_batch=int(max_batch))
+        h = C.c_void_p()
+        check(lib().finrom_mlp_train_create(C.byref(d), C.byref(h)), "finrom_mlp_train_create")
+        self._h = h
+        self.max_batch = int(max_batch)
+        self.n_flat = int(lib().finrom_mlp_train_param_count(h))
+        self.push()
+
+    @staticmethod
+    def _stream():
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+
+    # -- state to and from the host model ------------------------------------------------------------------------------------------
+    def push(self):
+        """The model's parameters, moving statistics and optimiser state -> the handle."""
+        m = self.model
+        fp = lambda a_: a_.ctypes.data_as(_ffi.c_f32p)
+        p = m.flatten(m._tree())
+        assert p.size == self.n_flat
+        mm = m.flatten(m.opt["m"]) if m.opt["m"] is not None else None
+        vv = m.flatten(m.opt["v"]) if m.opt["v"] is not None else None
+        check(lib().finrom_mlp_train_set_params(self._h, fp(p), fp(mm) if mm is not None else None, fp(vv) if vv is not None else None,
+                                                int(m.opt["t"])), "finrom_mlp_train_set_params")
+
+    def pull(self):
+        """The handle's parameters, moving statistics, m, v, t -> the model (fp32 arrays)."""
+        m = self.model
+        p, mm, vv = (np.empty(self.n_flat, np.float32) for _ in range(3))
+        t = C.c_int64()
+        fp = lambda a_: a_.ctypes.data_as(_ffi.c_f32p)
+        check(lib().finrom_mlp_train_get_params(self._h, fp(p), fp(mm), fp(vv), C.byref(t)), "finrom_mlp_train_get_params")
+        m.set_tree(m.unflatten(p))
+        m.opt["m"], m.opt["v"], m.opt["t"] = m.unflatten(mm), m.unflatten(vv), int(t.value)
+
+    def get_grads(self):
+        """-> (loss, MAPE, gradient tree with the batch statistics in "mean" / "var") of the last finrom_mlp_train_grad."""
+        g = np.empty(self.n_flat, np.float32); lm = np.empty(2)
+        check(lib().finrom_mlp_train_get_grads(self._h, g.ctypes.data_as(_ffi.c_f32p), lm.ctypes.data_as(_ffi.c_f64p)), "finrom_mlp_train_get_grads")
+        return float(lm[0]), float(lm[1]), self.model.unflatten(g)
+
+    def set_grads(self, grads, loss=0.0, mape=0.0, B=2):
+        g = self.model.flatten(grads); lm = np.array([loss, mape], dtype=np.float64)
+        check(lib().finrom_mlp_train_set_grads(self._h, g.ctypes.data_as(_ffi.c_f32p), lm.ctypes.data_as(_ffi.c_f64p), int(B)), "finrom_mlp_train_set_grads")
+
+    # -- the calls -----------------------------------------------------------------------------------------------------------------
+    def set_lr(self, lr):
+        check(lib().finrom_mlp_train_set_lr(self._h, float(lr), self._stream()), "finrom_mlp_train_set_lr")
+
+    def grad(self, X, Y, rows):
+        """X [S, n_in], Y [S, n_out] fp32 and rows [B] int32: contiguous CUDA tensors."""
+        check(lib().finrom_mlp_train_grad(self._h, X.data_ptr(), Y.data_ptr(), rows.data_ptr(), int(rows.numel()), self._stream()), "finrom_mlp_train_grad")
+
+    def apply(self):
+        check(lib().finrom_mlp_train_apply(self._h, self._stream()), "finrom_mlp_train_apply")
+
+    def epoch_stats(self, reset=True):
+        """-> (row-weighted mean loss, mean MAPE, rows) of the steps since the last reset; .last_mse: the mean loss without the
+        regulariser."""
+        o = np.zeros(4)
+        check(lib().finrom_mlp_train_epoch_stats(self._h, o.ctypes.data_as(_ffi.c_f64p), 1 if reset else 0, self._stream()), "finrom_mlp_train_epoch_stats")
+        self.last_mse = o[3] / o[2] if o[2] > 0 else 0.0
+        return (o[0] / o[2], o[1] / o[2], int(o[2])) if o[2] > 0 else (0.0, 0.0, 0)
+
+    def evaluate(self, X, Y):
+        """Inference form over CUDA fp32 tensors -> (loss with the regulariser, MAPE)."""
+        o = np.zeros(2)
+        check(lib().finrom_mlp_train_eval(self._h, X.data_ptr(), Y.data_ptr(), int(X.shape[0]), o.ctypes.data_as(_ffi.c_f64p), self._stream()), "finrom_mlp_train_eval")
+        return float(o[0]), float(o[1])
+
+    def export(self):
+        """The trained weights as a DeviceErrorModel (finrom_mlp_predict / finrom_romml_grad), through the host model's arrays."""
+        self.pull()
+        return DeviceErrorModel(self.model)
+
+    @staticmethod
+    def to_device(a, n):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, n))).cuda()
+
+    def fit(self, z, errors, *, epochs, batch_size=500, shuffle=True, validation_data=None, lr=3e-4, seed=0, graph=True, record_steps=False):
+        """ResBnFcModel.fit_host's run on the device: the same permutations (EpochPlan), the same history object.
+        record_steps: read every step's loss back (history.step_loss; stream order, one synchronisation per step)."""
+        import torch
+        from .deep_learning.dl_model import EpochPlan, History
+        m = self.model
+        X, Y = self.to_device(z, m.n_in), self.to_device(errors, m.n_out)
+        plan = EpochPlan(X.shape[0], batch_size, shuffle, seed, m.opt["epoch"])
+        if plan.B > self.max_batch:
+            raise ValueError(f"DeviceTrainer.fit: batch of {plan.B} rows exceeds max_batch = {self.max_batch}")
+        val = None if validation_data is None else (self.to_device(validation_data[0], m.n_in), self.to_device(validation_data[1], m.n_out))
+        rows_dev = torch.zeros(plan.S, dtype=torch.int32, device="cuda")
+        slices = [rows_dev[i:i + plan.B] for i in range(0, plan.S, plan.B)]
+        self.push()
+        hist = History(val is not None)
+
+        def epoch(record=False):
+            for r in slices:
+                self.grad(X, Y, r)
+                if record:
+                    hist.step_loss.append(self.get_grads()[0])
+                self.apply()
+        g = None
+        if graph and not record_steps and epochs > 0:
+            try:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):                           # warm-up on a side stream, as torch's graph recipe asks:
+                    self.set_lr(0.0)                                    # one step on valid rows, then the state is put back
+                    self.grad(X, Y, slices[0]); self.apply()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                self.push(); self.epoch_stats(reset=True)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    epoch()
+            except _ffi.FinromError:                                    # the library's own error is an error, graph or not
+                raise
+            except RuntimeError as exc:                                 # torch could not capture this sequence: plain stream order
+                import warnings
+                warnings.warn(f"DeviceTrainer: HIP graph capture failed ({exc!r}); the steps are launched kernel by kernel")
+                g = None
+                self.push(); self.epoch_stats(reset=True)
+        self.graph_used = g is not None
+        for _ in range(int(epochs)):
+            e = m.opt["epoch"]
+            self.set_lr(lr(e) if callable(lr) else lr)
+            rows = plan.next_rows()
+            if rows.min() < 0 or rows.max() >= plan.S:
+                raise ValueError("DeviceTrainer.fit: row index outside [0, S)")
+            rows_dev.copy_(torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)))
+            if g is not None:
+                g.replay()
+            else:
+                epoch(record_steps)
+            loss, mape, _ = self.epoch_stats(reset=True)
+            hist.mse.append(self.last_mse)
+            m.opt["epoch"] = e + 1
+            hist.add(loss, mape, self.evaluate(*val) if val is not None else None)
+        torch.cuda.synchronize()
+        self.pull()
+        return hist
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _ffi.destroy_handle("finrom_mlp_train_destroy", self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def romml_grad(rom, mlp, Sop_buf, K, data):
     """finrom_romml_grad: value and gradient of the ROM + learned-error misfit for a batch of nodal fields K [S, n] in ONE
     library call (sub-fin averages, network forward, ROM adjoint against data - e_NN, network backward + chain rule).

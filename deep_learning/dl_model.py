@@ -1,1 +1,2 @@
-from bayesianinferencedl_amd.deep_learning.dl_model import ResBnFcModel, load_dataset_avg_rom, res_bn_fc_model  # noqa: F401
+from bayesianinferencedl_amd.deep_learning.dl_model import (ResBnFcModel, History, load_dataset_avg_rom, lr_schedule, lr_schedule_pre,  # noqa: F401
+                                                            res_bn_fc_model, train_error_model)

@@ -540,6 +540,53 @@ int finrom_comm_destroy(finrom_comm_t comm);
 /* ---- elementwise helper: err = qoi - qoi_r (generate_fin_dataset.py:99) -------------- */
 int finrom_sub(const double* a, const double* b, int64_t count, double* out, void* stream);
 
+/* ---- training the learned error model (deep_learning/dl_model.py:230-243, model.fit) ------------------------------------------ *
+ * The network of finrom_mlp_desc trained in fp32 as Keras trains it in the reference: batch normalisation in training form
+ * (batch mean, biased batch variance, eps 1e-3; moving <- 0.99 moving + 0.01 batch), loss = mean squared error + l1_l2(1e-4, 1e-4)
+ * on W0 and the units' W, Adam in Keras 1.x form (lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t), p -= lr_t m / (sqrt(v) + 1e-7)).
+ * The handle owns parameters, Adam's m and v, the moving statistics, the tape and every workspace, all allocated at create
+ * (n_w, n_out <= 64, n_layers <= 8 -- FINROM_ERR_UNSUPPORTED beyond; max_batch >= 2): no later call allocates.
+ * Host arrays of the set / get calls are fp32 in ONE flat layout, the arrays of ResBnFcModel in this order:
+ *     W0 [n_in x n_w], b0 [n_w], then per layer l = 0 .. n_layers (the last one the head):
+ *     gamma [n_w], beta [n_w], mean [n_w], var [n_w], W [n_w x n_w] (head: [n_w x n_out]), b [n_w] (head: [n_out])
+ * finrom_mlp_train_param_count returns its length.  For m and v the mean / var slots are ignored (read back as zero); for the
+ * gradients they carry the step's batch mean and biased batch variance.
+ *   _set_params / _get_params   parameters with the moving statistics, m, v (NULL: zero / skipped) and Adam's step count t
+ *   _set_lr        the learning rate lives in device memory (the same captured launches serve every epoch); set between replays
+ *   _grad          one batch: X [S x n_in], Y [S x n_out] fp32 device arrays that stay resident, rows [B] device int32 row indices
+ *                  (the batch is taken by index; the caller checks them against S where it builds the permutation).  Training-form
+ *                  forward and backward: every gradient, the batch statistics, loss (with the regulariser) and MAPE
+ *                  (100 mean |y - out| / max(|y|, 1e-7)) into the handle.  2 <= B <= max_batch, FINROM_ERR_ARG otherwise.
+ *   _apply         Adam on every parameter with the gradients in the handle, the moving statistics, t += 1, and the running sums
+ *                  of loss x rows, MAPE x rows, rows, MSE x rows (the loss without the regulariser) that _epoch_stats reads into
+ *                  out [4] (and clears when reset != 0)
+ *   _get_grads / _set_grads   what _grad left / what _apply will use: gradients (flat layout), loss_mape [2] (doubles);
+ *                  _set_grads also takes the row count B that weighs the running sums (its loss stands in for the step's MSE)
+ *   _eval          inference form (moving statistics) over X, Y [S x ...] (any S, in pieces of max_batch): out [2] = loss with the
+ *                  regulariser, MAPE; synchronises the stream
+ * _grad and _apply are launches only -- a linear chain on `stream`, no allocation, no host synchronisation, no atomics, every
+ * sum in a fixed order: stream order and graph replay give the same bits, run to run.  An epoch may be captured in one graph
+ * (each step's `rows` pointer and B are baked in; the permutation is uploaded into the same buffer before each replay).  The
+ * set / get calls, _eval and _epoch_stats synchronise and are refused under capture.  Arguments are checked before any device
+ * call.  The trained weights reach finrom_mlp_predict / finrom_romml_grad through _get_params and finrom_mlp_create (scale =
+ * gamma / sqrt(var + 1e-3), shift = beta - mean scale, folded by the caller as for any other weights). */
+typedef struct finrom_mlp_train_s* finrom_mlp_train_t;
+typedef struct {
+  int32_t n_in, n_w, n_layers, n_out, max_batch;
+} finrom_mlp_train_desc;
+int finrom_mlp_train_create(const finrom_mlp_train_desc* desc, finrom_mlp_train_t* out);
+void finrom_mlp_train_destroy(finrom_mlp_train_t h);
+int64_t finrom_mlp_train_param_count(finrom_mlp_train_t h);
+int finrom_mlp_train_set_params(finrom_mlp_train_t h, const float* params, const float* m, const float* v, int64_t t);
+int finrom_mlp_train_get_params(finrom_mlp_train_t h, float* params, float* m, float* v, int64_t* t);
+int finrom_mlp_train_set_lr(finrom_mlp_train_t h, double lr, void* stream);
+int finrom_mlp_train_grad(finrom_mlp_train_t h, const float* X, const float* Y, const int32_t* rows, int32_t B, void* stream);
+int finrom_mlp_train_apply(finrom_mlp_train_t h, void* stream);
+int finrom_mlp_train_get_grads(finrom_mlp_train_t h, float* grads, double* loss_mape);
+int finrom_mlp_train_set_grads(finrom_mlp_train_t h, const float* grads, const double* loss_mape, int32_t B);
+int finrom_mlp_train_eval(finrom_mlp_train_t h, const float* X, const float* Y, int64_t S, double* out, void* stream);
+int finrom_mlp_train_epoch_stats(finrom_mlp_train_t h, double* out, int32_t reset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
