@@ -163,6 +163,14 @@ SIGNATURES = {
     "finrom_hmc_end": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p]),
     "finrom_hmc_leapfrog_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_metric_create": (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "finrom_metric_destroy": (None, [C.c_void_p]),
+    "finrom_metric_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_begin_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_void_p]),
+    "finrom_hmc_leapfrog_field_metric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
     "finrom_lbfgs_begin": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_propose": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_accept": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -187,6 +195,7 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 12
+ERR_UNSUPPORTED = -4                      # FINROM_ERR_UNSUPPORTED (include/finrom.h)
 # finrom_fom_last_path codes (include/finrom.h)
 FOM_PATHS = {0: "none", 1: "small_lds", 2: "small_global", 3: "interpreter", 4: "band_registers", 5: "band_lds_4wave",
              7: "band_registers_qoi", 8: "band_lds_4wave_qoi"}

@@ -18,7 +18,12 @@ two priors:
 Chains are independent, so C chains may advance in LOCKSTEP: one device call evaluates the current leapfrog point of every
 chain (a batch of C samples), each chain keeping its own momentum, random stream and accept/reject decision.  On N GPUs a
 rank owns chains `rank, rank + N, ...` (one chain per GPU at N = C) and there is no communication until the traces are
-gathered."""
+gathered.
+
+`metric=LowRankMetric` (laplace.py) on the three chain functions: a constant mass matrix M = I + V diag(lambda) V^T, the
+Gauss-Newton Hessian of the potential at the MAP point (the `scaling` the reference's sampler hands to NUTS, bayesian_inference/
+inference.py:102-140,165).  The random stream is the same: the standard normals xi become momenta p = M^(1/2) xi, the position
+moves by eps M^-1 p and the kinetic energy is p^T M^-1 p / 2 (= |xi|^2 / 2 at the start).  metric=None: every path and bit as before."""
 from __future__ import annotations
 
 import numpy as np
@@ -53,8 +58,17 @@ def _check_prior(prior, mean, who):
         raise ValueError(f"{who}: with a prior the chains start from whitened points and the field's mean is the prior's (mean=None)")
 
 
+def _check_metric(metric, n):
+    """A rank-zero metric is the identity: the plain paths, bit for bit."""
+    if metric is None or metric.rho == 0:
+        return None
+    if metric.n != n:
+        raise ValueError(f"metric: n = {metric.n}, the chains have {n} coordinates")
+    return metric
+
+
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False, prior=None):
+               keep_trace=False, prior=None, metric=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
@@ -63,10 +77,12 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     prior: None (i.i.d. N(mean, tau^2) per node; mean None: the start points) or a GaussianFieldPrior: then K0 holds WHITENED
     start points v (prior.whiten of a field), mean must be None (the prior carries it) and tau is unused; value_and_grad still
     receives fields, and `recorded` still holds (field, loss, field gradient).
+    metric: None (identity mass) or a LowRankMetric in the chain's own coordinates (with a prior: the whitened ones).
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
     trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
     with a prior also V [C, n], the whitened final states)."""
     _check_prior(prior, mean, "run_chains")
+    metric = _check_metric(metric, np.shape(K0)[-1])
     K = np.array(K0, dtype=np.float64, copy=True)
     C, n = K.shape
     if prior is None:
@@ -102,14 +118,16 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     proposals = 0
     while evals + n_leapfrog <= n_evals:
         P = np.stack([r.standard_normal(n) for r in rngs])
-        H0 = U + 0.5 * np.einsum("cn,cn->c", P, P)
+        H0 = U + 0.5 * np.einsum("cn,cn->c", P, P)                  # (under a metric: |xi|^2 / 2 = p^T M^-1 p / 2)
+        if metric is not None:
+            P = metric.apply(P, "sqrt")
         Kq, Pq, Uq, dUq = K.copy(), P.copy(), U, dU
         for _ in range(n_leapfrog):                                  # each step's input depends on the previous gradient
             Pq = Pq - 0.5 * eps * dUq
-            Kq = Kq + eps * Pq
+            Kq = Kq + eps * (Pq if metric is None else metric.apply(Pq, "inv"))
             Uq, dUq = evaluate(Kq)
             Pq = Pq - 0.5 * eps * dUq
-        H1 = Uq + 0.5 * np.einsum("cn,cn->c", Pq, Pq)
+        H1 = Uq + 0.5 * np.einsum("cn,cn->c", Pq, Pq if metric is None else metric.apply(Pq, "inv"))
         u = np.array([r.uniform() for r in rngs])
         with np.errstate(over="ignore", invalid="ignore"):
             ok = np.isfinite(H1) & (np.log(u) < H0 - H1)
@@ -134,7 +152,7 @@ def romml_value_and_grad(solver_r):
 
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                     keep_trace=False, graph=True, data=None, block=32, prior=None):
+                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -144,7 +162,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     `run_chains_device(..., fused=False)`.
     prior: a GaussianFieldPrior -- the state is whitened (K0 = v, mean None, tau unused) and a leapfrog step is
     finrom_hmc_leapfrog_field: field kernel, the plain finrom_romml_grad launches at the field, pullback kernel with the momentum
-    update; finrom_hmc_begin / _end unchanged (mean 0, c_pri 1).  The trace is mapped to fields after the run."""
+    update; finrom_hmc_begin / _end unchanged (mean 0, c_pri 1).  The trace is mapped to fields after the run.
+    metric: a LowRankMetric in the whitened coordinates (needs prior=; FINROM_ERR_UNSUPPORTED otherwise, so that fused=None falls
+    back): finrom_hmc_begin_metric, finrom_hmc_leapfrog_field_metric (one launch more per step: the velocity M^-1 p), _end_metric."""
     import ctypes as C
     import torch
     from .. import _ffi
@@ -157,6 +177,10 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     f64 = dict(dtype=torch.float64, device=dev)
     i64 = dict(dtype=torch.int64, device=dev)
     _check_prior(prior, mean, "run_chains_fused")
+    metric = _check_metric(metric, np.shape(K0)[-1])
+    if metric is not None and prior is None:
+        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog step under the i.i.d. "
+                               "prior has no metric form (pass prior=, or fused=False)")
     K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
     Cn, n = K.shape
     if prior is not None:                                            # whitened: N(0, I), c_pri = 1
@@ -164,6 +188,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         fs = prior.device()
         fmean = torch.as_tensor(prior.mean, **f64)
         F, grad_f = torch.zeros_like(K), torch.zeros_like(K)         # the step's field and misfit gradient
+        if metric is not None:
+            mh, vel = metric.device(), torch.zeros_like(K)           # the step's velocity M^-1 p
     else:
         mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (Cn, n)).copy(), **f64)
     data_np = np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64)
@@ -194,6 +220,13 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         return torch.cuda.current_stream().cuda_stream
 
     def leap(state, step, want_grad=False):
+        if metric is not None:
+            _ffi.check(L.finrom_hmc_leapfrog_field_metric(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(),
+                                                          grad_f.data_ptr(), C.byref(state), step, data_t.data_ptr(), per_sample,
+                                                          None, None, mh._h, vel.data_ptr(), stream()),
+                       "finrom_hmc_leapfrog_field_metric")
+            Sop.used_on(stream())
+            return
         if prior is not None:
             _ffi.check(L.finrom_hmc_leapfrog_field(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
                                                    C.byref(state), step, data_t.data_ptr(), per_sample, None, None, stream()),
@@ -216,12 +249,18 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         evals += 1
 
     def proposal(rec=False):
-        _ffi.check(L.finrom_hmc_begin(C.byref(st), stream()), "finrom_hmc_begin")
+        if metric is not None:
+            _ffi.check(L.finrom_hmc_begin_metric(C.byref(st), mh._h, stream()), "finrom_hmc_begin_metric")
+        else:
+            _ffi.check(L.finrom_hmc_begin(C.byref(st), stream()), "finrom_hmc_begin")
         for i in range(n_leapfrog):                                  # each step's input depends on the previous gradient
             leap(st, i, want_grad=rec)
             if rec:
                 note(i)
-        _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
+        if metric is not None:
+            _ffi.check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
+        else:
+            _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
 
     # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
     Kq[0].copy_(K)
@@ -287,7 +326,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                      keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None):
+                      keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -305,9 +344,12 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     prior: a GaussianFieldPrior (run_chains: K0 whitened, mean None, tau unused); every evaluation is FieldSampler.field, the
     romml call at the field, FieldSampler.pullback of its gradient (fused: finrom_hmc_leapfrog_field); K and trace are fields, V the
     whitened end states.
+    metric: a LowRankMetric in the chain's own coordinates (run_chains); its maps are finrom_metric_apply launches on the static
+    tensors (engine.MetricHandle), fused: run_chains_fused's kernels (needs prior=).
     Same chains as run_chains(romml_value_and_grad(solver_r), ...) up to the rounding of the elementwise updates.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     import torch
+    metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
         # the trajectory's arithmetic inside the library (round 4); fused=None: fall back to the torch-op form below where the
         # library has no one-sample form for this model (FINROM_ERR_UNSUPPORTED)
@@ -315,7 +357,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior)
+                                    prior=prior, metric=metric)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -334,6 +376,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     rngs = [np.random.default_rng(s) for s in seeds]
     assert len(rngs) == C
     c_lik, c_pri = 1.0 / sigma ** 2, 1.0 / tau ** 2
+    mh = metric.device() if metric is not None else None
     n_prop = max(0, (n_evals - 1) // n_leapfrog)
     B = max(1, min(block, n_prop))
     # static tensors (the graph's operands): state K, U, dU | work Kq, Pq, D, dUq | inputs P_dev, lu_dev | counters
@@ -358,7 +401,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         out["loss"], out["grad"], out["info"], out["field"] = res["loss"], res["grad"], res["info"], Fq
 
     def step():
-        Kq.add_(Pq, alpha=eps)
+        Kq.add_(Pq if mh is None else mh.apply(Pq, "inv"), alpha=eps)
         evaluate()
         Pq.add_(dUq, alpha=-eps * c_pri)                           # two half steps; the ends of a trajectory correct by +- eps/2
 
@@ -383,14 +426,14 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         torch.index_select(lu_dev, 0, jt, out=lu)
         H0 = torch.add(U, torch.linalg.vecdot(P0[0], P0[0]), alpha=0.5)
         Kq.copy_(K); dUq.copy_(dU)
-        torch.add(P0[0], dUq, alpha=-0.5 * eps * c_pri, out=Pq)     # first half step
+        torch.add(P0[0] if mh is None else mh.apply(P0[0], "sqrt"), dUq, alpha=-0.5 * eps * c_pri, out=Pq)     # first half step
         for _ in range(n_leapfrog):                                 # each step's input depends on the previous gradient
             step()
             if hook is not None:
                 hook()
         Pq.add_(dUq, alpha=0.5 * eps * c_pri)                       # the last update was a whole step: back to a half
         Uq = potential_now()
-        H1 = torch.add(Uq, torch.linalg.vecdot(Pq, Pq), alpha=0.5)
+        H1 = torch.add(Uq, torch.linalg.vecdot(Pq, Pq) if mh is None else mh.apply(Pq, "inv", want_quad=True)[1], alpha=0.5)
         ok = lu[0] < H0 - H1                                        # (H1 = inf or nan compares false, as on the host: rejected)
         torch.where(ok[:, None], Kq, K, out=K); torch.where(ok, Uq, U, out=U); torch.where(ok[:, None], dUq, dU, out=dU)
         acc.add_(ok)

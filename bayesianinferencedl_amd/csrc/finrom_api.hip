@@ -218,6 +218,7 @@ struct finrom_sampler_s {
   double* U = nullptr; int n = 0; Scratch xi;
   Scratch fpart, ftick;                // finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field: partial sums, arrival counters
 };
+struct finrom_metric_s { MetricDev d{}; };
 struct finrom_mlp_s {
   MlpDev d{}; std::vector<void*> owned; Scratch tape, theta, gth, shift, qtmp, etmp, g0, y0p, thp;
   // finrom_hmc_leapfrog: the partial sums of theta the last step left in thp, and the field they belong to (position buffer,
@@ -1937,10 +1938,11 @@ int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, c
 
 // the leapfrog step in whitened coordinates: field kernel (position update in front), the plain romml value and gradient at the
 // field, pullback kernel (momentum update behind); no theta carry (the field is not the position)
-int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior, const double* field_mean,
-                              double* field, double* grad_field, const finrom_hmc_state* a, int32_t step, const double* data,
-                              int32_t data_per_sample, double* qoi_r, double* e_nn, void* stream) {
-  CallGuard cg((hipStream_t)stream);
+// (metric: the position moves along vel = M^-1 p, formed first -- finrom_hmc_leapfrog_field_metric; nullptr: along p itself)
+static int hmc_leapfrog_field_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior, const double* field_mean,
+                                   double* field, double* grad_field, const finrom_hmc_state* a, int32_t step, const double* data,
+                                   int32_t data_per_sample, double* qoi_r, double* e_nn, const MetricDev* metric, double* vel,
+                                   void* stream) {
   HmcDev h;
   if (int rc = hmc_dev(a, &h, "hmc_leapfrog_field")) return rc;
   if (a->c_pri != 1.0) { set_error("hmc_leapfrog_field: c_pri must be 1 (whitened coordinates: the prior of v is N(0, I))"); return FINROM_ERR_ARG; }
@@ -1957,14 +1959,109 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
   hipStream_t st = (hipStream_t)stream;
   if (int rc = field_prior_ws(prior, a->C)) return rc;
   double* vq = a->Kq[(step + 1) & 1];
-  int rc = launch_field_prior(prior->U, prior->n, 0, a->Kq[step & 1], a->P, a->eps, field_mean, field, vq, nullptr, a->C,
-                              (double*)prior->fpart.p, (int*)prior->ftick.p, st);
+  int rc = metric ? launch_hmc_velocity(*metric, a->P, a->C, vel, st) : 0;
+  if (!rc) rc = launch_field_prior(prior->U, prior->n, 0, a->Kq[step & 1], metric ? vel : a->P, a->eps, field_mean, field, vq, nullptr,
+                                   a->C, (double*)prior->fpart.p, (int*)prior->ftick.p, st);
   if (!rc) rc = romml_grad_impl(rom, mlp, Sop, field, data, data_per_sample, a->C, grad_field, a->loss, qoi_r, e_nn, a->info, stream, nullptr);
   if (rc) return rc;
   FieldPriorTail tl;
   tl.vq = vq; tl.c_lik = a->c_lik; tl.info = a->info; tl.mom = a->P; tl.dU = a->dUq; tl.eps = a->eps;
   return launch_field_prior(prior->U, prior->n, 1, grad_field, nullptr, 0.0, nullptr, nullptr, nullptr, &tl, a->C,
                             (double*)prior->fpart.p, (int*)prior->ftick.p, st);
+}
+int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior, const double* field_mean,
+                              double* field, double* grad_field, const finrom_hmc_state* a, int32_t step, const double* data,
+                              int32_t data_per_sample, double* qoi_r, double* e_nn, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  return hmc_leapfrog_field_impl(rom, mlp, Sop, prior, field_mean, field, grad_field, a, step, data, data_per_sample, qoi_r, e_nn,
+                                 nullptr, nullptr, stream);
+}
+
+// ---- low-rank metric (hmc_metric.hip) --------------------------------------------------------------------------------------------
+int finrom_metric_create(const double* Vt, const double* lam, int32_t n, int32_t rho, finrom_metric_t* out) {
+  if (!out) { set_error("metric_create: null out"); return FINROM_ERR_ARG; }
+  *out = nullptr;
+  if (!Vt || !lam || n <= 0) { set_error("metric_create: null Vt or lam, or n <= 0"); return FINROM_ERR_ARG; }
+  if (rho < 1 || rho > METRIC_MAX_RHO) {
+    set_error("metric_create: rho = " + std::to_string(rho) + " (need 1 <= rho <= 64)"); return FINROM_ERR_ARG;
+  }
+  for (int j = 0; j < rho; ++j)
+    if (!std::isfinite(lam[j]) || !(lam[j] > 0.0)) {
+      set_error("metric_create: lambda[" + std::to_string(j) + "] = " + std::to_string(lam[j]) + " (need finite and > 0)"); return FINROM_ERR_ARG;
+    }
+  double worst = 0.0;
+  for (int i = 0; i < rho; ++i)
+    for (int j = 0; j <= i; ++j) {
+      long double s = 0.0L;
+      for (int q = 0; q < n; ++q) s += (long double)Vt[(size_t)i * n + q] * Vt[(size_t)j * n + q];
+      const double e = std::fabs((double)(s - (i == j ? 1.0L : 0.0L)));
+      if (!(e <= worst)) worst = e;                      // (a NaN sticks)
+    }
+  if (!(worst <= 1e-10)) {
+    set_error("metric_create: the rows of Vt are not orthonormal (|Vt Vt^T - I|_max = " + std::to_string(worst) + " > 1e-10)"); return FINROM_ERR_ARG;
+  }
+  std::vector<double> coef((size_t)METRIC_NUM_COEF * METRIC_MAX_RHO, 0.0);
+  for (int j = 0; j < rho; ++j) {                        // (forms without cancellation at small lambda)
+    const double l = lam[j], s = std::sqrt(1.0 + l);
+    coef[(size_t)METRIC_OP_M * METRIC_MAX_RHO + j] = l;
+    coef[(size_t)METRIC_OP_INV * METRIC_MAX_RHO + j] = -l / (1.0 + l);
+    coef[(size_t)METRIC_OP_SQRT * METRIC_MAX_RHO + j] = l / (s + 1.0);
+    coef[(size_t)METRIC_OP_INVSQRT * METRIC_MAX_RHO + j] = -l / ((1.0 + l) + s);
+    coef[(size_t)METRIC_OP_D * METRIC_MAX_RHO + j] = l / (1.0 + l);
+  }
+  auto* h = new finrom_metric_s();
+  h->d.n = n; h->d.rho = rho;
+  double* dv = nullptr; double* dc = nullptr;
+  int rc = upload(&dv, Vt, (size_t)rho * n);
+  if (!rc) rc = upload(&dc, coef.data(), coef.size());
+  h->d.Vt = dv; h->d.coef = dc;
+  if (rc) { finrom_metric_destroy(h); return rc; }
+  *out = h;
+  return 0;
+}
+void finrom_metric_destroy(finrom_metric_t h) { if (!h) return; dev_free((void*)h->d.Vt); dev_free((void*)h->d.coef); delete h; }
+int finrom_metric_apply(finrom_metric_t h, int32_t op, const double* x, int64_t S, double* y, double* quad, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (!h || S < 0 || (S > 0 && (!x || !y))) { set_error("metric_apply: bad argument (null handle, x or y, or S < 0)"); return FINROM_ERR_ARG; }
+  if (op < FINROM_METRIC_M || op > FINROM_METRIC_INVSQRT) { set_error("metric_apply: op = " + std::to_string(op) + " (need 0 .. 3)"); return FINROM_ERR_ARG; }
+  if (S > 0 && x == y) { set_error("metric_apply: y must not be x"); return FINROM_ERR_ARG; }
+  if (S == 0) return 0;
+  return launch_metric_apply(h->d, op, x, S, y, quad, (hipStream_t)stream);
+}
+static int hmc_metric_check(const finrom_hmc_state* a, finrom_metric_t m, const char* who) {
+  if (!m) { set_error(std::string(who) + ": null metric handle"); return FINROM_ERR_ARG; }
+  if (a->n != m->d.n) {
+    set_error(std::string(who) + ": n = " + std::to_string(a->n) + " is not the metric's (" + std::to_string(m->d.n) + ")"); return FINROM_ERR_ARG;
+  }
+  return 0;
+}
+int finrom_hmc_begin_metric(const finrom_hmc_state* a, finrom_metric_t metric, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_begin_metric")) return rc;
+  if (int rc = hmc_metric_check(a, metric, "hmc_begin_metric")) return rc;
+  return launch_hmc_begin_metric(h, metric->d, (hipStream_t)stream);
+}
+int finrom_hmc_end_metric(const finrom_hmc_state* a, finrom_metric_t metric, int32_t n_steps, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_end_metric")) return rc;
+  if (int rc = hmc_metric_check(a, metric, "hmc_end_metric")) return rc;
+  if (n_steps < 0) { set_error("hmc_end_metric: n_steps < 0"); return FINROM_ERR_ARG; }
+  return launch_hmc_end_metric(h, metric->d, a->Kq[n_steps & 1], (hipStream_t)stream);
+}
+int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior,
+                                     const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* a,
+                                     int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
+                                     finrom_metric_t metric, double* vel, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (!a || !metric || !vel) { set_error("hmc_leapfrog_field_metric: null state, metric handle or vel"); return FINROM_ERR_ARG; }
+  if (a->n != metric->d.n) {
+    set_error("hmc_leapfrog_field_metric: n = " + std::to_string(a->n) + " is not the metric's (" + std::to_string(metric->d.n) + ")");
+    return FINROM_ERR_ARG;
+  }
+  return hmc_leapfrog_field_impl(rom, mlp, Sop, prior, field_mean, field, grad_field, a, step, data, data_per_sample, qoi_r, e_nn,
+                                 &metric->d, vel, stream);
 }
 
 // multi-start L-BFGS (lbfgs_kernels.hip): every check on the host, before the stream is looked at

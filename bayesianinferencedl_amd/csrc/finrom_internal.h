@@ -74,6 +74,21 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
 
+// ---- low-rank metric M = I + V diag(lambda) V^T (hmc_metric.hip, finrom_metric_*, finrom_hmc_*_metric) -----------------------
+constexpr int METRIC_MAX_RHO = 64;
+// rows of MetricDev::coef: the c_j of y = x + sum_j c_j V_j (V_j . x) for the four maps (finrom.h's FINROM_METRIC_* codes), then
+// d_j = lambda_j / (1 + lambda_j) of the kinetic energy
+enum { METRIC_OP_M = 0, METRIC_OP_INV = 1, METRIC_OP_SQRT = 2, METRIC_OP_INVSQRT = 3, METRIC_OP_D = 4, METRIC_NUM_COEF = 5 };
+struct MetricDev {
+  int n = 0, rho = 0;
+  const double* Vt = nullptr;            // [rho x n] orthonormal rows
+  const double* coef = nullptr;          // [METRIC_NUM_COEF x METRIC_MAX_RHO]
+};
+int launch_metric_apply(const MetricDev& m, int op, const double* x, int64_t S, double* y, double* quad, hipStream_t st);
+int launch_hmc_velocity(const MetricDev& m, const double* P, int64_t C, double* Q, hipStream_t st);
+int launch_hmc_begin_metric(const HmcDev& h, const MetricDev& m, hipStream_t st);
+int launch_hmc_end_metric(const HmcDev& h, const MetricDev& m, const double* Kq, hipStream_t st);
+
 // ---- batched multi-start L-BFGS bookkeeping (lbfgs_kernels.hip, finrom_lbfgs_*) ------------------------------------------
 struct LbfgsDev {                // finrom_lbfgs_state, validated
   int64_t S; int d, m, maxls, gdim;

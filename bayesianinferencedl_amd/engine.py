@@ -559,6 +559,44 @@ class FieldSampler:
             pass
 
 
+class MetricHandle:
+    """The low-rank metric M = I + V diag(lam) V^T on the device (finrom_metric_*): Vt [rho, n] orthonormal rows, lam [rho] > 0,
+    1 <= rho <= 64.  apply(x, op): y = x + sum_j c_j V_j (V_j . x) row-wise for op in 'M', 'inv', 'sqrt', 'invsqrt'.  NumPy in ->
+    NumPy out; a float64 CUDA tensor in -> a tensor on its device, launched on torch's current stream."""
+    OPS = {"M": 0, "inv": 1, "sqrt": 2, "invsqrt": 3}
+
+    def __init__(self, Vt, lam):
+        Vt = np.ascontiguousarray(Vt, dtype=np.float64)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if Vt.ndim != 2 or lam.shape != (Vt.shape[0],):
+            raise ValueError("MetricHandle: Vt [rho, n] and lam [rho]")
+        self.rho, self.n = Vt.shape
+        h = C.c_void_p()
+        check(lib().finrom_metric_create(Vt.ctypes.data_as(_ffi.c_f64p), lam.ctypes.data_as(_ffi.c_f64p), self.n, self.rho, C.byref(h)),
+              "finrom_metric_create")
+        self._h = h
+
+    def apply(self, x, op="M", want_quad=False):
+        """y [S, n] (and quad [S] = x . y row-wise if want_quad)."""
+        b = _Batch(x, self.n)
+        y, yp = b.new((b.S, self.n), zero=False)
+        q, qp = b.new((b.S,), zero=False) if want_quad else (None, None)
+        check(lib().finrom_metric_apply(self._h, self.OPS[op], b.ptr, b.S, yp, qp, b.stream), "finrom_metric_apply")
+        out = b.out(y, (b.S, self.n))
+        return (out, b.out(q, (b.S,))) if want_quad else out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _ffi.destroy_handle("finrom_metric_destroy", self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceErrorModel:
     """The learned error model on the device (finrom_mlp_*): the weights of a deep_learning/dl_model.py::ResBnFcModel (the
     stand-in for the reference's Keras res_bn_fc_model, dl_model.py:149-176), batch normalisation folded into scale / shift in

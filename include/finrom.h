@@ -430,6 +430,40 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
                               int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
                               void* stream);
 
+/* ---- Laplace-preconditioned HMC: a low-rank metric at the MAP point ------------------------------------------------------------- *
+ * The reference's working sampler builds a low-rank Gauss-Newton Hessian of the misfit at the MAP point in prior-whitened
+ * coordinates and hands it to NUTS as `scaling` (bayesian_inference/inference.py:102-140,165).  Here that is a handle holding
+ *   M = I + V diag(lambda) V^T,   V [n x rho] orthonormal columns, lambda_j > 0, 1 <= rho <= 64,
+ * the Gauss-Newton Hessian of the whitened potential misfit / sigma^2 + |v|^2 / 2 (1 / sigma^2 INCLUDED in lambda; the reference's
+ * H-tilde leaves it out).  Every map is y = x + sum_j c_j V_j (V_j . x), row-wise, sums in a fixed order (a row's bits depend on
+ * that row alone):
+ *   FINROM_METRIC_M        c = lambda                       FINROM_METRIC_INV      c = -lambda / (1 + lambda)
+ *   FINROM_METRIC_SQRT     c = sqrt(1 + lambda) - 1         FINROM_METRIC_INVSQRT  c = 1 / sqrt(1 + lambda) - 1
+ * finrom_metric_create  Vt [rho x n] row-major (the eigenvectors as ROWS) and lam [rho] are HOST arrays, copied; refuses rho outside
+ *                       1 .. 64, a lambda that is not finite and > 0, and |Vt Vt^T - I|_max > 1e-10 (FINROM_ERR_ARG, with a message).
+ * finrom_metric_apply   x, y [S x n] device (y != x), quad [S] device or NULL: quad[s] = x_s . y_s.  One launch, no workspace.
+ * finrom_metric_destroy queued while a stream capture is open, like every handle's.
+ * Chains under the metric (hmc.py metric=, whitened coordinates under the latent Gaussian-field prior): momenta p ~ N(0, M),
+ * kinetic energy p^T M^-1 p / 2, position update eps M^-1 p.
+ *   finrom_hmc_begin_metric           finrom_hmc_begin with P_block holding STANDARD normals xi (the same random stream):
+ *                                     p = M^(1/2) xi, H0 = U + |xi|^2 / 2 (= U + p^T M^-1 p / 2);
+ *   finrom_hmc_leapfrog_field_metric  vel [C x n] (caller's buffer) = M^-1 p, then finrom_hmc_leapfrog_field with vel in the place
+ *                                     of p in the position update; gradient, pullback and momentum update (of p) unchanged: one
+ *                                     launch more per step, no fork;
+ *   finrom_hmc_end_metric             finrom_hmc_end with kinetic energy (|p|^2 - sum_j d_j (V_j . p)^2) / 2, d = lambda / (1 + lambda).
+ * None of them allocates: they may be captured once the plain step has run with the same C. */
+typedef struct finrom_metric_s* finrom_metric_t;
+enum { FINROM_METRIC_M = 0, FINROM_METRIC_INV = 1, FINROM_METRIC_SQRT = 2, FINROM_METRIC_INVSQRT = 3 };
+int finrom_metric_create(const double* Vt, const double* lam, int32_t n, int32_t rho, finrom_metric_t* out);
+void finrom_metric_destroy(finrom_metric_t h);
+int finrom_metric_apply(finrom_metric_t h, int32_t op, const double* x, int64_t S, double* y, double* quad, void* stream);
+int finrom_hmc_begin_metric(const finrom_hmc_state* st, finrom_metric_t metric, void* stream);
+int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior,
+                                     const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* st,
+                                     int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
+                                     finrom_metric_t metric, double* vel, void* stream);
+int finrom_hmc_end_metric(const finrom_hmc_state* st, finrom_metric_t metric, int32_t n_steps, void* stream);
+
 /* ---- batched multi-start MAP estimation: a projected L-BFGS on the device ------------------------------------------------------- *
  * The reference minimises 0.5 |y(k) - d|^2 + reg(k) with SciPy's L-BFGS-B, one start after another (bayesian_inference/
  * estimate_MAP.py:246-281).  Here S starts advance in lockstep on device-resident state, and a ROUND is three pieces in stream
