@@ -1808,10 +1808,18 @@ void finrom_mlp_destroy(finrom_mlp_t h) {
 int finrom_mlp_predict(finrom_mlp_t h, const double* k, int64_t S, double* e, void* stream) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!k || !e))) { set_error("mlp_predict: bad argument"); return FINROM_ERR_ARG; }
+  if (int fits = mlp_forward_fits(h->d)) return fits;      // (before any device call)
   int rc = h->tape.reserve((size_t)S * (h->d.n_layers + 1) * h->d.n_w * sizeof(float));
   if (rc) return rc;
   return launch_mlp_forward(h->d, k, S, nullptr, 0, (float*)h->tape.p, e, nullptr, (hipStream_t)stream);
 }
+int32_t finrom_mlp_stage_reach(int32_t n_layers, int32_t n_w, int32_t n_out, int32_t* staged, int32_t* stage_floats) {
+  if (n_layers < 0 || n_layers > 64 || n_w <= 0 || n_w > 64 || n_out <= 0 || n_out > 64) { set_error("mlp_stage_reach: sizes outside finrom_mlp_create's"); return FINROM_ERR_ARG; }
+  if (staged) *staged = mlp_tail_staged(n_layers, n_w, n_out) ? 1 : 0;
+  if (stage_floats) *stage_floats = MLP_STAGE_FLOATS;
+  return mlp_stage_reach(n_layers, n_w, n_out);
+}
+int32_t finrom_mlp_forward_max_in(void) { return MLP_FORWARD_MAX_IN; }
 // (hs: the call is a leapfrog step -- finrom_hmc_leapfrog: position update in front, momentum update behind; one-sample form only)
 struct HmcStep { const double* mom; double eps; double* k_out; HmcTail tail; const double* theta_parts_in; };
 static int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,

@@ -34,6 +34,26 @@ struct MlpFuse {
   // phase at the head of every contraction workgroup becomes one load of 8 x P doubles
   const double* theta_parts = nullptr;
 };
+// The one-sample form's spare wave (mlp_forward_tail_wave<true>, mlp_device.h) reads the hidden layers' and the head's weights from
+// MLP_STAGE_FLOATS floats of LDS -- the weights, zeros behind them -- and ALL 64 lanes run every layer's loop over 64 inputs
+// unguarded: lane t reads [l n_w^2 + t + i n_w] for i < 64 in hidden layer l and [L n_w^2 + t + i n_out] in the head.
+// mlp_stage_reach: one past the furthest of those indices.  The staged wave is taken only where that lies inside the zero-filled
+// region (the weights' own count, L n_w^2 + n_w n_out, is never larger): e.g. 12 layers of 36 units are 15 876 floats of weights
+// but lane 63 of layer 11 reads index 16 587 -- past the staged floats and past the kernel's LDS -- so they take the unstaged wave.
+constexpr int MLP_STAGE_FLOATS = 16 * 256 * 4;      // what 256 threads stage with 16 four-float loads each: 64 KB (5 x 50 x 50 + 50 x 9 = 12 950 floats fit)
+__host__ __device__ inline int mlp_stage_reach(int n_layers, int n_w, int n_out) {
+  const int nh = n_layers * n_w * n_w;
+  const int hid = n_layers > 0 ? nh - n_w * n_w + 63 * n_w + 63 : -1, head = nh + 63 * n_out + 63;
+  return (hid > head ? hid : head) + 1;
+}
+__host__ __device__ inline bool mlp_tail_staged(int n_layers, int n_w, int n_out) {      // (& 3: the hidden weights are staged as four-float loads)
+  return mlp_stage_reach(n_layers, n_w, n_out) <= MLP_STAGE_FLOATS && ((n_layers * n_w * n_w) & 3) == 0;
+}
+// mlp_forward_kernel keeps its input in dynamic LDS beside mlp_forward_body<1024>'s static arrays (part [16][64] + y, a [64] floats,
+// tred [16] doubles = 4736 bytes) under the 64 KB a kernel may use without asking for more: inputs beyond this are refused by
+// launch_mlp_forward (FINROM_ERR_UNSUPPORTED), not left to fail at launch.  The largest mesh with a band plan (m = 28) has 7 757 nodes.
+constexpr int MLP_FORWARD_STATIC_LDS = (16 * 64 + 2 * 64) * 4 + 16 * 8;
+constexpr int MLP_FORWARD_MAX_IN = (64 * 1024 - MLP_FORWARD_STATIC_LDS) / 4;      // 15 200
 constexpr int HMC_THETA_PARTS = 8;      // = mlp_kernels.hip's MLP_SPLIT: one partial sum per workgroup of the backward kernel
 constexpr int HMC_THETA_MAXP = 10;      // averages the carry handles (the fin has nine); beyond: every step forms theta itself
 // finrom_hmc_leapfrog: the momentum update rides behind the gradient (mlp_backward_kernel's epilogue):
@@ -49,6 +69,7 @@ struct HmcTail {
 int launch_mlp_forward(const MlpDev& m, const double* k, int64_t S, const double* data, int64_t data_stride, float* tape,
                        double* e_out, double* data_shift, hipStream_t st, const double* Sop = nullptr, int P = 0,
                        double* theta_out = nullptr);
+int mlp_forward_fits(const MlpDev& m);      // 0, or FINROM_ERR_UNSUPPORTED with the error text set (n_in > MLP_FORWARD_MAX_IN)
 // (g_parts, n_parts: instead of g_theta, its n_parts partial sums [S x n_parts x 32] as rom_grad_contract_small_kernel leaves them)
 int launch_mlp_backward(const MlpDev& m, int64_t S, const float* tape, const double* data, int64_t data_stride, const double* qoi_r,
                         const double* e_nn, const double* g_theta, const double* Sop, int P, double* grad, hipStream_t st,

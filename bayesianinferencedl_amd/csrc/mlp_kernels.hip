@@ -142,10 +142,17 @@ __global__ __launch_bounds__(MLP_THREADS) void mlp_backward_kernel(MlpDev m, int
   }
 }
 
+int mlp_forward_fits(const MlpDev& m) {                // (the input lives in the workgroup's LDS: finrom_internal.h)
+  if (m.n_in <= MLP_FORWARD_MAX_IN) return 0;
+  set_error("mlp_forward: n_in = " + std::to_string(m.n_in) + " exceeds " + std::to_string(MLP_FORWARD_MAX_IN) + " (the input is kept in LDS)");
+  return FINROM_ERR_UNSUPPORTED;
+}
+
 int launch_mlp_forward(const MlpDev& m, const double* k, int64_t S, const double* data, int64_t data_stride, float* tape,
                        double* e_out, double* data_shift, hipStream_t st, const double* Sop, int P, double* theta_out) {
   if (S == 0) return 0;
   if (theta_out != nullptr && (P < 1 || P > 16)) { set_error("mlp_forward: at most 16 sub-fin averages"); return FINROM_ERR_UNSUPPORTED; }
+  if (int rc = mlp_forward_fits(m)) return rc;
   ScopedKernelTimer t(K_MISC, st);
   hipLaunchKernelGGL(mlp_forward_kernel, dim3((unsigned)S), dim3(MLP_THREADS), (size_t)m.n_in * sizeof(float), st, m, k, S, data, data_stride,
                      tape, e_out, data_shift, Sop, P, theta_out);

@@ -154,7 +154,6 @@ __global__ __launch_bounds__(256, 1) void rom_small_proj_kernel(RomDev p, const 
 typedef double v4d __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4d mma(double a, double b, v4d cacc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, cacc, 0, 0, 0); }
 
-constexpr int MLP_STAGE_FLOATS = 16 * 256 * 4;      // what 256 threads stage with 16 four-float loads each: 64 KB (5 x 50 x 50 + 50 x 9 = 12 950 floats fit)
 template <int NB> constexpr int small_solve_lds(bool mlp = false) { return onesample_nt<NB>() * 256 + 2 * NB * 256 + 16 * NB + 32 + 32 + 32 + 64 + 2 + (mlp ? MLP_STAGE_FLOATS / 2 : 0); }
 
 template <int NB>
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(320, 1) void rom_small_solve_kernel(RomDev p, const
     // waits for the four arrivals on an LDS counter (the hardware barrier would tie the others to it; the counter is zeroed behind
     // a barrier at the kernel's first instruction, when nobody has anything to wait for)
     const int n_stage = fm.on ? fm.m.n_layers * fm.m.n_w * fm.m.n_w + fm.m.n_w * fm.m.n_out : 0;
-    const bool staged = fm.on && n_stage <= MLP_STAGE_FLOATS && ((fm.m.n_layers * fm.m.n_w * fm.m.n_w) & 3) == 0;
+    const bool staged = fm.on && mlp_tail_staged(fm.m.n_layers, fm.m.n_w, fm.m.n_out);      // (finrom_internal.h: what the unguarded loops reach)
     if (fm.on) {
       if (threadIdx.x == 0) *mlp_flag = 0;
       __syncthreads();

@@ -602,17 +602,24 @@ class DeviceErrorModel:
     stand-in for the reference's Keras res_bn_fc_model, dl_model.py:149-176), batch normalisation folded into scale / shift in
     fp32 exactly as the host model does."""
 
-    def __init__(self, model):
+    @staticmethod
+    def fold(model):
+        """The fp32 arrays of finrom_mlp_desc for a ResBnFcModel: scale = gamma / sqrt(var + eps) and shift = beta - mean scale
+        formed in fp32 (what the device evaluates; tests/mlp_cases.py widens these same arrays for its float64 reference)."""
         from .deep_learning.dl_model import BN_EPS
         layers = list(model.units) + [model.head]
         f32 = lambda a_: np.ascontiguousarray(a_, dtype=np.float32)
         scale = np.stack([u["gamma"] / np.sqrt(u["var"] + np.float32(BN_EPS)) for u in layers]).astype(np.float32)
         shift = np.stack([u["beta"] - u["mean"] * s_ for u, s_ in zip(layers, scale)]).astype(np.float32)
         L, nw = len(model.units), model.n_weights
-        arrs = {"W0": f32(model.W0), "b0": f32(model.b0), "scale": f32(scale), "shift": f32(shift),
+        return {"W0": f32(model.W0), "b0": f32(model.b0), "scale": f32(scale), "shift": f32(shift),
                 "W": f32(np.stack([u["W"] for u in model.units]) if L else np.zeros((0, nw, nw))),
                 "b": f32(np.stack([u["b"] for u in model.units]) if L else np.zeros((0, nw))),
                 "Wh": f32(model.head["W"]), "bh": f32(model.head["b"])}
+
+    def __init__(self, model):
+        arrs = self.fold(model)
+        L, nw = len(model.units), model.n_weights
         self.n_in, self.n_out = model.n_in, model.n_out
         d = MlpDesc(n_in=model.n_in, n_w=nw, n_layers=L, n_out=model.n_out,
                     **{k: v.ctypes.data_as(_ffi.c_f32p) for k, v in arrs.items()})

@@ -379,6 +379,14 @@ typedef struct {
 int finrom_mlp_create(const finrom_mlp_desc* desc, finrom_mlp_t* out);
 void finrom_mlp_destroy(finrom_mlp_t h);
 int finrom_mlp_predict(finrom_mlp_t h, const double* k, int64_t S, double* e, void* stream);
+/* Two limits of the device code, for callers and tests (host arithmetic, no device call).  finrom_mlp_stage_reach: the one-sample
+ * form of finrom_romml_grad keeps the hidden and head weights in *stage_floats floats of LDS when the returned value -- one past
+ * the furthest index its unguarded loops read -- does not exceed that count and n_layers n_w^2 is a multiple of 4 (*staged = 1);
+ * other shapes read the weights from memory (*staged = 0).  Either pointer may be NULL; sizes outside finrom_mlp_create's give
+ * FINROM_ERR_ARG.  finrom_mlp_forward_max_in: the largest n_in finrom_mlp_predict and the batched form of finrom_romml_grad take
+ * (the input is kept in LDS); beyond it they return FINROM_ERR_UNSUPPORTED before any launch. */
+int32_t finrom_mlp_stage_reach(int32_t n_layers, int32_t n_w, int32_t n_out, int32_t* staged, int32_t* stage_floats);
+int32_t finrom_mlp_forward_max_in(void);
 int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,
                       int32_t data_per_sample, int64_t S, double* grad, double* loss, double* qoi_r, double* e_nn,
                       int32_t* info, void* stream);
