@@ -42,22 +42,37 @@ class Segment:
         self.g0, self.e0, self.npiv, self.ntot, self.NS, self.L0 = g0, e0, npiv, ntot, NS, L0
 
 
+def mirror_permutation(mesh):
+    """P[v] = the node that mirrors node v about the fin's symmetry line x = 3 (lattice column 3 m)."""
+    xe = 6 * mesh.m
+    li, lj = mesh.lattice[:, 0], mesh.lattice[:, 1]
+    node_at = {(int(i), int(j)): k for k, (i, j) in enumerate(zip(li, lj))}
+    return np.asarray([node_at[(xe - int(i), int(j))] for i, j in zip(li, lj)], np.int64)
+
+
 class BandPlan:
-    def __init__(self, mesh, indptr, indices, nonzero):
+    def __init__(self, mesh, indptr, indices, nonzero, mirror=False):
         """mesh: fem.FinMesh; (indptr, indices): shared CSR pattern of A; nonzero[e]: entry e of the pattern can be non-zero
-        (False = zero in every operator table: the hypotenuse entries of the right-triangle lattice)."""
+        (False = zero in every operator table: the hypotenuse entries of the right-triangle lattice).
+        mirror: the plan of the HALF problem of a mirror-symmetric operator (same conductivity left and right of x = 3): the
+        nodes with lattice column i <= 3 m, i.e. the four left fins and the left half of the post up to and including the
+        symmetry line, which carries a natural boundary condition.  With E the map half dofs -> mesh dofs (a left node to
+        itself and its mirror image, a centre-line node to itself) the half operator is 1/2 E^T A E: entries among left nodes
+        and between a left and a centre-line node are A's own, entries among centre-line nodes are halved (`ab_scale`), and so
+        is the centre-line load (`rhs_scale`).  `n` is then the number of half nodes and `perm` maps onto mesh dofs."""
         m = mesh.m
-        self.m, self.n = m, mesh.n
-        n = mesh.n
+        self.m, self.mirror, self.n_mesh = m, bool(mirror), mesh.n
         q, x0, x1, xe, ytop = m // 4, 5 * m // 2, 7 * m // 2, 6 * m, 4 * m
-        self.q, self.W = q, m + 1
-        self.NSF, self.NSP = q + 2, m + 2                # window slots = half bandwidth + 1
+        if mirror:
+            x1 = 3 * m                                    # the post ends at the symmetry line
+        self.q, self.W = q, x1 - x0 + 1
+        self.NSF, self.NSP = q + 2, self.W + 1            # window slots = half bandwidth + 1
         li, lj = mesh.lattice[:, 0], mesh.lattice[:, 1]
         node_at = {(int(i), int(j)): k for k, (i, j) in enumerate(zip(li, lj))}
 
         # ---- band order ---------------------------------------------------------------------------------------------
         fins = []                                         # (own nodes in elimination order, interface nodes bottom -> top)
-        for side, ybs in ((0, _LEFT_YB), (1, _RIGHT_YB)):
+        for side, ybs in ((0, _LEFT_YB),) if mirror else ((0, _LEFT_YB), (1, _RIGHT_YB)):
             for yb in ybs:
                 j0 = int(round(yb * m))
                 cols = range(0, x0) if side == 0 else range(xe, x1, -1)
@@ -69,10 +84,12 @@ class BandPlan:
         self.npf = len(fins[0][0])
         self.npost = len(post)
         order = [v for own, _ in fins for v in own] + post
-        if len(order) != n or len(set(order)) != n:
+        n = int(np.count_nonzero(li <= x1)) if mirror else mesh.n
+        self.n = n
+        if len(order) != n or len(set(order)) != n or (mirror and any(li[v] > x1 for v in order)):
             raise BandPlanError("band order does not cover the mesh")
         self.perm = np.asarray(order, np.int64)           # elimination index -> dof
-        self.iperm = np.empty(n, np.int64); self.iperm[self.perm] = np.arange(n)
+        self.iperm = np.full(mesh.n, -1, np.int64); self.iperm[self.perm] = np.arange(n)   # (-1: not a node of the half plan)
 
         # ---- segments and the global numbering of segment nodes (fins carry their interface nodes as trailing nodes) --
         segs, gnode = [], []                              # gnode[g] = dof of segment node g
@@ -89,7 +106,7 @@ class BandPlan:
         self.nL = L0                                      # doubles of regular L per sample (B off-diagonals + 1/L_jj per pivot)
 
         # ---- matrix entries each segment node brings: (diag, previous node, node B back) as CSR indices (-1 = none) ----
-        A = sp.csr_matrix((np.arange(1, len(indices) + 1), indices, indptr), shape=(n, n))   # value = csr index + 1
+        A = sp.csr_matrix((np.arange(1, len(indices) + 1), indices, indptr), shape=(mesh.n, mesh.n))   # value = csr index + 1
         nz = np.asarray(nonzero, bool)
 
         def csr_of(a, b):
@@ -124,8 +141,19 @@ class BandPlan:
                     self.ab_csr[seg.g0 + t, k] = c
                     covered[c] = True
                     covered[A[post[t - back], v] - 1] = True
-        if not np.all(covered | ~nz):
+        inplan = self.iperm >= 0                          # (half plan: couplings across the symmetry line are not its entries)
+        mine = inplan[np.repeat(np.arange(mesh.n), np.diff(indptr))] & inplan[np.asarray(indices)]
+        if not np.all(covered | ~nz | ~mine):
             raise BandPlanError("the operator has entries outside the band (not a lattice fin?)")
+        self.ab_scale = self.rhs_scale = None             # half plan: 1/2 on the entries among centre-line nodes and on their load
+        if mirror:
+            self.mirror_of = mirror_permutation(mesh)
+            self.ab_scale = np.ones((self.G, 3))
+            for t, v in enumerate(post):
+                for k, back in enumerate((0, 1, B)):
+                    if t - back >= 0 and li[v] == x1 and li[post[t - back]] == x1:
+                        self.ab_scale[seg.g0 + t, k] = 0.5
+            self.rhs_scale = np.where(li[self.perm] == x1, 0.5, 1.0)
 
         # ---- where the fins' Schur complements go ---------------------------------------------------------------------
         # fin f leaves S (q+1 x q+1, lower triangle) on its interface nodes u_0..u_q.  S[t][t] adds to u_t's diagonal entry,
@@ -263,6 +291,9 @@ class BandPlan:
             a = flat[e]
             sl = slice(W_csr.indptr[a], W_csr.indptr[a + 1])
             idx[ptr[e]:ptr[e + 1]] = W_csr.indices[sl]; w[ptr[e]:ptr[e + 1]] = W_csr.data[sl]
+        if self.ab_scale is not None:                     # (halving is exact: the records stay the tables' own values)
+            sc = np.ones(self.nAB); sc[:len(flat)] = self.ab_scale.reshape(-1)
+            c0 *= sc; w *= np.repeat(sc, cnt)
         return c0, ptr.astype(np.int32), idx, w
 
     def compact_slots(self, c0, ptr, idx, w):
@@ -302,6 +333,8 @@ class BandPlan:
         n = self.n
         L = np.zeros(self.nL); Lx = np.zeros(max(self.nLx, 1)); y = np.zeros(n)
         Fe = np.asarray(F, float)[self.perm]
+        if self.rhs_scale is not None:
+            Fe = Fe * self.rhs_scale
         NX = max(self.NX, 1)
 
         def sweep(seg, is_post):
@@ -422,7 +455,9 @@ class BandPlan:
             return q
         for f, seg in enumerate(self.fin_segs):
             bsweep(seg, False, f)
-        out = np.empty(n); out[self.perm] = w
+        out = np.empty(self.n_mesh); out[self.perm] = w
+        if self.mirror:
+            out[self.mirror_of[self.perm]] = w             # the right half is the mirror image
         return out
 
 

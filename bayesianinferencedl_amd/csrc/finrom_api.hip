@@ -161,6 +161,10 @@ struct finrom_fom_s {
   BandDev band{};                      // frontal band sweep (finrom_fom_set_band); band.on = 0: interpreter
   BandGradDev band_grad{};             // adjoint gradient on the band layout (finrom_fom_set_band_gradient)
   FomDev band_asm{};                   // parameters of the band sweep's assembly pre-pass (fom_assemble_kernel)
+  // half-domain plan of a mirror-symmetric operator (finrom_fom_set_band_mirror): serves the calls that want no w
+  BandDev band_m{};
+  FomDev band_m_asm{};
+  const BandDev& band_for(bool want_w) const { return !want_w && band_m.on ? band_m : band; }
   std::vector<void*> owned;
   Scratch xT, Gw, gradT, qtmp;
   int last_path = FINROM_FOM_PATH_NONE;   // finrom_fom_last_path
@@ -566,7 +570,8 @@ static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* 
     return launch_fom_small(d, h->small, x, S, (double*)h->Gw.p, qoi, w, info, st);
   }
   if (h->band.on && !env_no_band) {
-    const BandDev& b = h->band;
+    const BandDev& b = h->band_for(w != nullptr);        // (the half plan of a mirror-symmetric operator when nobody wants w)
+    const FomDev& basm = &b == &h->band_m ? h->band_m_asm : h->band_asm;
     h->last_path = band_path(b, w == nullptr);
     const int64_t limit = fom_chunk_samples(d, &b);
     const int64_t npieces = (S + limit - 1) / limit;
@@ -580,7 +585,7 @@ static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* 
       }
       if (stages & 1) {
         if ((rc = launch_pack(x + s0 * d.xdim, Sc, d.xdim, (double*)h->xT.p, st))) return rc;
-        if ((rc = launch_fom_assemble(h->band_asm, (const double*)h->xT.p, nblk, (double*)h->Gw.p, st))) return rc;
+        if ((rc = launch_fom_assemble(basm, (const double*)h->xT.p, nblk, (double*)h->Gw.p, st))) return rc;
       }
       if (stages & 2) {
         if ((rc = launch_fom_band(b, (double*)h->Gw.p, nblk, Sc, qoi ? qoi + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st, w == nullptr))) return rc;
@@ -838,12 +843,12 @@ int finrom_fom_band_validate(const finrom_fom_band_desc* a, int32_t n, int32_t x
   return validate_band(a, n, xdim, n_obs, nullptr, nullptr);
 }
 
-int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
-  if (!h || !a) { set_error("fom_set_band: null argument"); return FINROM_ERR_ARG; }
-  const FomDev& d = h->d;
-  int64_t gsize = 0, nL = 0;
-  if (int rc = validate_band(a, d.n, d.xdim, d.n_obs, &gsize, &nL)) return rc;
-  const int n = d.n, G = a->nfins * (a->npf + a->nif) + a->npost, nift = a->nif * (a->nif + 1) / 2;
+// Device tables of a validated band descriptor for a problem of n dofs and n_obs computed observation rows (the handle's own
+// sizes for finrom_fom_set_band, the half problem's for finrom_fom_set_band_mirror): the sweep's BandDev and the parameters of
+// its assembly pre-pass.  The handle owns the uploads.
+static int build_band(finrom_fom_t h, const finrom_fom_band_desc* a, int n, int n_obs, int64_t gsize, int64_t nL, BandDev* b_out, FomDev* asm_out) {
+  struct { int n, xdim, n_obs; } d{n, h->d.xdim, n_obs};
+  const int G = a->nfins * (a->npf + a->nif) + a->npost, nift = a->nif * (a->nif + 1) / 2;
   BandDev b{};
   b.n = n; b.n_obs = d.n_obs; b.xdim = d.xdim; b.gsize = (int)gsize; b.nAB = a->nAB; b.nL = (int)nL; b.nLx = a->nLx;
   b.NSF = a->NSF; b.NSP = a->NSP; b.NX = a->NX; b.nfins = a->nfins; b.npf = a->npf; b.nif = a->nif; b.npost = a->npost;
@@ -859,7 +864,7 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
     for (int k = 0; k < 4 && t0 + k < t1; ++k) { reci[e * 8 + 1 + k] = a->ab_idx[t0 + k]; recd[e * 5 + 1 + k] = a->ab_w[t0 + k]; }
     reci[e * 8 + 5] = std::min(t0 + 4, t1); reci[e * 8 + 6] = t1;
   }
-  FomDev& q = h->band_asm;
+  FomDev& q = *asm_out;
   q = FomDev{};
   q.xdim = d.xdim; q.gsize = (int)gsize; q.n_alist = a->nAB;
   int rc = 0;
@@ -893,7 +898,66 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   }
   if (rc) return rc;
   b.on = getenv("FINROM_BAND_TIMING") != nullptr ? 2 : 1;      // 2: block 0 reports its phase clocks in sample 0's QoI (diagnostic)
+  *b_out = b;
+  return 0;
+}
+
+int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
+  if (!h || !a) { set_error("fom_set_band: null argument"); return FINROM_ERR_ARG; }
+  const FomDev& d = h->d;
+  int64_t gsize = 0, nL = 0;
+  if (int rc = validate_band(a, d.n, d.xdim, d.n_obs, &gsize, &nL)) return rc;
+  BandDev b{};
+  if (int rc = build_band(h, a, d.n, d.n_obs, gsize, nL, &b, &h->band_asm)) return rc;
   h->band = b;
+  h->band_m = BandDev{};                  // (a half plan belongs to the plan it was installed beside)
+  return 0;
+}
+
+// Host-only check of the half problem of a mirror-symmetric operator: the half descriptor like any band descriptor (for n_half dofs
+// and n_rows computed observation rows), register windows only, QoI-only tables present (the half plan serves calls without w),
+// and the map from computed rows to output columns: in range, every one of the n_obs output columns written exactly once.
+static int validate_band_mirror(const finrom_fom_band_desc* a, int n_half, int xdim, int n_rows, int n_obs, const int32_t* out_ptr,
+                                const int32_t* out_col, int64_t* gsize_out, int64_t* nL_out) {
+  if (!a || !out_ptr || !out_col || n_rows <= 0 || n_obs <= 0) { set_error("fom_set_band_mirror: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_band(a, n_half, xdim, n_rows, gsize_out, nL_out)) return rc;
+  auto bad = [&](const char* what) { set_error(std::string("fom_set_band_mirror: invalid ") + what); return FINROM_ERR_ARG; };
+  if (a->NSP > 14) { set_error("fom_set_band_mirror: only the register sweep takes a half plan"); return FINROM_ERR_UNSUPPORTED; }
+  if (!a->qoi_FgQ) return bad("descriptor (the half plan needs the QoI-only tables)");
+  if (out_ptr[0] != 0) return bad("out_ptr");
+  for (int o = 0; o < n_rows; ++o) if (out_ptr[o + 1] < out_ptr[o]) return bad("out_ptr");
+  if (out_ptr[n_rows] != n_obs) return bad("out_ptr (must end at the number of output columns)");
+  std::vector<char> written(n_obs, 0);
+  for (int c = 0; c < n_obs; ++c) {
+    const int col = out_col[c];
+    if (col < 0 || col >= n_obs) return bad("out_col (out of range)");
+    if (written[col]) return bad("out_col (an output column is written twice, another one not at all)");
+    written[col] = 1;
+  }
+  return 0;
+}
+
+int finrom_fom_band_mirror_validate(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                    const int32_t* out_ptr, const int32_t* out_col) {
+  return validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr);
+}
+
+int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* a, int32_t n_half, int32_t n_rows, const int32_t* out_ptr,
+                               const int32_t* out_col) {
+  if (!h || !a) { set_error("fom_set_band_mirror: null argument"); return FINROM_ERR_ARG; }
+  if (!h->band.on) { set_error("fom_set_band_mirror: finrom_fom_set_band has not been called"); return FINROM_ERR_ARG; }
+  const FomDev& d = h->d;
+  if (n_half <= 0 || n_half > d.n) { set_error("fom_set_band_mirror: invalid n_half"); return FINROM_ERR_ARG; }
+  int64_t gsize = 0, nL = 0;
+  if (int rc = validate_band_mirror(a, n_half, d.xdim, n_rows, d.n_obs, out_ptr, out_col, &gsize, &nL)) return rc;
+  BandDev b{};
+  FomDev q{};
+  if (int rc = build_band(h, a, n_half, n_rows, gsize, nL, &b, &q)) return rc;
+  int rc = up(h->owned, &b.out_ptr, out_ptr, n_rows + 1);
+  if (!rc) rc = up(h->owned, &b.out_col, out_col, d.n_obs);
+  if (rc) return rc;
+  b.n_out = d.n_obs;
+  h->band_m = b; h->band_m_asm = q;
   return 0;
 }
 
@@ -1643,7 +1707,8 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // FOM side, and only the sub-fin averages -- the head of the ROM half -- precede it.
   // Every workspace the two halves need is reserved BEFORE the fork: an allocation failure after it would return while the
   // side stream still writes the caller's outputs.  Any other failure after the fork joins the side stream first.
-  const bool split = S <= fom_chunk_samples(fom->d, &fom->band);
+  const BandDev& fband = fom->band_for(w != nullptr);
+  const bool split = S <= fom_chunk_samples(fom->d, &fband);
   // Round 4: beside the ONE-WAVE projection kernel (r <= 80, two 200-register waves per SIMD) the register band sweep (m <= 12, one
   // 312-register wave per SIMD) runs on a stream masked to THREE CUs of every shader engine (96 of 256): what the projection loses is
   // proportional to the CU-time it shares with sweep waves, and confined to fewer CUs the sweep's waves -- fewer at a time, less
@@ -1654,9 +1719,14 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   static const int env_fom_cus = getenv("FINROM_FOM_CUS") != nullptr ? atoi(getenv("FINROM_FOM_CUS")) : -1;
   static const bool env_no_band2 = getenv("FINROM_NO_BAND") != nullptr;
   int fom_cus = env_fom_cus;
+  // The half plan of a mirror-symmetric operator (finrom_fom_set_band_mirror: a 154-register wave, 60 KB per sample, 1.3 ms alone)
+  // is confined to ONE CU of every shader engine: it then lives 6.1 ms on 32 CUs instead of 3.1 ms on 96, still a third of the
+  // projection's time, and the projection loses least.  Headline, step in ms: unmasked 19.48, one CU per engine 19.06, two 19.20,
+  // three 19.32 (the full plan with three: 20.11-20.15).
+  const bool half_plan = &fband == &fom->band_m;
   if (fom_cus < 0)
     fom_cus = (rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !env_no_band2 &&
-               w == nullptr && S >= 16384) ? -3 : 0;
+               w == nullptr && S >= 16384) ? (half_plan ? -1 : -3) : 0;
   hipStream_t fst = st;
   if (overlap && fom_cus != 0) {
     if ((rc = rom->ensure_fom_side(fom_cus))) return rc;

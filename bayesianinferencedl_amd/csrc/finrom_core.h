@@ -191,6 +191,10 @@ struct BandDev {
   const double* FgQ = nullptr;       // [G] observation weights on the fins' segment nodes, the load on the post's
   const int* qobs_ptr = nullptr; const int* qobs_idx = nullptr; const double* qobs_w = nullptr;   // post-only remainder of B_obs
   const int* row_fin = nullptr;      // [n_obs] fin whose functional belongs to the row, -1: none
+  // half plan of a mirror-symmetric operator (finrom_fom_set_band_mirror): the n_obs computed rows are stored to the n_out columns
+  // of the caller's QoI that out_col[out_ptr[o] .. out_ptr[o + 1]) lists (a row and its mirror twin: one value, two columns)
+  int n_out = 0;
+  const int* out_ptr = nullptr; const int* out_col = nullptr;
 };
 struct BandGradDev {              // adjoint gradient on the band layout (finrom_fom_set_band_gradient)
   int on = 0;

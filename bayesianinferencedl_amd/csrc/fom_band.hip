@@ -506,7 +506,7 @@ __device__ __forceinline__ double qoi_row(const BandDev& p, const Io& io, const 
 }
 
 template <int NSF, int NSP, int NXM, bool QO>
-__global__ __launch_bounds__(64) void fom_band_kernel(BandDev p, const int* __restrict__ abmap, const double* __restrict__ Fg,
+__device__ __forceinline__ void fom_band_body(BandDev p, const int* __restrict__ abmap, const double* __restrict__ Fg,
                                                       const int* __restrict__ act,
                                                       const int* __restrict__ lx_ptr, const int* __restrict__ ent_extra,
                                                       const int* __restrict__ ecp_ptr, const int* __restrict__ ecp_slot,
@@ -565,7 +565,10 @@ __global__ __launch_bounds__(64) void fom_band_kernel(BandDev p, const int* __re
   }
   for (int o = 0; o < p.n_obs; ++o) {                    // QoI = B_obs w (fom :408-412)
     const double q = qoi_row(p, io, obs_ptr, obs_idx, obs_w, row_fin, iface_elim, o, QO);
-    if (s < S) qoi[s * p.n_obs + o] = bad ? nanv : q;
+    if (p.out_ptr != nullptr) {                          // half plan: each distinct row once, stored to all its output columns
+      if (s < S)
+        for (int c = p.out_ptr[o], c1 = p.out_ptr[o + 1]; c < c1; ++c) qoi[s * p.n_out + p.out_col[c]] = bad ? nanv : q;
+    } else if (s < S) qoi[s * p.n_obs + o] = bad ? nanv : q;
   }
 }
 
@@ -785,6 +788,16 @@ __device__ __forceinline__ void fom_band_ldsw_body(const BandDev& p, const int* 
     const int* __restrict__ obs_idx, const double* __restrict__ obs_w, const int* __restrict__ row_fin, double* __restrict__ Gw, int64_t S, \
     double* __restrict__ qoi, int* __restrict__ info
 #define FR_BAND_PASS p, abmap, Fg, act, lx_ptr, ent_extra, ecp_ptr, ecp_slot, ecp_off, schur_off, iface_elim, obs_ptr, obs_idx, obs_w, row_fin, Gw, S, qoi, info
+template <int NSF, int NSP, int NXM, bool QO>
+__global__ __launch_bounds__(64) void fom_band_kernel(FR_BAND_ARGS) { fom_band_body<NSF, NSP, NXM, QO>(FR_BAND_PASS); }
+// The same sweep for the half plans of mirror-symmetric operators (bandplan.py, BandPlan(mirror=True)), under a name of its own in
+// a kernel trace and with a register budget of its own: the second launch bound is the number of waves per SIMD the compiler has
+// to leave room for (3: the 154 registers the (5, 8) window takes uncapped; 4: <= 128; 5: <= 96).  DESIGN 5 has the measurements.
+#ifndef FINROM_HALF_WPE
+#define FINROM_HALF_WPE 3
+#endif
+template <int NSF, int NSP, int NXM, bool QO>
+__global__ __launch_bounds__(64, FINROM_HALF_WPE) void fom_band_half_kernel(FR_BAND_ARGS) { fom_band_body<NSF, NSP, NXM, QO>(FR_BAND_PASS); }
 template <int NSF, int NSP, int NXM, int WV, bool QO>
 __global__ __launch_bounds__(64 * WV) void fom_band_ldsw_kernel(FR_BAND_ARGS) { fom_band_ldsw_body<NSF, NSP, NXM, WV, QO>(FR_BAND_PASS); }
 
@@ -809,11 +822,11 @@ int launch_ldsw(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* q
   return 0;
 }
 
-template <int NSF, int NSP, bool QO>
+template <int NSF, int NSP, bool QO, int NXM = 4, bool HALF = false>
 int launch_t(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st) {
-  constexpr int NXM = 4;
   const size_t lds = (size_t)XL<NSP, NXM>::SIZE * 64 * sizeof(double);
-  hipLaunchKernelGGL((fom_band_kernel<NSF, NSP, NXM, QO>), dim3((unsigned)nblk), dim3(64), lds, st, FR_BAND_LAUNCH_ARGS(QO));
+  if constexpr (HALF) hipLaunchKernelGGL((fom_band_half_kernel<NSF, NSP, NXM, QO>), dim3((unsigned)nblk), dim3(64), lds, st, FR_BAND_LAUNCH_ARGS(QO));
+  else hipLaunchKernelGGL((fom_band_kernel<NSF, NSP, NXM, QO>), dim3((unsigned)nblk), dim3(64), lds, st, FR_BAND_LAUNCH_ARGS(QO));
   FR_HIP(hipGetLastError());
   return 0;
 }
@@ -832,6 +845,7 @@ int launch_fom_band_wide(const BandDev& p, double* Gw, int64_t nblk, int64_t S, 
 #else
 bool band_supported(int NSF, int NSP, int NX) {
   if (NX <= 4 && ((NSF == 3 && NSP == 6) || (NSF == 4 && NSP == 10) || (NSF == 5 && NSP == 14))) return true;      // window in registers
+  if (NX <= 2 && ((NSF == 3 && NSP == 4) || (NSF == 4 && NSP == 6) || (NSF == 5 && NSP == 8))) return true;        // ... of the half plans (m = 4, 8, 12)
   if (NX <= 8 && ((NSF == 6 && NSP == 18) || (NSF == 7 && NSP == 22))) return true;                                 // window over four waves
   return (NX <= 10 && NSF == 8 && NSP == 26) || (NX <= 12 && NSF == 9 && NSP == 30);                               // (some of the extras' rows in the workspace)
 }
@@ -849,6 +863,10 @@ int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, doubl
   const bool qo = qoi_only && p.qo;
 #define FR_T(A, B) if (p.NSF == A && p.NSP == B) return qo ? launch_t<A, B, true>(p, Gw, nblk, S, qoi, info, st) : launch_t<A, B, false>(p, Gw, nblk, S, qoi, info, st);
   FR_T(3, 6) FR_T(4, 10) FR_T(5, 14)
+#undef FR_T
+  // the half plans of the same meshes (mirror-symmetric operators, bandplan.py): at most two extras alive
+#define FR_T(A, B) if (p.NSF == A && p.NSP == B) return qo ? launch_t<A, B, true, 2, true>(p, Gw, nblk, S, qoi, info, st) : launch_t<A, B, false, 2, true>(p, Gw, nblk, S, qoi, info, st);
+  FR_T(3, 4) FR_T(4, 6) FR_T(5, 8)
 #undef FR_T
   FR_W4(6, 18, 8) FR_W4(7, 22, 8)
   if (p.NSP >= 26) return launch_fom_band_wide(p, Gw, nblk, S, qoi, info, st, qo);

@@ -128,6 +128,7 @@ class FomEngine:
     def __init__(self, plan, c0_csr, W_csr, rhs, B_obs, pattern=None, ops=None):
         self.plan = plan
         self.band = None
+        self.band_mirror = None             # half-domain plan of a mirror-symmetric operator (calls without w), if installed
         self.n = plan.n
         W_csr = sp.csr_matrix(W_csr)
         self.xdim = W_csr.shape[1]
@@ -180,6 +181,8 @@ class FomEngine:
         c0, ptr, idx, w = bp.ab_table(c0_csr, W_csr)
         abmap, c0p, ptrp, idxp, wp = bp.compact_slots(c0, ptr, idx, w)      # logical -> physical value slots (duplicates shared)
         F = np.asarray(rhs, dtype=np.float64)
+        if bp.rhs_scale is not None:                     # half plan: the centre line's load is halved (bandplan.py)
+            F = F.copy(); F[bp.perm] *= bp.rhs_scale
         Fg = np.zeros(bp.G)
         for seg in bp.fin_segs + [bp.post_seg]:
             Fg[seg.g0:seg.g0 + seg.npiv] = F[bp.perm[seg.e0:seg.e0 + seg.npiv]]
@@ -199,7 +202,8 @@ class FomEngine:
                         nterms=len(idxp), nLx=bp.nLx, ab_c0=D(c0p), ab_ptr=I(ptrp), ab_idx=I(idxp), ab_w=D(wp), abmap=I(abmap[:3 * bp.G]),
                         Fg=D(Fg), act=I(bp.act), lx_ptr=I(bp.lx_ptr), ent_extra=I(bp.ent_extra),
                         ecp_ptr=I(bp.ecp_ptr), ecp_slot=I(bp.ecp_slot), ecp_off=I(abmap[bp.ecp_off] if len(bp.ecp_off) else bp.ecp_off),
-                        schur_off=I(schur), iface_elim=I(bp.iface_elim), perm=I(bp.perm),
+                        schur_off=I(schur), iface_elim=I(bp.iface_elim),
+                        perm=I(np.arange(bp.n) if bp.mirror else bp.perm),      # (the half plan serves no call that unpacks w)
                         obs_ptr=I(optr), obs_idx=I(oidx), obs_w=D(ow))
         if qo is not None:
             FgQ, row_fin, qptr, qidx, qw = qo
@@ -262,6 +266,104 @@ class FomEngine:
         self._B_band = sp.csr_matrix(np.asarray(B_obs)[:, bp.perm]) if not sp.issparse(B_obs) else sp.csr_matrix(B_obs)[:, bp.perm]
         self.band_slots = nslots            # physical value slots per sample (bench: algorithmic bytes)
         self.band_qoi_only = bool(d.qoi_FgQ)      # calls without w: QoI-only form
+        self._enable_mirror(ops, c0_csr, W_csr, rhs, B_obs)
+
+    @staticmethod
+    def mirror_rows(ops, c0_csr, W_csr, rhs, B_obs, tol=1e-13):
+        """Is this operator table mirror-symmetric about x = 3?  With P the mesh's mirror permutation (bandplan.mirror_permutation)
+        and the pattern entry (a, b) mapped to (P a, P b): `c0`, every column of `W` (the PARAMETERS stay where they are: a nodal
+        field or nine fin conductivities are not symmetric, the five-parameter lift is), `rhs`, and the rows of `B_obs`, each
+        of which must map onto a row.  Tolerance `tol` relative to each table's largest magnitude; the tables of the lattice
+        mesh are symmetric to 4.4e-15 in that measure (m = 12: c0 4.1e-15, W 2.0e-15, B_obs 4.4e-15, F exactly; m = 4, 8: <= 2e-16).
+        -> twin[o] = the row that mirrors row o (twin[o] == o: a self-mirrored row), or None."""
+        from .bandplan import mirror_permutation
+        n = ops.n
+        P = mirror_permutation(ops.mesh)
+        indptr, indices = np.asarray(ops.indptr), np.asarray(ops.indices)
+        rows = np.repeat(np.arange(n), np.diff(indptr))
+        key = rows.astype(np.int64) * n + indices
+        order = np.argsort(key, kind="stable")
+        mkey = P[rows] * n + P[indices]
+        pos = np.searchsorted(key[order], mkey)
+        if np.any(pos >= len(key)) or np.any(key[order][np.minimum(pos, len(key) - 1)] != mkey):
+            return None                                   # the pattern itself is not mirror-symmetric
+        pe = order[pos]                                   # entry (a, b) -> entry (P a, P b)
+
+        def same(a, b):
+            a, b = (sp.csr_matrix(a), sp.csr_matrix(b)) if sp.issparse(a) or sp.issparse(b) else (np.asarray(a, float), np.asarray(b, float))
+            scale = abs(a).max()
+            return scale == 0.0 or abs(a - b).max() <= tol * scale
+        c0 = np.asarray(c0_csr, dtype=np.float64)
+        W = sp.csr_matrix(W_csr)
+        F = np.asarray(rhs, dtype=np.float64)
+        if not (same(c0, c0[pe]) and same(W, W[pe]) and same(F, F[P])):
+            return None
+        B = B_obs.toarray() if sp.issparse(B_obs) else np.asarray(B_obs, dtype=np.float64)
+        Bm, scale = B[:, P], np.abs(B).max()
+        twin = np.full(B.shape[0], -1, np.int64)
+        for o in range(B.shape[0]):
+            hit = np.nonzero(np.abs(B - Bm[o][None, :]).max(axis=1) <= tol * scale)[0]
+            if len(hit) != 1:
+                return None
+            twin[o] = hit[0]
+        if np.any(twin[twin] != np.arange(len(twin))):
+            return None
+        return twin
+
+    @staticmethod
+    def mirror_tables(ops, bp, B_obs, twin):
+        """Observation operator of the half problem.  For a mirror-symmetric w, row o is  sum_l (B[o, l] + B[o, P l]) w_l  over
+        the left nodes plus its own weights on the centre line: a row that lives on a left fin stays as it is, a self-mirrored
+        row (the post's) is folded, and the right-hand twin of a row is not computed at all -- it is a copy.
+        -> (B_half [rows x n_mesh] in dof columns, out_ptr, out_col: the output columns of each computed row)."""
+        B = B_obs.toarray() if sp.issparse(B_obs) else np.asarray(B_obs, dtype=np.float64)
+        P = bp.mirror_of
+        left = bp.perm[bp.rhs_scale == 1.0]
+        reps = [o for o in range(len(twin)) if o <= twin[o]]
+        Bh = np.zeros((len(reps), B.shape[1]))
+        Bh[:, bp.perm] = B[reps][:, bp.perm]
+        Bh[:, left] += B[reps][:, P[left]]
+        out_ptr, out_col = [0], []
+        for o in reps:
+            out_col += [o] if twin[o] == o else [o, int(twin[o])]
+            out_ptr.append(len(out_col))
+        return Bh, np.asarray(out_ptr, np.int32), np.asarray(out_col, np.int32)
+
+    @staticmethod
+    def mirror_form(ops, xdim, c0_csr, W_csr, rhs, B_obs):
+        """The half-domain form of one operator table, or None: the table must be mirror-symmetric (mirror_rows), the mesh must
+        have a half plan and the half operator QoI-only tables (the half plan serves calls without w only).
+        -> (half plan, its finrom_fom_band_desc, arrays the descriptor borrows, physical slots, out_ptr, out_col)."""
+        bpm = ops.band_plan_mirror() if hasattr(ops, "band_plan_mirror") else None
+        if bpm is None:
+            return None
+        twin = FomEngine.mirror_rows(ops, c0_csr, W_csr, rhs, B_obs)
+        if twin is None:
+            return None
+        Bh, out_ptr, out_col = FomEngine.mirror_tables(ops, bpm, B_obs, twin)
+        d, keep, nslots = FomEngine.band_descriptor(bpm, xdim, c0_csr, W_csr, rhs, Bh)
+        if not d.qoi_FgQ:
+            return None
+        return bpm, d, keep, nslots, out_ptr, out_col
+
+    def _enable_mirror(self, ops, c0_csr, W_csr, rhs, B_obs):
+        """Install the half-domain plan for calls that want no w (finrom_fom_set_band_mirror) when the operator table is
+        mirror-symmetric (mirror_rows), the half operator has QoI-only tables and the library has the half plan's window sizes.
+        Otherwise nothing changes.  FINROM_NO_MIRROR=1 at engine creation switches the form off."""
+        self.band_mirror = None
+        if _os.environ.get("FINROM_NO_MIRROR") is not None or not self.band_qoi_only:
+            return
+        form = self.mirror_form(ops, self.xdim, c0_csr, W_csr, rhs, B_obs)
+        if form is None:
+            return
+        bpm, d, keep, nslots, out_ptr, out_col = form
+        op, oc = i32(out_ptr), i32(out_col)
+        rc = lib().finrom_fom_set_band_mirror(self._h, C.byref(d), bpm.n, len(out_ptr) - 1, op[1], oc[1])
+        if rc == -4:                                     # window sizes not built in
+            return
+        check(rc, "finrom_fom_set_band_mirror")
+        self.band_mirror = bpm
+        self.band_mirror_slots = nslots
 
     def solve(self, X, want_w=False):
         b = _Batch(X, self.xdim)

@@ -352,6 +352,18 @@ class FinOperators:
                 self._band_plan = None
         return self._band_plan
 
+    def band_plan_mirror(self):
+        """Plan of the band sweep on the left half of the fin up to the symmetry line x = 3 (BandPlan(mirror=True)): what a
+        mirror-symmetric operator -- the five-parameter conductivity -- needs solved.  None like band_plan()."""
+        if not hasattr(self, "_band_plan_mirror"):
+            from .bandplan import BandPlan, BandPlanError, nonzero_entries
+            try:
+                self._band_plan_mirror = BandPlan(self.mesh, self.indptr, self.indices,
+                                                  nonzero_entries(self.robin_vals, self.W_field, list(self.sub_vals)), mirror=True)
+            except BandPlanError:
+                self._band_plan_mirror = None
+        return self._band_plan_mirror
+
     # -- convenience ----------------------------------------------------------
     def csr(self, vals):
         return sp.csr_matrix((vals, self.indices, self.indptr), shape=(self.n, self.n))

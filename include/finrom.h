@@ -249,6 +249,26 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* desc);
  * only (the four-wave kernel sweeps the fins of a sample block on different waves).  Host only: usable without a GPU. */
 int finrom_fom_band_validate(const finrom_fom_band_desc* desc, int32_t n, int32_t xdim, int32_t n_obs);
 
+/* The half problem of a MIRROR-SYMMETRIC operator, for the calls that want no w (finrom_fom_solve with w == NULL, the FOM half of
+ * finrom_solve_pairs).  Where the conductivity, the load and the observation operator are the same left and right of the fin's
+ * symmetry line x = 3 (the five-parameter conductivity on the lattice mesh), so is w, and the sweep only has to solve the left half
+ * up to that line: four fins, a post half as wide, under a third of the multiply-adds and of the factor.  `desc` describes the half
+ * problem 1/2 E^T A E u = 1/2 E^T F like any band plan (bayesianinferencedl_amd/bandplan.py, BandPlan(mirror=True)): n_half dofs,
+ * n_rows DISTINCT observation rows with their QoI-only tables (required: a row and its mirror twin are one row, a self-mirrored row
+ * is folded onto the left nodes), windows (3, 4), (4, 6) or (5, 8) with NX <= 2; desc->perm is the identity (no w leaves this plan).
+ * Computed row o is stored to the output columns out_col[out_ptr[o] .. out_ptr[o + 1]) of the handle's n_obs -- every column
+ * exactly once -- NaN and the info flag of a sample that is not positive definite included.  Calls that want w, gradients and
+ * finrom_fom_solve_rhs keep the plan of finrom_fom_set_band, which must have been called; finrom_fom_last_path reports
+ * FINROM_FOM_PATH_BAND_REGISTERS_QOI.  FINROM_ERR_UNSUPPORTED when the window sizes are not built in: nothing changes then.
+ * Whether an operator table IS symmetric is the caller's finding (engine.py tests c0, every column of W, the load and the rows of
+ * B_obs under the mesh's mirror permutation to 1e-13 of each table's largest entry; FINROM_NO_MIRROR=1 at engine creation keeps
+ * the full plan for every call). */
+int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* desc, int32_t n_half, int32_t n_rows, const int32_t* out_ptr,
+                               const int32_t* out_col);
+/* Its checks, host only: finrom_fom_band_validate for (n_half, xdim, n_rows), plus the output map for n_obs columns. */
+int finrom_fom_band_mirror_validate(const finrom_fom_band_desc* desc, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                    const int32_t* out_ptr, const int32_t* out_col);
+
 /* The adjoint gradient on the band sweep's layout (finrom_fom_gradient for batches beyond the small-batch schedule): after the
  * full sweep the workspace holds the factor and w; A v = -B_obs^T (B_obs w - d) is solved with the stored columns (one forward
  * substitution, one more backward sweep) and grad_j = sum dA_ab/dx_j v_a w_b is contracted there.  Tables over the band plan's
@@ -546,7 +566,8 @@ int finrom_sampler_pullback(finrom_sampler_t h, const double* g, int64_t S, doub
  * concurrently, on a stream owned by the library, theta = Sop x (sub-fin averages of the
  * field, or of the interpolated per-fin conductivities) and the LSPG reduced solve + QoI;
  * then err = qoi - qoi_r.  (Large batches of the r <= 80 / m <= 12 pairing: the FOM's band
- * sweep runs on a library stream restricted to three CUs of every shader engine -- the
+ * sweep runs on a library stream restricted to three CUs of every shader engine, one
+ * where the half plan of finrom_fom_set_band_mirror serves the call -- the
  * HBM-bound sweep then shares fewer SIMDs with the projection, DESIGN.md 5 -- its pack +
  * assembly pre-pass on an unmasked stream, and when the caller's stream is a non-blocking
  * one the ROM half stays on it: no cross-stream wait on the call's critical path.

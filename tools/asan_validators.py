@@ -161,4 +161,52 @@ band_cases(12, ("five",), corrupt=True)
 band_cases(20, ("field",), corrupt=True)
 for m_ in (4, 8, 16):
     band_cases(m_, ("field", "nine", "five"), corrupt=False)
+
+
+# ---- the half plan of a mirror-symmetric operator (finrom_fom_set_band_mirror's validator, exported as
+# finrom_fom_band_mirror_validate): the half descriptor like every other table, plus the map from computed rows to output columns
+def mirror_cases(m):
+    Vm = get_space(None, m=m)
+    ops = Vm.operators()
+    fin = Fin(Vm)
+    W = sp.csr_matrix(ops.W_field @ sp.csr_matrix(ops.N9 @ ops.E59))
+    form = FomEngine.mirror_form(ops, 5, ops.robin_vals, W, ops.F, fin.B_obs)
+    assert form is not None, m
+    bp, d, keep, _, out_ptr, out_col = form
+    op, oc = np.array(out_ptr, np.int32), np.array(out_col, np.int32)
+    nrows = len(op) - 1
+    call = lambda: lib.finrom_fom_band_mirror_validate(C.byref(d), bp.n, 5, nrows, fin.n_obs, op.ctypes.data_as(_ffi.c_i32p),
+                                                       oc.ctypes.data_as(_ffi.c_i32p))
+    rc = call()
+    assert rc == 0, (m, lib.finrom_last_error())
+    cases.append((f"half band descriptor m={m}: accepted", rc))
+    tweak(oc, 1, oc[0], call, "mirror: an output column written twice, another one never")
+    tweak(oc, 0, fin.n_obs, call, "mirror: output column out of range")
+    tweak(oc, 2, -1, call, "mirror: negative output column")
+    tweak(op, nrows, fin.n_obs - 1, call, "mirror: the last output column is nobody's")
+    tweak(op, 1, -1, call, "mirror: out_ptr not monotone")
+    tweak(op, 0, 1, call, "mirror: out_ptr does not start at zero")
+    tweak(d.abmap, 7, d.nAB, call, "mirror: abmap out of range")
+    tweak(d.iface_elim, 1, bp.n, call, "mirror: iface_elim beyond the half problem")
+    tweak(d.obs_idx, 0, bp.n, call, "mirror: observation index beyond the half problem")
+    tweak(d.perm, 0, d.perm[1], call, "mirror: perm is not a permutation")
+    tweak(d.schur_off, 1, d.schur_off[0], call, "mirror: Schur slot repeated within a fin")
+    tweak(d.qoi_obs_w, 0, d.qoi_obs_w[0] * 2, call, "mirror: QoI-only remainder weight differs")
+    for field in ("qoi_FgQ", "qoi_row_fin", "qoi_obs_ptr", "abmap", "act"):
+        ptype = type(getattr(d, field))
+        addr = C.cast(getattr(d, field), C.c_void_p).value
+        setattr(d, field, ptype())
+        try:
+            expect_error(f"mirror: {field} is NULL", call())
+        finally:
+            setattr(d, field, C.cast(addr, ptype))
+    expect_error("mirror: n_half of the full mesh", lib.finrom_fom_band_mirror_validate(
+        C.byref(d), ops.n, 5, nrows, fin.n_obs, op.ctypes.data_as(_ffi.c_i32p), oc.ctypes.data_as(_ffi.c_i32p)))
+    expect_error("mirror: null output map", lib.finrom_fom_band_mirror_validate(C.byref(d), bp.n, 5, nrows, fin.n_obs, None, None))
+    expect_error("fom_set_band_mirror: null", lib.finrom_fom_set_band_mirror(None, None, 0, 0, None, None))
+    assert call() == 0, ("half descriptor not restored", lib.finrom_last_error())
+
+
+for m_ in (4, 8, 12):
+    mirror_cases(m_)
 print(f"ASAN-VALIDATORS-OK {len(cases)} cases")

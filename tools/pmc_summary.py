@@ -13,7 +13,7 @@ import sys
 out = sys.argv[1]
 WORKLOADS = {"headline": "five/m12/r80/S100000", "c3": "nine/m12/r120/S100000", "c4": "field/m20/r200/S20000",
              "c4full": "field/m20/r200/S125000"}
-SLOT_OF = {"fom_band_kernel": "fom_chol_solve", "fom_band_ldsw_kernel": "fom_chol_solve", "fom_vm_kernel": "fom_chol_solve",
+SLOT_OF = {"fom_band_kernel": "fom_chol_solve", "fom_band_half_kernel": "fom_chol_solve", "fom_band_ldsw_kernel": "fom_chol_solve", "fom_vm_kernel": "fom_chol_solve",
            "fom_bwd_kernel": "fom_chol_solve", "fom_small_kernel": "fom_chol_solve", "rom_gram_kernel": "rom_proj_mfma",
            "rom_gram_store_kernel": "rom_proj_mfma", "fom_assemble_kernel": "fom_assemble", "rom_proj_kernel": "rom_proj_mfma",
            "rom_proj_single_kernel": "rom_proj_mfma", "rom_solve_kernel": "rom_reduced_solve",
