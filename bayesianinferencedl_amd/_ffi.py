@@ -141,6 +141,10 @@ SIGNATURES = {
     "finrom_fom_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5),
     "finrom_rom_create": (C.c_int, [C.POINTER(RomDesc), C.POINTER(C.c_void_p)]),
     "finrom_rom_grouped_tables": (C.c_int, [C.POINTER(RomDesc), c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, c_f64p, c_i32p]),
+    "finrom_rom_set_mirror": (C.c_int, [C.c_void_p, C.POINTER(RomDesc), c_i32p, c_f64p, c_i32p]),
+    "finrom_rom_mirror_validate": (C.c_int, [C.POINTER(RomDesc), C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "finrom_rom_mirror_tables": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, c_f64p, c_i32p]),
+    "finrom_rom_last_form": (C.c_int, [C.c_void_p]),
     "finrom_rom_destroy": (None, [C.c_void_p]),
     "finrom_rom_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -203,6 +207,8 @@ ERR_UNSUPPORTED = -4                      # FINROM_ERR_UNSUPPORTED (include/finr
 # finrom_fom_last_path codes (include/finrom.h)
 FOM_PATHS = {0: "none", 1: "small_lds", 2: "small_global", 3: "interpreter", 4: "band_registers", 5: "band_lds_4wave",
              7: "band_registers_qoi", 8: "band_lds_4wave_qoi"}
+# finrom_rom_last_form codes (include/finrom.h)
+ROM_FORMS = {0: "none", 1: "full", 2: "half"}
 
 _lib = None
 

@@ -176,6 +176,8 @@ struct finrom_rom_s {
   int g_npairs = 0; const int* g_pair_p = nullptr; const int* g_pair_i = nullptr; const double* g_Gt = nullptr;
   RomGramDev gram;                     // offline/online form (finrom_rom_set_gram); gram.h is filled at create
   int projection = FINROM_PROJECTION_DIRECT;
+  std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
+  int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
   hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's
@@ -1208,55 +1210,69 @@ std::vector<KStep> uniform_ksteps(const finrom_rom_desc* a, const std::vector<in
 // first, at scale 1, with the usual coefficients.  The per-sample scalars (1, theta, 1 / theta, the rescale factors) are
 // one row of RomDev::ext, filled by rom_ext_kernel ahead of the projection kernel; the records name them by index.
 struct GroupedTables { std::vector<double> tvg; std::vector<int> kmg, def; int nkg = 0, n_ext = 0, ext_final = 0; };
-bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ksteps, int rp, GroupedTables& out) {
+// kclass (the half list of a mirror-symmetric ROM, DESIGN 4b'): per k-step 0 = rows that count twice (left of the symmetry line),
+// 1 = rows that count once (on it).  The k-steps that count twice all come first; the factor of the record that opens the first
+// k-step that counts once -- or the final factor if there is none -- carries an exact 2 (bit 1 of its ext_def flags), so the
+// weights act on the accumulators and no row is scaled by sqrt(2).  slot0 / ext0: the list's rows and factors sit behind
+// another list's (slot0 table slots, ext0 scalars, of which the first 1 + 2 P are shared); `def` then holds the factors only.
+bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ksteps, int rp, GroupedTables& out,
+                          const std::vector<int>* kclass = nullptr, int slot0 = 0, int ext0 = 0) {
   const int r = a->r;
-  struct GStep { int group; std::vector<int> pat; const int* rows; };
+  struct GStep { int cls, group; std::vector<int> pat; const int* rows; };
   std::vector<GStep> gs;
-  for (const KStep& ks : ksteps) {
+  for (size_t k = 0; k < ksteps.size(); ++k) {
+    const KStep& ks = ksteps[k];
     if (ks.rows[0] < 0 && ks.rows[1] < 0 && ks.rows[2] < 0 && ks.rows[3] < 0) continue;      // (padding k-steps of the ungrouped list)
     int group = 0;
     std::vector<int> pat = ks.pat;
     if (pat.size() == 1 && pat[0] != 0) group = pat[0];
     else if (pat.size() == 2 && (pat[0] == 0) != (pat[1] == 0)) { group = pat[0] ? pat[0] : pat[1]; pat = {group, 0}; }
-    gs.push_back({group, pat, ks.rows});
+    gs.push_back({kclass ? (*kclass)[k] : 0, group, pat, ks.rows});
   }
-  std::stable_sort(gs.begin(), gs.end(), [](const GStep& x, const GStep& y) { return x.group < y.group; });
-  std::vector<int> groups;
-  for (const GStep& g : gs) if (g.group && (groups.empty() || groups.back() != g.group)) groups.push_back(g.group);
-  const int P = a->P, n_ext = 1 + 2 * P + (int)groups.size() + 1;
-  if (groups.empty() || n_ext > 64) return false;
-  // ext[0] = 1, ext[p] = theta_p, ext[P + p] = 1 / theta_p, then one factor per change of group; as (numerator, denominator, squared)
-  std::vector<int> def(3 * (size_t)n_ext, 0);
-  for (int pp = 1; pp <= P; ++pp) { def[3 * pp] = pp; def[3 * (P + pp) + 1] = pp; }
-  std::vector<int> factor_of(groups.size() + 1);
-  for (size_t g = 0; g <= groups.size(); ++g) {
-    const int e = 1 + 2 * P + (int)g;
-    def[3 * e] = g == 0 ? 0 : groups[g - 1]; def[3 * e + 1] = g == groups.size() ? 0 : groups[g]; def[3 * e + 2] = 1;
-    factor_of[g] = e;
+  std::stable_sort(gs.begin(), gs.end(), [](const GStep& x, const GStep& y) { return x.cls != y.cls ? x.cls < y.cls : x.group < y.group; });
+  // segments: runs of one (class, group); segment 0 is the scale-1 start (group 0 of the first class, possibly empty)
+  struct Seg { int cls, group; };
+  std::vector<Seg> segs;
+  bool any_group = false;
+  if (!gs.empty()) segs.push_back({gs[0].cls, 0});
+  for (const GStep& g : gs) {
+    if (g.cls != segs.back().cls || g.group != segs.back().group) segs.push_back({g.cls, g.group});
+    any_group = any_group || g.group != 0;
+  }
+  const int P = a->P, nfac = (int)segs.size(), base = ext0 ? ext0 : 1 + 2 * P, n_ext = base + nfac;
+  if (!any_group || n_ext > 64) return false;
+  // ext[0] = 1, ext[p] = theta_p, ext[P + p] = 1 / theta_p, then one factor per change of segment and the final one; as
+  // (numerator, denominator, flags: 1 squared, 2 times two)
+  std::vector<int> def(ext0 ? 0 : 3 * (size_t)base, 0);
+  if (!ext0) for (int pp = 1; pp <= P; ++pp) { def[3 * pp] = pp; def[3 * (P + pp) + 1] = pp; }
+  for (int g = 0; g < nfac; ++g) {      // factor g: from segment g to segment g + 1, the last one back to scale 1
+    const bool last = g + 1 == nfac;
+    const bool twice = kclass != nullptr && segs[g].cls == 0 && (last || segs[g + 1].cls == 1);
+    def.push_back(segs[g].group); def.push_back(last ? 0 : segs[g + 1].group); def.push_back(1 | (twice ? 2 : 0));
   }
   std::vector<double>& tvg = out.tvg; std::vector<int>& kmg = out.kmg;
   tvg.clear(); kmg.clear();
-  int slot = 0, prev = 0;
+  int slot = slot0, seg = 0;
   bool first = true;
   for (const GStep& g : gs) {
     const int nt = (int)g.pat.size();
     int rec[8] = {slot, nt, 0, 0, 0, 0, 0, 0};
     for (int t = 0; t < nt; ++t) rec[4 + t] = g.group ? (t == 0 ? 0 : P + g.group) : g.pat[t];
     if (rec[4] == 0) rec[2] |= 1;                       // the first coefficient is 1: its rows are the slab as they are
-    if (g.group != prev && !first) {                   // (nothing to rescale in front of the very first k-step)
-      const size_t gi = std::find(groups.begin(), groups.end(), g.group) - groups.begin();
-      rec[2] |= 2; rec[3] = factor_of[gi];             // (from scale 1: (1 / theta_d)^2)
+    if (g.cls != segs[seg].cls || g.group != segs[seg].group) {
+      ++seg;
+      if (!first) { rec[2] |= 2; rec[3] = base + seg - 1; }      // (nothing to rescale in front of the very first k-step)
     }
-    prev = g.group; first = false;
+    first = false;
     kmg.insert(kmg.end(), rec, rec + 8);
     for (int t = 0; t < nt; ++t)
       for (int q = 0; q < 4; ++q) {
-        const size_t base = tvg.size();
-        tvg.resize(base + rp, 0.0);
+        const size_t base_ = tvg.size();
+        tvg.resize(base_ + rp, 0.0);
         const int row = g.rows[q];
         if (row < 0) continue;
         for (int tt = a->row_ptr[row]; tt < a->row_ptr[row + 1]; ++tt)
-          if (a->term_p[tt] == g.pat[t]) for (int col = 0; col < r; ++col) tvg[base + col] += a->term_val[(size_t)tt * r + col];
+          if (a->term_p[tt] == g.pat[t]) for (int col = 0; col < r; ++col) tvg[base_ + col] += a->term_val[(size_t)tt * r + col];
       }
     slot += nt;
   }
@@ -1267,8 +1283,46 @@ bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ks
   tvg.resize(tvg.size() + (size_t)4 * 4 * rp, 0.0);
   while (nkg % 3) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); ++nkg; }
   for (int k = 0; k < 8; ++k) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); }
-  out.def = def; out.nkg = nkg; out.n_ext = n_ext; out.ext_final = factor_of[groups.size()];
+  out.def = def; out.nkg = nkg; out.n_ext = n_ext; out.ext_final = base + nfac - 1;
   return true;
+}
+
+// ---- the half descriptor of a mirror-symmetric ROM (finrom_rom_set_mirror) -------------------------------------------------
+int validate_rom_mirror(const finrom_rom_desc* a, int n_full, const int32_t* row_node, const double* row_weight, const int32_t* theta_twin) {
+  if (!a || !row_node || !row_weight || !theta_twin) { set_error("rom_mirror: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  if (a->n > n_full) { set_error("rom_mirror: more half rows than rows"); return FINROM_ERR_ARG; }
+  for (int p = 0; p < a->P; ++p)
+    if (theta_twin[p] < 0 || theta_twin[p] >= a->P || theta_twin[theta_twin[p]] != p) { set_error("rom_mirror: theta_twin is not an involution"); return FINROM_ERR_ARG; }
+  std::vector<char> seen((size_t)n_full, 0);
+  int64_t covered = 0;
+  for (int i = 0; i < a->n; ++i) {
+    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
+    if (row_node[i] < 0 || row_node[i] >= n_full) { set_error("rom_mirror: row_node out of range"); return FINROM_ERR_ARG; }
+    if (seen[row_node[i]]) { set_error("rom_mirror: a row is listed twice"); return FINROM_ERR_ARG; }
+    seen[row_node[i]] = 1;
+    covered += row_weight[i] == 2.0 ? 2 : 1;
+  }
+  if (covered != n_full) { set_error("rom_mirror: the weights do not add up to the number of rows"); return FINROM_ERR_ARG; }
+  // only one parameter of a mirror pair may appear (the samples that walk this list carry the same value in both)
+  unsigned used = 0;
+  for (int t = 0; t < a->nterms; ++t) if (a->term_p[t] > 0) used |= 1u << (a->term_p[t] - 1);
+  for (int p = 0; p < a->P; ++p)
+    if (theta_twin[p] != p && (used & (1u << p)) && (used & (1u << theta_twin[p]))) { set_error("rom_mirror: both parameters of a mirror pair appear"); return FINROM_ERR_ARG; }
+  return 0;
+}
+
+// the half list's k-steps: rows that count twice and rows that count once never share a k-step
+std::vector<KStep> mirror_ksteps(const finrom_rom_desc* a, const double* row_weight, std::vector<int>& kclass) {
+  std::vector<KStep> ksteps;
+  kclass.clear();
+  const std::vector<int> order = rows_by_term_count(a);
+  for (int cls = 0; cls < 2; ++cls) {
+    std::vector<int> part;
+    for (int row : order) if ((row_weight[row] == 2.0) == (cls == 0)) part.push_back(row);
+    for (const KStep& ks : uniform_ksteps(a, part)) { ksteps.push_back(ks); kclass.push_back(cls); }
+  }
+  return ksteps;
 }
 }  // namespace
 
@@ -1280,6 +1334,30 @@ int finrom_rom_grouped_tables(const finrom_rom_desc* a, int32_t* nkg, int32_t* n
   const int NB = (a->r + 15) / 16, rp = 16 * NB;
   GroupedTables g;
   if (NB > 5 || !build_grouped_tables(a, uniform_ksteps(a, rows_by_term_count(a)), rp, g)) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
+  *nkg = g.nkg; *n_ext = g.n_ext; *ext_final = g.ext_final; *n_slots = (int64_t)(g.tvg.size() / ((size_t)4 * rp));
+  if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
+  if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
+  if (ext_def) std::memcpy(ext_def, g.def.data(), g.def.size() * sizeof(int));
+  return 0;
+}
+
+int finrom_rom_mirror_validate(const finrom_rom_desc* a, int32_t n_full, const int32_t* row_node, const double* row_weight,
+                               const int32_t* theta_twin) {
+  return validate_rom_mirror(a, n_full, row_node, row_weight, theta_twin);
+}
+
+// Host only: the half list finrom_rom_set_mirror builds from the half descriptor, as a list of its own (slots and scalars from 0).
+int finrom_rom_mirror_tables(const finrom_rom_desc* a, const double* row_weight, int32_t* nkg, int32_t* n_ext, int32_t* ext_final,
+                             int64_t* n_slots, int32_t* kmg, double* tvg, int32_t* ext_def) {
+  if (!a || !row_weight || !nkg || !n_ext || !ext_final || !n_slots) { set_error("rom_mirror_tables: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  for (int i = 0; i < a->n; ++i)
+    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
+  const int NB = (a->r + 15) / 16, rp = 16 * NB;
+  GroupedTables g;
+  std::vector<int> kclass;
+  const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
+  if (NB > 5 || !build_grouped_tables(a, ksteps, rp, g, &kclass)) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
   *nkg = g.nkg; *n_ext = g.n_ext; *ext_final = g.ext_final; *n_slots = (int64_t)(g.tvg.size() / ((size_t)4 * rp));
   if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
   if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
@@ -1365,10 +1443,12 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
 
     // ---- the same k-steps grouped by their leading parameter (build_grouped_tables above; proj_main_grouped, NB <= 5) ------
     d.n_ext = 0; d.nkg = 0; d.ext_final = 0; d.ext = nullptr;
+    d.nkg_m = 0; d.kmg_m = 0; d.ext_final_m = 0; d.twin = nullptr;
     if (NB <= 5 && getenv("FINROM_PROJ_UNGROUPED") == nullptr) {
       GroupedTables gt;
       if (build_grouped_tables(a, ksteps, rp, gt)) {
         d.nkg = gt.nkg; d.n_ext = gt.n_ext; d.ext_final = gt.ext_final;
+        h->tvg_host = gt.tvg; h->kmg_host = gt.kmg; h->def_host = gt.def;      // (finrom_rom_set_mirror appends the half list)
         d.tvg_bytes = (int)std::min<size_t>(gt.tvg.size() * sizeof(double), (size_t)0x7FFFFFF0);
         int grc = up(h->owned, &d.tvg, gt.tvg.data(), gt.tvg.size());
         if (!grc) grc = up(h->owned, &d.kmg, gt.kmg.data(), gt.kmg.size());
@@ -1414,6 +1494,41 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
   if (rc) { finrom_rom_destroy(h); return rc; }
   *out = h;
   return 0;
+}
+
+int finrom_rom_set_mirror(finrom_rom_t h, const finrom_rom_desc* a, const int32_t* row_node, const double* row_weight,
+                          const int32_t* theta_twin) {
+  if (!h || !a) { set_error("rom_set_mirror: null argument"); return FINROM_ERR_ARG; }
+  RomDev& d = h->d;
+  if (int rc = validate_rom_mirror(a, d.n, row_node, row_weight, theta_twin)) return rc;
+  if (a->r != d.r || a->P != d.P) { set_error("rom_set_mirror: basis size / parameter count differ from the handle's"); return FINROM_ERR_ARG; }
+  if (d.nkg_m > 0) { set_error("rom_set_mirror: already installed"); return FINROM_ERR_ARG; }
+  // the one-wave grouped kernel is the only form that walks the half list
+  if (d.NB > 5 || d.nkg == 0) { set_error("rom_set_mirror: the handle has no grouped form (r > 80, FINROM_PROJ_UNGROUPED, nothing to group)"); return FINROM_ERR_UNSUPPORTED; }
+  GroupedTables g;
+  std::vector<int> kclass;
+  const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
+  const int slot0 = (int)(h->tvg_host.size() / ((size_t)4 * d.rp));
+  if (!build_grouped_tables(a, ksteps, d.rp, g, &kclass, slot0, d.n_ext)) { set_error("rom_set_mirror: the half descriptor has no grouped form"); return FINROM_ERR_UNSUPPORTED; }
+  std::vector<double> tvg(h->tvg_host); tvg.insert(tvg.end(), g.tvg.begin(), g.tvg.end());
+  std::vector<int> kmg(h->kmg_host); kmg.insert(kmg.end(), g.kmg.begin(), g.kmg.end());
+  std::vector<int> def(h->def_host); def.insert(def.end(), g.def.begin(), g.def.end());
+  if (tvg.size() * sizeof(double) > (size_t)0x7FFFFFF0) { set_error("rom_set_mirror: tables too large"); return FINROM_ERR_UNSUPPORTED; }
+  RomDev nd = d;
+  int rc = up(h->owned, &nd.tvg, tvg.data(), tvg.size());
+  if (!rc) rc = up(h->owned, &nd.kmg, kmg.data(), kmg.size());
+  if (!rc) rc = up(h->owned, &nd.ext_def, def.data(), def.size());
+  if (!rc) rc = up(h->owned, &nd.twin, theta_twin, (size_t)d.P);
+  if (rc) return rc;                                     // (the handle keeps its tables; what was uploaded is freed with it)
+  nd.tvg_bytes = (int)(tvg.size() * sizeof(double));
+  nd.kmg_m = (int)h->kmg_host.size(); nd.nkg_m = g.nkg; nd.n_ext = g.n_ext; nd.ext_final_m = g.ext_final;
+  d = nd;
+  return 0;
+}
+
+int finrom_rom_last_form(finrom_rom_t h) {
+  if (!h) { set_error("rom_last_form: null handle"); return FINROM_ERR_ARG; }
+  return h->last_form;
 }
 
 void finrom_rom_destroy(finrom_rom_t h) {
@@ -1484,15 +1599,19 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
 }
 
 // A_r, B_r (or, with factor > 0, the factor / the solution) by the form of the reduced operator the handle is set to
+// (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
-                       double* w_r = nullptr, double* qoi_r = nullptr) {
+                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false) {
+  h->last_form = FINROM_ROM_FORM_FULL;
   if (h->projection == FINROM_PROJECTION_GRAM)
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
   RomDev d = h->d;
   d.ext = nullptr;
+  if (!mirror) d.nkg_m = 0;
   if (d.nkg > 0 && S > 0 && !rom_splitk_applies(d, S)) {      // the grouped main loop: room for the samples' scalars
     if (int rc = h->ext.reserve((size_t)S * d.n_ext * sizeof(double))) return rc;
     d.ext = (double*)h->ext.p;
+    if (d.nkg_m > 0) h->last_form = FINROM_ROM_FORM_HALF;
   }
   return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
 }
@@ -1513,6 +1632,7 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     // the MFMA-form factorisation + substitutions (rom_onesample.hip)
     if (A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
       if ((rc = h->part.reserve(rom_onesample_scratch_bytes(d, Sc)))) return rc;
+      h->last_form = FINROM_ROM_FORM_FULL;
       if ((rc = launch_rom_onesample(d, theta + s0 * d.P, Sc, (double*)h->part.p, 0, RomGradArgs(), w_r ? w_r + s0 * d.r : nullptr,
                                      qoi_r ? qoi_r + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st))) return rc;
       continue;
@@ -1532,7 +1652,7 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
         qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
-                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr))) return rc;
+                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true))) return rc;
     if (factor >= 2) continue;
     int factored = factor;
     if (want_factor && d.NB > 6) {                                     // wider bases: blocked MFMA Cholesky kernel

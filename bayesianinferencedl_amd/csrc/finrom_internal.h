@@ -161,8 +161,15 @@ struct RomDev {
   const int* kmg;                       // [(nkg + 8) * 8]
   int nkg;                              // multiple of 3; 0: no grouped form (nothing to group, too many parameters, NB > 5)
   int n_ext, ext_final;                 // per-sample scalars (<= 64); ext index of the factor behind the last k-step
-  const int* ext_def;                   // [n_ext * 3] ext[l] = (theta'[a] / theta'[b]) ^ (1 + sq), theta'[0] = 1
+  const int* ext_def;                   // [n_ext * 3] ext[l] = (theta'[a] / theta'[b]) ^ (1 + (f & 1)) * (f & 2 ? 2 : 1), theta'[0] = 1
   double* ext;                          // [S x n_ext] workspace of the CALL (set by rom_project; nullptr: the ungrouped loop)
+  // the HALF list of a mirror-symmetric ROM (finrom_rom_set_mirror, DESIGN 4b'): a second record list in the same format over the
+  // left and centre-line rows of the symmetrised basis.  Its records sit behind the full list's in kmg (kmg_m ints in), its rows
+  // behind the full table's in tvg, its factors behind the full list's in ext_def / the sample's row of ext; a sample whose
+  // parameters equal their twins' (twin, 0-based) walks it instead of the full list.
+  int nkg_m;                            // multiple of 3; 0: no half list (on this handle, or in this call)
+  int kmg_m, ext_final_m;
+  const int* twin;                      // [P]
   // rows with a non-zero load F (root nodes): slot-major padded r-vectors (4 per slot) with the theta index of each
   // (0 = the constant 1), a runtime term count
   int rhs_nk, rhs_nt;

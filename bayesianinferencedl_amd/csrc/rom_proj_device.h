@@ -322,7 +322,8 @@ __device__ __forceinline__ void mfma_fence(d4 (&acc)[N]) {      // VALU wrote th
 
 template <int NB>
 __device__ __forceinline__ void proj_main_grouped(const RomDev& p, const int* __restrict__ kmg_g, const double* __restrict__ ext_g,
-                                                  int q, int c, d4 (&acc)[NB * (NB + 1) / 2]) {
+                                                  int q, int c, d4 (&acc)[NB * (NB + 1) / 2], int nkg, int ext_final) {
+  // (nkg, ext_final: wave-uniform -- the full list's, or with kmg_g the half list's of a mirror-symmetric sample, see rom_proj_entry)
   constexpr int NTL = NB * (NB + 1) / 2;
   typedef const i4 __attribute__((address_space(4)))* c_i4_p;
   const c_i4_p kmg = (c_i4_p)(unsigned long long)kmg_g;
@@ -402,12 +403,12 @@ __device__ __forceinline__ void proj_main_grouped(const RomDev& p, const int* __
     f1 = f2; nt1 = m2[1]; fl1 = m2[2]; m2 = m3; k2 = k3;
   };
 #pragma unroll 1
-  for (int ks = 0; ks < p.nkg; ks += 3) {
+  for (int ks = 0; ks < nkg; ks += 3) {
     step(xa, xb, xc, ks);
     step(xb, xc, xa, ks + 1);
     step(xc, xa, xb, ks + 2);
   }
-  if (p.ext_final) rescale(ext_s[p.ext_final]);
+  if (ext_final) rescale(ext_s[ext_final]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1053,8 +1054,9 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
                                               double* __restrict__ qoi_r = nullptr, double* slab = nullptr,
                                               const double* __restrict__ theta_s = nullptr, const int* __restrict__ kpat = nullptr,
                                               int kpart = 0, int kparts = 1, const RomGradArgs* ga = nullptr, double* mt_lds = nullptr,
-                                              const double* __restrict__ ext_s = nullptr) {
+                                              const double* __restrict__ ext_s = nullptr, bool half = false) {
   // GR with ext_s: the grouped main loop -- kpat is then RomDev::kmg and ext_s the sample's row of RomDev::ext
+  // (half: kpat is the half list of a mirror-symmetric sample, RomDev::kmg + kmg_m)
   // kparts > 1 (NW == 1, small batches): the sample's k-steps are split over the kparts waves of the workgroup, the partial
   // block triangles are summed through LDS (`slab`) in a fixed order and wave 0 alone runs the epilogue
   constexpr int NTL = (NB * (NB + 1) / 2 + NW - 1) / NW;
@@ -1070,7 +1072,7 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
     proj_main_uniform_mw<NB, NW, W, HF>(p, kpat, theta_s, q, c, lane, slab, acc);
   } else {
     if constexpr (NW == 1 && GR) {
-      if (ext_s != nullptr) proj_main_grouped<NB>(p, kpat, ext_s, q, c, acc);
+      if (ext_s != nullptr) proj_main_grouped<NB>(p, kpat, ext_s, q, c, acc, half ? p.nkg_m : p.nkg, half ? p.ext_final_m : p.ext_final);
       else proj_main_uniform<NB>(p, p.ext != nullptr ? p.kmeta : kpat, theta_s, q, c, acc, p.nku);      // (kpat is RomDev::kmg when the launch is a grouped one)
     } else if constexpr (NW == 1) {
       const int per = ((p.nku + kparts - 1) / kparts + 1) / 2 * 2, k0 = kpart * per;
@@ -1307,6 +1309,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
   const double* theta_u = theta_s;
   if constexpr (NW == 1) {
     const double* ext_s = nullptr;
+    bool half = false;
     if constexpr (GR) {
       // (the grouped form divides by the conductivities: a sample with a zero, tiny (< 1e-60), huge (> 1e60) or non-finite one
       // takes the ungrouped loop -- same sums as a handle without the grouped tables)
@@ -1316,10 +1319,17 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
         const unsigned long long ea = (unsigned long long)(p.ext + ((int64_t)blockIdx.x * WPB + wave) * p.n_ext);
         ext_s = (const double*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ea >> 32)) << 32) |
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ea));
+        // a handle with the half list (finrom_rom_set_mirror): a sample whose every parameter equals its twin's to 1e-13 relative
+        // (the FOM's mirror test; the sub-fin averages of a mirrored field agree to 1.7e-15) walks it; NaN fails the test
+        if (p.nkg_m > 0) {
+          const double tt = __shfl(tl, lane < p.P ? p.twin[lane] : lane);
+          half = __ballot(!(__builtin_fabs(tl - tt) <= 1e-13 * __builtin_fmax(__builtin_fabs(tl), __builtin_fabs(tt)))) == 0;
+        }
       }
     }
-    rom_proj_body<NB, 1, 0, false, GR>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s, kpat, 0, 1, nullptr,
-                                       NB <= 5 ? mt_sw + wave * ROM_SW_LDS : nullptr, ext_s);
+    rom_proj_body<NB, 1, 0, false, GR>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
+                                       half ? kpat + __builtin_amdgcn_readfirstlane(p.kmg_m) : kpat, 0, 1, nullptr,
+                                       NB <= 5 ? mt_sw + wave * ROM_SW_LDS : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {
     switch (wave % 4) {
       case 0: rom_proj_body<NB, 4, 0, false, false, HF>(p, thw, s, lane, Ar, Br, factor, info, nullptr, qoi_r, slab, theta_u, kpat); break;

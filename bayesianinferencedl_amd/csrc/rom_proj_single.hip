@@ -19,7 +19,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(100))) void 
   rom_proj_entry<NB, 1, true>(p, theta, S, Ar, Br, factor, info, w_r, qoi_r, kpat);
 }
 
-// the samples' scalars for the grouped main loop (RomDev::ext_def): ext[s][l] = (theta'[a_l] / theta'[b_l]) ^ (1 + sq_l), theta'[0] = 1
+// the samples' scalars for the grouped main loop (RomDev::ext_def): ext[s][l] = (theta'[a_l] / theta'[b_l]) ^ (1 + (f_l & 1)), theta'[0] = 1,
+// times an exact 2 where f_l & 2 (the half list of a mirror-symmetric ROM: the left rows count twice)
 __global__ __launch_bounds__(256) void rom_ext_kernel(const double* __restrict__ theta, int P, int64_t S, const int* __restrict__ def,
                                                       int n_ext, double* __restrict__ ext) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -29,7 +30,9 @@ __global__ __launch_bounds__(256) void rom_ext_kernel(const double* __restrict__
   const int a = def[3 * l], b = def[3 * l + 1];
   const double num = a ? theta[s * P + a - 1] : 1.0, den = b ? theta[s * P + b - 1] : 1.0;
   double v = num / den;
-  if (def[3 * l + 2]) v *= v;
+  const int f = def[3 * l + 2];
+  if (f & 1) v *= v;
+  if (f & 2) v *= 2.0;
   ext[i] = v;
 }
 

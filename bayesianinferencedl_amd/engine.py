@@ -269,12 +269,14 @@ class FomEngine:
         self._enable_mirror(ops, c0_csr, W_csr, rhs, B_obs)
 
     @staticmethod
-    def mirror_rows(ops, c0_csr, W_csr, rhs, B_obs, tol=1e-13):
+    def mirror_rows(ops, c0_csr, W_csr, rhs, B_obs, tol=1e-13, col_twin=None):
         """Is this operator table mirror-symmetric about x = 3?  With P the mesh's mirror permutation (bandplan.mirror_permutation)
         and the pattern entry (a, b) mapped to (P a, P b): `c0`, every column of `W` (the PARAMETERS stay where they are: a nodal
         field or nine fin conductivities are not symmetric, the five-parameter lift is), `rhs`, and the rows of `B_obs`, each
         of which must map onto a row.  Tolerance `tol` relative to each table's largest magnitude; the tables of the lattice
         mesh are symmetric to 4.4e-15 in that measure (m = 12: c0 4.1e-15, W 2.0e-15, B_obs 4.4e-15, F exactly; m = 4, 8: <= 2e-16).
+        `col_twin` (the reduced model's test, RomEngine.set_mirror): column p of `W` must map onto column col_twin[p] instead --
+        parameters that mirror each other, for samples that carry the same value in both.
         -> twin[o] = the row that mirrors row o (twin[o] == o: a self-mirrored row), or None."""
         from .bandplan import mirror_permutation
         n = ops.n
@@ -296,7 +298,8 @@ class FomEngine:
         c0 = np.asarray(c0_csr, dtype=np.float64)
         W = sp.csr_matrix(W_csr)
         F = np.asarray(rhs, dtype=np.float64)
-        if not (same(c0, c0[pe]) and same(W, W[pe]) and same(F, F[P])):
+        Wm = W[pe] if col_twin is None else W[pe][:, np.asarray(col_twin)]
+        if not (same(c0, c0[pe]) and same(W, Wm) and same(F, F[P])):
             return None
         B = B_obs.toarray() if sp.issparse(B_obs) else np.asarray(B_obs, dtype=np.float64)
         Bm, scale = B[:, P], np.abs(B).max()
@@ -503,6 +506,96 @@ class RomEngine:
         h = C.c_void_p()
         check(lib().finrom_rom_create(C.byref(d), C.byref(h)), "finrom_rom_create")
         self._h = h
+        self.mirror_eps = None                            # set_mirror: the gate's measured value
+        self.mirror = False
+
+    # ---- the half form of a mirror-symmetric reduced model (DESIGN 4b', finrom_rom_set_mirror) ----------------------------------
+    MIRROR_EPS_GATE = 1e-9       # a hundredth of the rtol (1e-7) at which the tests equate the qoi_r of two projection forms
+    MIRROR_PROBES = 16
+
+    @staticmethod
+    def mirror_probe_eps(tables, perm, theta_twin, nprobe=16, seed=0, low=0.1, high=10.0):
+        """How far from mirror-symmetric is the basis, in the metric that matters?  tables[p] = A_p Phi (p = 0: the constant
+        term); with perm the mesh's mirror permutation and theta_twin the parameters' (0-based), A_p Phi_s = (tables[p] +
+        tables[twin p][perm]) / 2 and A_p Phi_a is the rest.  For mirror-symmetric theta psi^T psi = A_s + D with A_s = psi_s^T psi_s
+        and D = psi_a^T psi_a (the cross terms vanish); dropping D changes w_r by at most eps = lambda_max(D, A_s) relative in the
+        energy norm.  -> the largest eps over `nprobe` seeded probes, log-uniform over [low, high] per mirror pair."""
+        import scipy.linalg as sla
+        P = len(theta_twin)
+        tw1 = np.concatenate([[0], np.asarray(theta_twin) + 1])
+        Ts = [0.5 * (np.asarray(tables[p]) + np.asarray(tables[tw1[p]])[perm]) for p in range(P + 1)]
+        Ta = [np.asarray(tables[p]) - Ts[p] for p in range(P + 1)]
+        rng = np.random.default_rng(seed)
+        worst = 0.0
+        for _ in range(nprobe):
+            th = np.exp(rng.uniform(np.log(low), np.log(high), P))
+            th = th[np.minimum(np.arange(P), np.asarray(theta_twin))]          # the same value in both of a pair
+            th1 = np.concatenate([[1.0], th])
+            ps = sum(th1[p] * Ts[p] for p in range(P + 1)); pa = sum(th1[p] * Ta[p] for p in range(P + 1))
+            try:
+                L = np.linalg.cholesky(ps.T @ ps)
+            except np.linalg.LinAlgError:                   # psi_s alone is rank-deficient: nothing like a symmetric basis
+                return float("inf"), Ts
+            M = sla.solve_triangular(L, sla.solve_triangular(L, pa.T @ pa, lower=True).T, lower=True)
+            worst = max(worst, float(np.linalg.eigvalsh(0.5 * (M + M.T)).max()))
+        return worst, Ts
+
+    @staticmethod
+    def mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs):
+        """The half descriptor: rows `rows` (left of the symmetry line: weight 2, on it: weight 1) of the symmetrised tables Ts,
+        the two tables of a mirror pair merged under the smaller index (the samples that use it carry the same value in both);
+        rhs = weight F.  -> (finrom_rom_desc, the arrays it borrows, row_node, row_weight, theta_twin as ctypes pairs)."""
+        rows = np.asarray(rows, np.int64)
+        merged = []
+        for p in range(P + 1):
+            t = 0 if p == 0 else int(theta_twin[p - 1]) + 1
+            if t < p:
+                continue
+            M = Ts[p][rows] if t == p else Ts[p][rows] + Ts[t][rows]
+            merged.append((p, M))
+        row_ptr, term_p, tv = RomEngine.pack_terms(len(rows), r, merged)
+        keep = [i32(row_ptr), i32(term_p), f64(tv), f64(np.asarray(weight, float) * np.asarray(rhs, float)[rows]),
+                i32(rows), f64(weight), i32(theta_twin)]
+        d = RomDesc(n=len(rows), r=r, P=P, n_obs=0, nterms=len(term_p), row_ptr=keep[0][1], term_p=keep[1][1], term_val=keep[2][1],
+                    rhs=keep[3][1], obs_phi=None)
+        return d, keep
+
+    @staticmethod
+    def mirror_form(r, P, tables, rhs, perm, rows, weight, theta_twin):
+        """Host only.  The half form of one reduced model, gated: (b) r <= 80 (the grouped one-wave kernel), (c) the probes' eps at
+        most MIRROR_EPS_GATE, (d) FINROM_ROM_NO_MIRROR not set; (a), the operator's own symmetry, is the caller's test
+        (FomEngine.mirror_rows with col_twin).  -> dict(eps, installs, and when it installs: desc, keep) or None ((b) / (d))."""
+        if _os.environ.get("FINROM_ROM_NO_MIRROR") is not None or r > 80:
+            return None
+        eps, Ts = RomEngine.mirror_probe_eps(tables, perm, theta_twin, nprobe=RomEngine.MIRROR_PROBES)
+        form = {"eps": eps, "installs": bool(eps <= RomEngine.MIRROR_EPS_GATE), "Ts": Ts}
+        if form["installs"]:
+            form["desc"], form["keep"] = RomEngine.mirror_descriptor(np.asarray(perm).shape[0], r, P, Ts, rows, weight, theta_twin, rhs)
+        return form
+
+    def set_mirror(self, form):
+        """Install a form of mirror_form (finrom_rom_set_mirror); the measured eps stays on the engine (mirror_eps) either way.
+        -> installed?"""
+        if form is None:
+            return False
+        self.mirror_eps = form["eps"]
+        if not form["installs"]:
+            return False
+        keep = form["keep"]
+        rc = lib().finrom_rom_set_mirror(self._h, C.byref(form["desc"]), keep[4][1], keep[5][1], keep[6][1])
+        if rc == _ffi.ERR_UNSUPPORTED:                    # no grouped form on this handle
+            return False
+        check(rc, "finrom_rom_set_mirror")
+        self.mirror = True
+        return True
+
+    def last_form(self):
+        """'half' when the most recent projection launch of solve / solve_pairs offered its samples the half list (each sample
+        whose parameters equal their twins' walked it), 'full' otherwise, 'none' before the first call (finrom_rom_last_form)."""
+        rc = lib().finrom_rom_last_form(self._h)
+        if rc < 0:
+            check(rc, "finrom_rom_last_form")
+        return _ffi.ROM_FORMS[rc]
 
     def solve(self, theta, want_state=False, want_w=True):
         """want_w=False: only the reduced QoI comes back; bases wider than 96 then factor and solve inside the projection

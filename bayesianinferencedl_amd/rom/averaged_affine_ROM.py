@@ -60,6 +60,7 @@ class AffineROMFin:
         robin_phi = ops.csr(ops.robin_vals) @ self.phi
         terms = [(0, robin_phi)] + [(i + 1, self.dA_dsigmak_phi[i]) for i in range(9)]
         self._rom = RomEngine(self.n, self.n_r, 9, terms, ops.F, self.B_obs_phi)
+        self._enable_rom_mirror(ops, [robin_phi] + [self.dA_dsigmak_phi[i] for i in range(9)])
         self._avg = SubfinAverager(ops.S)
         self._plan = _plan_for(V)
         self._fom = None
@@ -68,6 +69,44 @@ class AffineROMFin:
         self.projection = "direct"
         self.set_projection(projection or os.environ.get("FINROM_PROJECTION", "direct"))
         self.set_dl_model(err_model)
+
+    @staticmethod
+    def mirror_form(ops, tables):
+        """Host only.  The half form of the projection (DESIGN 4b') for the tables A_p Phi of one basis (tables[0]: the Robin
+        term), or None: the affine operator must be mirror-symmetric about x = 3 with the sub-fins' twins (FomEngine.mirror_rows,
+        the FOM's 1e-13 test), r <= 80 and FINROM_ROM_NO_MIRROR unset; whether the basis is symmetric enough is the form's
+        `installs` (RomEngine.mirror_form: a basis from five-parameter snapshots is, one from nine-parameter snapshots is not)."""
+        from ..bandplan import mirror_permutation
+        r = np.asarray(tables[0]).shape[1]
+        if os.environ.get("FINROM_ROM_NO_MIRROR") is not None or r > 80:
+            return None
+        try:
+            perm = mirror_permutation(ops.mesh)
+        except (KeyError, AttributeError):
+            return None
+        S = ops.S.toarray() if sp.issparse(ops.S) else np.asarray(ops.S, dtype=np.float64)
+        twin = []
+        for o in range(S.shape[0]):                        # sub-fin o's averaging row, mirrored, is sub-fin twin[o]'s
+            hit = np.nonzero(np.abs(S - S[o][perm][None, :]).max(axis=1) <= 1e-13 * np.abs(S).max())[0]
+            if len(hit) != 1:
+                return None
+            twin.append(int(hit[0]))
+        rows_twin = FomEngine.mirror_rows(ops, ops.robin_vals, sp.csr_matrix(ops.sub_vals.T), ops.F, S, col_twin=twin)
+        if rows_twin is None or list(rows_twin) != twin:
+            return None
+        li, xc = ops.mesh.lattice[:, 0], 3 * ops.mesh.m
+        left, centre = np.nonzero(li < xc)[0], np.nonzero(li == xc)[0]
+        rows = np.concatenate([left, centre])
+        weight = np.concatenate([np.full(len(left), 2.0), np.ones(len(centre))])
+        form = RomEngine.mirror_form(r, len(twin), tables, ops.F, perm, rows, weight, np.asarray(twin, np.int32))
+        if form is not None:
+            form.update(perm=perm, rows=rows, weight=weight, twin=np.asarray(twin, np.int32))
+        return form
+
+    def _enable_rom_mirror(self, ops, tables):
+        """Samples whose nine averages mirror then walk the half list; every other sample keeps the full loop (decided per sample
+        in the kernel).  FINROM_ROM_NO_MIRROR=1 at creation switches the form off."""
+        self._rom.set_mirror(self.mirror_form(ops, tables))
 
     def set_projection(self, mode):
         """How the reduced operator is formed per sample.  'direct' (default): psi = A(theta) Phi, A_r = psi^T psi on the

@@ -342,6 +342,36 @@ void finrom_rom_destroy(finrom_rom_t h);
  * ext_final: the factor behind the last k-step.  nkg = 0: no grouped form for this descriptor. */
 int finrom_rom_grouped_tables(const finrom_rom_desc* desc, int32_t* nkg, int32_t* n_ext, int32_t* ext_final, int64_t* n_slots,
                               int32_t* kmg, double* tvg, int32_t* ext_def);
+/* The HALF form of a mirror-symmetric reduced model (DESIGN.md 4b'; additive, the reference has no counterpart: it contracts all
+ * rows of psi for every sample, rom/averaged_affine_ROM.py:291-297).  Where the affine operator commutes with the mesh's mirror
+ * permutation for parameters that equal their twins', and the basis is mirror-symmetric up to rounding, psi^T psi is twice the
+ * sum over the rows left of the symmetry line plus the sum over the rows on it.  `desc` is a second descriptor in the same
+ * format: its rows are those rows (row_node[i]: the handle's row that half row i stands for; row_weight[i]: 2 left of the line,
+ * 1 on it), its terms come from the symmetrised basis, and of two parameters that mirror each other (theta_twin [P], 0-based,
+ * an involution) only one appears.  finrom_rom_solve and the ROM half of finrom_solve_pairs then walk this list instead of the
+ * full one for every sample whose parameters equal their twins' to 1e-13 relative (decided per sample, inside the kernel; any
+ * other sample runs exactly what it ran before); B_r, B_obs Phi, gradients, the small-batch kernels and the offline/online form
+ * keep the handle's own tables.  Whether the basis is symmetric ENOUGH is the caller's decision (engine.py: RomEngine.set_mirror's
+ * gate).  FINROM_ERR_UNSUPPORTED when the handle has no grouped one-wave form (r > 80): nothing changes then. */
+int finrom_rom_set_mirror(finrom_rom_t h, const finrom_rom_desc* desc, const int32_t* row_node, const double* row_weight,
+                          const int32_t* theta_twin);
+/* Its checks, host only (n_full: the rows of the full descriptor): finrom_rom_create's for `desc`, weights 1 or 2 that add up to
+ * n_full, no row listed twice, theta_twin an involution, one parameter of a mirror pair at most. */
+int finrom_rom_mirror_validate(const finrom_rom_desc* desc, int32_t n_full, const int32_t* row_node, const double* row_weight,
+                               const int32_t* theta_twin);
+/* HOST ONLY: the half list as finrom_rom_set_mirror builds it, in the format of finrom_rom_grouped_tables (slots and scalars
+ * counted from 0 here; on the handle they sit behind the full list's).  Rows of weight 2 and rows of weight 1 never share a
+ * k-step; all k-steps of weight 2 come first, and the factor that follows them carries an exact 2: ext_def's third column is
+ * a flag word, bit 0 = squared, bit 1 = times two. */
+int finrom_rom_mirror_tables(const finrom_rom_desc* desc, const double* row_weight, int32_t* nkg, int32_t* n_ext, int32_t* ext_final,
+                             int64_t* n_slots, int32_t* kmg, double* tvg, int32_t* ext_def);
+/* Which list the most recent projection launch of finrom_rom_solve / finrom_solve_pairs on this handle OFFERED its samples
+ * (tests assert on it, like finrom_fom_last_path): FINROM_ROM_FORM_HALF = the launch carried the half list and every sample that
+ * passed the per-sample mirror test walked it; FINROM_ROM_FORM_FULL = every sample ran the handle's own tables. */
+#define FINROM_ROM_FORM_NONE 0
+#define FINROM_ROM_FORM_FULL 1
+#define FINROM_ROM_FORM_HALF 2
+int finrom_rom_last_form(finrom_rom_t h);
 /* theta [S x P] -> w_r [S x r] (NULL to skip), qoi_r [S x n_obs], info [S] (NULL ok);
  * optional A_r [S x r x r] and B_r [S x r] (the state the reference keeps in
  * self._A_r / self._B_r for its gradients, :296-297) -- NULL to skip. */
