@@ -179,6 +179,7 @@ SIGNATURES = {
                                                    C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
+    "finrom_hmc_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_lbfgs_begin": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_propose": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_accept": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -23,7 +23,14 @@ gathered.
 `metric=LowRankMetric` (laplace.py) on the three chain functions: a constant mass matrix M = I + V diag(lambda) V^T, the
 Gauss-Newton Hessian of the potential at the MAP point (the `scaling` the reference's sampler hands to NUTS, bayesian_inference/
 inference.py:102-140,165).  The random stream is the same: the standard normals xi become momenta p = M^(1/2) xi, the position
-moves by eps M^-1 p and the kinetic energy is p^T M^-1 p / 2 (= |xi|^2 / 2 at the start).  metric=None: every path and bit as before."""
+moves by eps M^-1 p and the kinetic energy is p^T M^-1 p / 2 (= |xi|^2 / 2 at the start).  metric=None: every path and bit as before.
+
+`rng="philox"` on the three chain functions: the momenta and the Metropolis uniforms come from a counter-based stream (philox.py;
+on the device finrom_hmc_draw, one launch per block of proposals, no host draw and no upload) instead of one NumPy generator per
+chain.  The draw of proposal p of the chain with seed s depends on (s, p) alone, so a chain is the same for any `block`, any deal
+of the chains over ranks, and a run of p1 proposals followed by a run from its end state (K; V under a prior) with proposal0=p1
+and an explicit mean= (the first run's; under a prior the prior carries it) walks the path of one uninterrupted run.
+rng="numpy" (the default): every path and bit as before; a NumPy generator cannot be advanced to a proposal, so proposal0 must be 0."""
 from __future__ import annotations
 
 import numpy as np
@@ -58,6 +65,34 @@ def _check_prior(prior, mean, who):
         raise ValueError(f"{who}: with a prior the chains start from whitened points and the field's mean is the prior's (mean=None)")
 
 
+def _check_rng(rng, seeds, proposal0, who):
+    """rng="numpy": None.  rng="philox": the seeds as a uint64 array (ValueError for one outside [0, 2^64))."""
+    if rng == "numpy":
+        if proposal0 != 0:
+            raise ValueError(f"{who}: proposal0 = {proposal0} needs rng='philox' (a NumPy generator cannot be advanced to a proposal)")
+        return None
+    if rng != "philox":
+        raise ValueError(f"{who}: rng must be 'numpy' or 'philox', not {rng!r}")
+    from . import philox
+    if int(proposal0) != proposal0 or not 0 <= proposal0 < 1 << 62:
+        raise ValueError(f"{who}: rng='philox': proposal0 = {proposal0} is not an index in [0, 2^62)")
+    return philox.check_seeds(seeds)
+
+
+def _device_draw(seeds64, dev):
+    """draw(first, nb, P_dev, lu_dev): one finrom_hmc_draw launch on the current stream -- the draws of proposals first .. first + nb - 1
+    of every chain into the head of the block buffers.  The seeds sit in an int64 tensor that holds the uint64 bit patterns."""
+    import torch
+    from .. import _ffi
+    L = _ffi.lib()
+    seeds_t = torch.as_tensor(seeds64.view(np.int64), dtype=torch.int64, device=dev)
+
+    def draw(first, nb, P_dev, lu_dev):
+        _ffi.check(L.finrom_hmc_draw(seeds_t.data_ptr(), seeds_t.numel(), P_dev.shape[2], first, nb, P_dev.data_ptr(), lu_dev.data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream), "finrom_hmc_draw")
+    return draw
+
+
 def _check_metric(metric, n):
     """A rank-zero metric is the identity: the plain paths, bit for bit."""
     if metric is None or metric.rho == 0:
@@ -68,7 +103,7 @@ def _check_metric(metric, n):
 
 
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False, prior=None, metric=None):
+               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
@@ -78,9 +113,15 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     start points v (prior.whiten of a field), mean must be None (the prior carries it) and tau is unused; value_and_grad still
     receives fields, and `recorded` still holds (field, loss, field gradient).
     metric: None (identity mass) or a LowRankMetric in the chain's own coordinates (with a prior: the whitened ones).
+    rng: "numpy" -- chain c draws from np.random.default_rng(seeds[c]): n normals for the momentum, then one uniform, per proposal;
+    "philox" -- proposal i of this call takes philox.draw_block's draw of GLOBAL proposal proposal0 + i for seed seeds[c] (Philox4x32-10,
+    key = seed, counter = (proposal, pair index, 0) for the Box-Muller pairs of the momentum and (proposal, 0, 1) for the uniform;
+    seeds in [0, 2^64)).  Continuation: a run of p1 proposals, then a run from its end state (K, or V under a prior) with
+    proposal0=p1 and the first run's mean passed explicitly, is the uninterrupted run.  proposal0 != 0 needs rng="philox".
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
     trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
     with a prior also V [C, n], the whitened final states)."""
+    seeds64 = _check_rng(rng, seeds, proposal0, "run_chains")
     _check_prior(prior, mean, "run_chains")
     metric = _check_metric(metric, np.shape(K0)[-1])
     K = np.array(K0, dtype=np.float64, copy=True)
@@ -94,8 +135,12 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             return U, dU, Kq, loss, grad, bad
     else:
         pot = whitened_potential(value_and_grad, prior, sigma)
-    rngs = [np.random.default_rng(s) for s in seeds]
-    assert len(rngs) == C
+    if seeds64 is None:
+        rngs = [np.random.default_rng(s) for s in seeds]
+        assert len(rngs) == C
+    else:
+        from . import philox
+        assert len(seeds64) == C
     recorded = []
     evals = 0
 
@@ -117,7 +162,11 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     accept = np.zeros(C, np.int64)
     proposals = 0
     while evals + n_leapfrog <= n_evals:
-        P = np.stack([r.standard_normal(n) for r in rngs])
+        if seeds64 is None:
+            P = np.stack([r.standard_normal(n) for r in rngs])
+        else:
+            Pb, lub = philox.draw_block(seeds64, proposal0 + proposals, 1, n)
+            P = Pb[0]
         H0 = U + 0.5 * np.einsum("cn,cn->c", P, P)                  # (under a metric: |xi|^2 / 2 = p^T M^-1 p / 2)
         if metric is not None:
             P = metric.apply(P, "sqrt")
@@ -128,9 +177,9 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             Uq, dUq = evaluate(Kq)
             Pq = Pq - 0.5 * eps * dUq
         H1 = Uq + 0.5 * np.einsum("cn,cn->c", Pq, Pq if metric is None else metric.apply(Pq, "inv"))
-        u = np.array([r.uniform() for r in rngs])
         with np.errstate(over="ignore", invalid="ignore"):
-            ok = np.isfinite(H1) & (np.log(u) < H0 - H1)
+            lu = np.log(np.array([r.uniform() for r in rngs])) if seeds64 is None else lub[0]
+            ok = np.isfinite(H1) & (lu < H0 - H1)
         K = np.where(ok[:, None], Kq, K); U = np.where(ok, Uq, U); dU = np.where(ok[:, None], dUq, dU)
         accept += ok
         proposals += 1
@@ -152,7 +201,7 @@ def romml_value_and_grad(solver_r):
 
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None):
+                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -164,7 +213,11 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     finrom_hmc_leapfrog_field: field kernel, the plain finrom_romml_grad launches at the field, pullback kernel with the momentum
     update; finrom_hmc_begin / _end unchanged (mean 0, c_pri 1).  The trace is mapped to fields after the run.
     metric: a LowRankMetric in the whitened coordinates (needs prior=; FINROM_ERR_UNSUPPORTED otherwise, so that fused=None falls
-    back): finrom_hmc_begin_metric, finrom_hmc_leapfrog_field_metric (one launch more per step: the velocity M^-1 p), _end_metric."""
+    back): finrom_hmc_begin_metric, finrom_hmc_leapfrog_field_metric (one launch more per step: the velocity M^-1 p), _end_metric.
+    rng, proposal0: as for run_chains.  Under "philox" nothing is drawn on the host or uploaded: one finrom_hmc_draw launch per block,
+    in stream order between two blocks' replays, writes the draws of proposals proposal0 + done .. into the block buffers the
+    graph reads (standard normals, also under a metric); the chain does not depend on `block`."""
+    seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
     import ctypes as C
     import torch
     from .. import _ffi
@@ -195,8 +248,12 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     data_np = np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64)
     data_t = torch.as_tensor(data_np, **f64)
     per_sample = 1 if data_np.ndim == 2 else 0
-    rngs = [np.random.default_rng(s) for s in seeds]
-    assert len(rngs) == Cn
+    if seeds64 is None:
+        rngs = [np.random.default_rng(s) for s in seeds]
+        assert len(rngs) == Cn
+    else:
+        assert len(seeds64) == Cn
+        draw = _device_draw(seeds64, dev)
     c_lik, c_pri = 1.0 / sigma ** 2, 1.0 / tau ** 2
     n_prop = max(0, (n_evals - 1) // n_leapfrog)
     B = max(1, min(block, n_prop))
@@ -292,13 +349,16 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     done = 0
     while done < n_prop:
         nb = min(B, n_prop - done)
-        P_host, lu_host = np.zeros((B, Cn, n)), np.zeros((B, Cn))
-        for j in range(nb):                                         # the host chain's draws, in its order
-            for c_, r in enumerate(rngs):
-                P_host[j, c_] = r.standard_normal(n)
-            with np.errstate(divide="ignore"):
-                lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-        P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
+        if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
+            draw(proposal0 + done, nb, P_dev, lu_dev)
+        else:
+            P_host, lu_host = np.zeros((B, Cn, n)), np.zeros((B, Cn))
+            for j in range(nb):                                     # the host chain's draws, in its order
+                for c_, r in enumerate(rngs):
+                    P_host[j, c_] = r.standard_normal(n)
+                with np.errstate(divide="ignore"):
+                    lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
+            P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
         jt.zero_()
         for j in range(nb):
             first = 1 + (done + j) * n_leapfrog
@@ -326,7 +386,8 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                      keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None):
+                      keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
+                      proposal0=0):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -346,8 +407,12 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     whitened end states.
     metric: a LowRankMetric in the chain's own coordinates (run_chains); its maps are finrom_metric_apply launches on the static
     tensors (engine.MetricHandle), fused: run_chains_fused's kernels (needs prior=).
-    Same chains as run_chains(romml_value_and_grad(solver_r), ...) up to the rounding of the elementwise updates.
+    rng, proposal0: as for run_chains (the same stream, the same continuation rule).  Under "philox" the host loop and the two uploads
+    per block are one finrom_hmc_draw launch per block, with first_proposal = proposal0 + the proposals done; the chain is then the
+    same for any `block`.
+    Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
+    seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
@@ -357,7 +422,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior, metric=metric)
+                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -373,8 +438,12 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     else:
         mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
     data_t = torch.as_tensor(np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64), **f64)
-    rngs = [np.random.default_rng(s) for s in seeds]
-    assert len(rngs) == C
+    if seeds64 is None:
+        rngs = [np.random.default_rng(s) for s in seeds]
+        assert len(rngs) == C
+    else:
+        assert len(seeds64) == C
+        draw = _device_draw(seeds64, dev)
     c_lik, c_pri = 1.0 / sigma ** 2, 1.0 / tau ** 2
     mh = metric.device() if metric is not None else None
     n_prop = max(0, (n_evals - 1) // n_leapfrog)
@@ -473,13 +542,16 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     done = 0
     while done < n_prop:
         nb = min(B, n_prop - done)
-        P_host, lu_host = np.zeros((B, C, n)), np.zeros((B, C))
-        for j in range(nb):                                         # the host chain's draws, in its order (overlaps the device's
-            for c_, r in enumerate(rngs):                           #  work on the previous block: nothing here waits for it)
-                P_host[j, c_] = r.standard_normal(n)
-            with np.errstate(divide="ignore"):
-                lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-        P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
+        if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
+            draw(proposal0 + done, nb, P_dev, lu_dev)
+        else:
+            P_host, lu_host = np.zeros((B, C, n)), np.zeros((B, C))
+            for j in range(nb):                                     # the host chain's draws, in its order (overlaps the device's
+                for c_, r in enumerate(rngs):                       #  work on the previous block: nothing here waits for it)
+                    P_host[j, c_] = r.standard_normal(n)
+                with np.errstate(divide="ignore"):
+                    lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
+            P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
         jt.zero_()
         for j in range(nb):
             first = 1 + (done + j) * n_leapfrog                     # evaluation indices of this proposal: first .. first + L - 1

@@ -150,6 +150,7 @@ int launch_subfin_avg(const double*, int, int, const double*, int64_t, double*, 
 int launch_sampler(const double*, int, const double*, int64_t, double*, hipStream_t);
 int launch_sub(const double*, const double*, int64_t, double*, hipStream_t);
 int launch_philox_normal(unsigned long long, int64_t, int64_t, int, double*, hipStream_t);
+int launch_hmc_draw(const unsigned long long*, int64_t, int, int64_t, int64_t, double*, double*, hipStream_t);
 
 }  // namespace finrom
 
@@ -2109,6 +2110,20 @@ int finrom_hmc_end(const finrom_hmc_state* a, int32_t n_steps, void* stream) {
   if (int rc = hmc_dev(a, &h, "hmc_end")) return rc;
   if (n_steps < 0) { set_error("hmc_end: n_steps < 0"); return FINROM_ERR_ARG; }
   return launch_hmc_end(h, a->Kq[n_steps & 1], (hipStream_t)stream);       // (the position ping-pongs once per step)
+}
+int finrom_hmc_draw(const uint64_t* seeds, int64_t C, int32_t n, int64_t first_proposal, int64_t B, double* P_block, double* lu_block,
+                    void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (C < 0) { set_error("hmc_draw: C < 0"); return FINROM_ERR_ARG; }
+  if (B < 0) { set_error("hmc_draw: B < 0"); return FINROM_ERR_ARG; }
+  if (first_proposal < 0) { set_error("hmc_draw: first_proposal < 0"); return FINROM_ERR_ARG; }
+  if (n < 1) { set_error("hmc_draw: n < 1"); return FINROM_ERR_ARG; }
+  if (B == 0 || C == 0) return 0;
+  if (!seeds || !P_block || !lu_block) { set_error("hmc_draw: null seeds, P_block or lu_block"); return FINROM_ERR_ARG; }
+  if (B > INT64_MAX / C || B * C > INT64_MAX / 8 / n || first_proposal > INT64_MAX - B) {
+    set_error("hmc_draw: B x C x n or first_proposal + B does not fit 64 bits"); return FINROM_ERR_ARG;
+  }
+  return launch_hmc_draw((const unsigned long long*)seeds, C, n, first_proposal, B, P_block, lu_block, (hipStream_t)stream);
 }
 int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const finrom_hmc_state* a, int32_t step,
                         const double* data, int32_t data_per_sample, double* grad_out, double* qoi_r, double* e_nn, void* stream) {

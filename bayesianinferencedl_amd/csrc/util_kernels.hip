@@ -448,6 +448,50 @@ int launch_philox_normal(unsigned long long seed, int64_t first, int64_t S, int 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// The draws of a block of B HMC proposals for C chains (hmc.py rng="philox"): row j * C + c of P_block holds the standard normals
+// of proposal first + j of the chain with seed seeds[c] -- row 0 of philox_normal_kernel(seed, first + j, 1, n), the same words
+// through the same arithmetic -- and lu_block its log-uniform from counter (proposal lo, hi, 0, 1): u = ((o1 o0 >> 11) + 1) 2^-53
+// in (0, 1], so log u is finite and <= 0.  A draw depends on (seed, proposal index) alone: any block size, any deal of the chains
+// over ranks and a run continued at a proposal index walk the same chain.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hmc_draw_kernel(const unsigned long long* __restrict__ seeds, int64_t C, int n, int64_t first,
+                                                       int64_t B, double* __restrict__ P_block, double* __restrict__ lu_block) {
+  const int npair = (n + 1) / 2;
+  const int64_t total = B * C * npair;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / npair;                                 // j * C + c
+    const int jb = (int)(i - row * npair);
+    const int64_t j = row / C;
+    const unsigned long long seed = seeds[row - j * C], g = (unsigned long long)(first + j);
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    unsigned o[4];
+    philox4x32_10((unsigned)g, (unsigned)(g >> 32), (unsigned)jb, 0u, k0, k1, o);
+    const unsigned long long a = ((unsigned long long)o[1] << 32) | o[0], b = ((unsigned long long)o[3] << 32) | o[2];
+    const double u1 = (double)((a >> 11) + 1) * 0x1.0p-53;       // (0, 1]
+    const double u2 = (double)(b >> 11) * 0x1.0p-53;             // [0, 1)
+    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+    P_block[row * n + 2 * jb] = rad * cos(ang);
+    if (2 * jb + 1 < n) P_block[row * n + 2 * jb + 1] = rad * sin(ang);
+    if (jb == 0) {                                                 // the row's Metropolis uniform
+      philox4x32_10((unsigned)g, (unsigned)(g >> 32), 0u, 1u, k0, k1, o);
+      const unsigned long long m = ((unsigned long long)o[1] << 32) | o[0];
+      lu_block[row] = log((double)((m >> 11) + 1) * 0x1.0p-53);
+    }
+  }
+}
+
+int launch_hmc_draw(const unsigned long long* seeds, int64_t C, int n, int64_t first, int64_t B, double* P_block, double* lu_block,
+                    hipStream_t st) {
+  if (B == 0 || C == 0) return 0;
+  ScopedKernelTimer t(K_MISC, st);
+  const int64_t total = B * C * ((n + 1) / 2);
+  const int64_t blocks = std::min<int64_t>((total + 255) / 256, 16384);
+  hipLaunchKernelGGL(hmc_draw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seeds, C, n, first, B, P_block, lu_block);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
 __global__ void sub_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t count,
                            double* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)

@@ -521,6 +521,19 @@ int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const d
                                      int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
                                      finrom_metric_t metric, double* vel, void* stream);
 int finrom_hmc_end_metric(const finrom_hmc_state* st, finrom_metric_t metric, int32_t n_steps, void* stream);
+/* The draws of a block of B proposals ON THE DEVICE (hmc.py rng="philox"), in the layout finrom_hmc_begin / _begin_metric read: row
+ * j * C + c of P_block [B x C x n] and of lu_block [B x C] belongs to proposal first_proposal + j of the chain with seed seeds[c]
+ * (seeds [C]: DEVICE array).  For seed s and global proposal index p, Philox4x32-10 with key (s lo, s hi):
+ *   momentum     counter (p lo, p hi, pair index jb, 0): words (o1 o0) and (o3 o2) give 53-bit uniforms u1 in (0, 1], u2 in [0, 1),
+ *                Box-Muller makes xi[2 jb], xi[2 jb + 1] -- row 0 of finrom_sampler_draw_seeded's xi for (seed s, sample p, S = 1);
+ *                standard normals also under a metric (finrom_hmc_begin_metric forms p = M^(1/2) xi);
+ *   log-uniform  counter (p lo, p hi, 0, 1): a = (o1 << 32) | o0, u = ((a >> 11) + 1) 2^-53 in (0, 1], lu = log u, finite and <= 0.
+ * A draw depends on (s, p) and on nothing else: the same chain for any block size B, any deal of the chains over ranks, and for a
+ * run continued from its end state with first_proposal = the proposals already made.  One launch on `stream`, one thread per
+ * Box-Muller pair, no allocation: legal while the stream is capturing.  Checks before any device call (FINROM_ERR_ARG, with a
+ * message): C, B or first_proposal negative, n < 1, a null pointer with B x C > 0.  B == 0 or C == 0: returns 0, no launch. */
+int finrom_hmc_draw(const uint64_t* seeds, int64_t C, int32_t n, int64_t first_proposal, int64_t B, double* P_block, double* lu_block,
+                    void* stream);
 
 /* ---- batched multi-start MAP estimation: a projected L-BFGS on the device ------------------------------------------------------- *
  * The reference minimises 0.5 |y(k) - d|^2 + reg(k) with SciPy's L-BFGS-B, one start after another (bayesian_inference/
