@@ -83,6 +83,14 @@ class HmcState(C.Structure):
                 ("accept", C.c_void_p), ("trace", C.c_void_p), ("loss", C.c_void_p), ("info", C.c_void_p)]
 
 
+class HmcStats(C.Structure):
+    _fields_ = [("C", C.c_int64), ("n", C.c_int32), ("proposal0", C.c_int64), ("burn", C.c_int64), ("batch", C.c_int64),
+                ("pt", C.c_void_p), ("accept", C.c_void_p), ("cand", C.c_void_p), ("cand_loss", C.c_void_p),
+                ("cur", C.c_void_p), ("cur_loss", C.c_void_p), ("acc_prev", C.c_void_p),
+                ("mean", C.c_void_p), ("m2", C.c_void_p), ("bsum", C.c_void_p), ("bm_mean", C.c_void_p), ("bm_m2", C.c_void_p),
+                ("misfit", C.c_void_p), ("accepted", C.c_void_p)]
+
+
 class LbfgsState(C.Structure):
     _fields_ = [("S", C.c_int64), ("d", C.c_int32), ("m", C.c_int32), ("ftol", C.c_double), ("gtol", C.c_double),
                 ("maxiter", C.c_int64), ("maxfun", C.c_int64), ("maxls", C.c_int32), ("lo", C.c_void_p), ("hi", C.c_void_p),
@@ -180,6 +188,7 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
     "finrom_hmc_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_stats_update": (C.c_int, [C.POINTER(HmcStats), C.c_void_p]),
     "finrom_lbfgs_begin": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_propose": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_accept": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

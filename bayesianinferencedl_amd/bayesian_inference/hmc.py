@@ -30,7 +30,20 @@ on the device finrom_hmc_draw, one launch per block of proposals, no host draw a
 chain.  The draw of proposal p of the chain with seed s depends on (s, p) alone, so a chain is the same for any `block`, any deal
 of the chains over ranks, and a run of p1 proposals followed by a run from its end state (K; V under a prior) with proposal0=p1
 and an explicit mean= (the first run's; under a prior the prior carries it) walks the path of one uninterrupted run.
-rng="numpy" (the default): every path and bit as before; a NumPy generator cannot be advanced to a proposal, so proposal0 must be 0."""
+rng="numpy" (the default): every path and bit as before; a NumPy generator cannot be advanced to a proposal, so proposal0 must be 0.
+
+`stats=ChainStats(burn, batch)` on the three chain functions: what the reference's drivers take from the trace after the run
+(bayesian_inference/inference.py:175-214 `np.mean(trace, 0)`, `np.std(trace, 0)`, the misfit per draw; pymc_func_bayes_inverse.py:
+212-220) accumulated WHILE the chains run, so that no trace is kept: per chain and node the Welford mean and sum of squared
+deviations of the FIELD (under a prior the field, not the whitened state: its variance needs Cov(v) in full) and the Welford moments
+of the means of batches of `batch` consecutive draws, per chain the misfit and the accept flag after every proposal.  On the device
+that is one launch per proposal (finrom_hmc_stats_update, behind the Metropolis test, inside the replayed graph); ChainStats.update
+is the same recursion in NumPy, operation for operation, and the device's sums are its bits.  `res.stats.summarize()` forms the
+pooled mean, standard deviation, R-hat, batch-means effective sample size and Monte-Carlo standard error on the host.  Draws are the
+states after the proposals with GLOBAL index >= burn; everything is indexed by the global proposal index, so the sums do not depend
+on `block`, on graph or stream order, or on where a run was interrupted: `stats=ChainStats(resume=first.stats)` with the
+continuation rule above (rng="philox", proposal0 = the proposals already made) continues every sum.  stats=None: every path and bit
+as before, no launch and no buffer more."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,6 +51,235 @@ import numpy as np
 
 class HmcResult(dict):
     __getattr__ = dict.__getitem__
+
+
+class ChainStats:
+    """Streaming posterior summaries of C chains in lockstep: the specification handed to a chain function (`stats=ChainStats(burn,
+    batch)` or `ChainStats(resume=earlier.stats)`) and, started, the result `res.stats`.
+
+    burn: draws are the states after the proposals with GLOBAL index >= burn (a rejected proposal repeats the state: a draw as well).
+    batch: length of the batches whose means give the effective sample size (>= 1); a trailing partial batch stays in `bsum`.
+    resume: the `stats` of the run this one continues (its burn and batch are taken over; the run must start at proposal0 =
+    resume.next, the existing continuation rule).
+    A started ChainStats holds, per chain and node [C, n]: mean, m2 (sum of squared deviations from the mean), bsum (sum of the open
+    batch), bm_mean, bm_m2 (the same two moments of the closed batches' means), cur (field of the current state); per chain [C]:
+    cur_loss; per proposal [proposals + 1, C] (row 0: the start point): misfit, accepted (int32 0 / 1); and first, next (global index
+    of the first proposal covered, of the next one), t (draws) and n_batches (closed batches).  After a device run also `chain`:
+    the end state with its potential and gradient, from which a run given resume= restarts to the bit (_restore_chain)."""
+    SUMS = ("mean", "m2", "bsum", "bm_mean", "bm_m2")
+
+    def __init__(self, burn=0, batch=32, resume=None):
+        if resume is not None:
+            if not isinstance(resume, ChainStats) or not resume.started:
+                raise ValueError("ChainStats: resume= takes the stats a run returned")
+            if (burn, batch) not in ((0, 32), (resume.burn, resume.batch)):
+                raise ValueError(f"ChainStats: burn = {burn}, batch = {batch} differ from the resumed run's {resume.burn}, {resume.batch}")
+            burn, batch = resume.burn, resume.batch
+        if int(burn) != burn or burn < 0:
+            raise ValueError(f"ChainStats: burn = {burn} is not a proposal index >= 0")
+        if int(batch) != batch or batch < 1:
+            raise ValueError(f"ChainStats: batch = {batch} is not a length >= 1")
+        self.burn, self.batch, self.resume = int(burn), int(batch), resume
+        self.first = self.next = None
+        self.chain = None                                            # device runs: (state, U, dU) at the end, see _restore_chain
+
+    started = property(lambda self: self.next is not None)
+    t = property(lambda self: max(0, self.next - self.burn))
+    n_batches = property(lambda self: self.t // self.batch)
+    C = property(lambda self: self.mean.shape[0])
+
+    def begin(self, field0, loss0, proposal0, proposals=0):
+        """-> a started ChainStats for a run from the start point (field0 [C, n], loss0 [C]) whose first proposal has global index
+        proposal0: zero sums, or a copy of resume's (then the current field and misfit are resume's too: the same state by the
+        continuation rule, refused if field0 is not within 1e-9 of it).  proposals: rows of misfit / accepted to allocate ahead (they grow as needed)."""
+        field0, loss0 = np.array(field0, dtype=np.float64, ndmin=2), np.array(loss0, dtype=np.float64, ndmin=1)
+        C, r = field0.shape[0], self.resume
+        loss0 = np.broadcast_to(loss0, (C,)).copy()
+        s = ChainStats(self.burn, self.batch)
+        if r is None:
+            if proposal0 > self.burn:
+                raise ValueError(f"ChainStats: proposal0 = {proposal0} > burn = {self.burn}: the draws of proposals {self.burn} .. "
+                                 f"{proposal0 - 1} are not at hand (pass resume=, or a burn >= proposal0)")
+            s.first = int(proposal0)
+            for name in self.SUMS:
+                setattr(s, name, np.zeros_like(field0))
+            s.misfit, s.accepted = loss0[None].copy(), np.zeros((1, C), np.int32)
+        else:
+            if proposal0 != r.next:
+                raise ValueError(f"ChainStats: the resumed run ended before proposal {r.next}; this one starts at proposal0 = {proposal0}")
+            if r.mean.shape != field0.shape:
+                raise ValueError(f"ChainStats: the resumed run had chains x nodes = {r.mean.shape}, this one {field0.shape}")
+            s.first = r.first
+            for name in self.SUMS:
+                setattr(s, name, getattr(r, name).copy())
+            s.misfit, s.accepted = r.misfit[:r._row + 1].copy(), r.accepted[:r._row + 1].copy()
+            if not np.allclose(field0, r.cur, rtol=1e-9, atol=1e-9 * np.max(np.abs(r.cur))):
+                raise ValueError("ChainStats: this run does not start from the resumed run's end state")
+            field0, loss0 = r.cur.copy(), r.cur_loss.copy()          # the state the sums have seen, to the bit
+        s._row = len(s.misfit) - 1
+        s.misfit = np.concatenate([s.misfit, np.full((proposals, C), np.nan)])
+        s.accepted = np.concatenate([s.accepted, np.zeros((proposals, C), np.int32)])
+        s.next, s.cur, s.cur_loss = int(proposal0), field0, loss0
+        return s
+
+    def update(self, field, loss, ok, g):
+        """The state after the proposal with global index g: field [C, n] and loss [C] at the trajectory's end point, ok [C] whether
+        the chain accepted it.  The NumPy statement of finrom_hmc_stats_update's kernel: the same operations in the same order (no
+        fused multiply-add on either side), so that the device's sums are these bits."""
+        if g != self.next:
+            raise ValueError(f"ChainStats.update: proposal {g} after proposal {self.next - 1}")
+        ok = np.asarray(ok, dtype=bool)
+        self.cur = np.where(ok[:, None], field, self.cur)
+        self.cur_loss = np.where(ok, loss, self.cur_loss)
+        self._row += 1
+        if self._row == len(self.misfit):
+            self.misfit = np.concatenate([self.misfit, self.cur_loss[None]])
+            self.accepted = np.concatenate([self.accepted, np.zeros((1, len(ok)), np.int32)])
+        self.misfit[self._row], self.accepted[self._row] = self.cur_loss, ok
+        self.next = g + 1
+        if g < self.burn:
+            return
+        t, x = g - self.burn + 1, self.cur
+        d = x - self.mean
+        self.mean = self.mean + d / float(t)
+        self.m2 = self.m2 + d * (x - self.mean)
+        self.bsum = self.bsum + x
+        if t % self.batch == 0:
+            b, bm = t // self.batch, self.bsum / float(self.batch)
+            d = bm - self.bm_mean
+            self.bm_mean = self.bm_mean + d / float(b)
+            self.bm_m2 = self.bm_m2 + d * (bm - self.bm_mean)
+            self.bsum = np.zeros_like(self.bsum)
+
+    def select(self, chains):
+        """The started stats of the listed chains, in that order."""
+        s = ChainStats(self.burn, self.batch)
+        s.first, s.next, s._row = self.first, self.next, self._row
+        for name in self.SUMS + ("cur", "cur_loss"):
+            setattr(s, name, getattr(self, name)[chains].copy())
+        s.misfit, s.accepted = self.misfit[:, chains].copy(), self.accepted[:, chains].copy()
+        return s
+
+    @staticmethod
+    def concat(parts):
+        """The per-rank results of chains dealt over ranks, joined along the chain axis in the order given."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, ChainStats) and p.started for p in parts):
+            raise ValueError("ChainStats.concat: needs the stats of finished runs")
+        a = parts[0]
+        for p in parts[1:]:
+            if (p.t, p.burn, p.batch) != (a.t, a.burn, a.batch) or (p.first, p.next) != (a.first, a.next):
+                raise ValueError(f"ChainStats.concat: (t, burn, batch, first, next) = {(p.t, p.burn, p.batch, p.first, p.next)} "
+                                 f"against {(a.t, a.burn, a.batch, a.first, a.next)}")
+            if p.mean.shape[1] != a.mean.shape[1]:
+                raise ValueError("ChainStats.concat: different numbers of nodes")
+        s = ChainStats(a.burn, a.batch)
+        s.first, s.next, s._row = a.first, a.next, a._row
+        for name in a.SUMS + ("cur", "cur_loss"):
+            setattr(s, name, np.concatenate([getattr(p, name) for p in parts], axis=0))
+        rows = a._row + 1
+        s.misfit = np.concatenate([p.misfit[:rows] for p in parts], axis=1)
+        s.accepted = np.concatenate([p.accepted[:rows] for p in parts], axis=1)
+        return s
+
+    def summarize(self):
+        """Pooled over the chains, each [n]: mean, std (sqrt of var+), rhat (Gelman-Rubin, not split), ess (batch means) and mcse
+        (Monte-Carlo standard error of `mean`):
+          W = mean_c(m2 / (t - 1)),  B = t var_c(mean, ddof=1),  var+ = (t - 1) / t W + B / t,  rhat = sqrt(var+ / W),
+          s^2 = batch mean_c(bm_m2 / (n_batches - 1)),  ess = C t W / s^2,  mcse = sqrt(s^2 / (C t)).
+        One chain: rhat is NaN and var+ = (t - 1) / t W."""
+        if not self.started or self.t < 2 or self.n_batches < 2:
+            raise ValueError(f"ChainStats.summarize: needs >= 2 draws and >= 2 closed batches of {self.batch} "
+                             f"(draws: {self.t if self.started else 0})")
+        t, nb, C = self.t, self.n_batches, self.C
+        W = np.mean(self.m2 / (t - 1), axis=0)
+        Bv = t * np.var(self.mean, axis=0, ddof=1) if C > 1 else np.zeros_like(W)
+        varp = (t - 1) / t * W + Bv / t
+        s2 = self.batch * np.mean(self.bm_m2 / (nb - 1), axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rhat = np.sqrt(varp / W) if C > 1 else np.full_like(W, np.nan)
+            ess = C * t * W / s2
+        return HmcResult(mean=np.mean(self.mean, axis=0), std=np.sqrt(varp), rhat=rhat, ess=ess, mcse=np.sqrt(s2 / (C * t)))
+
+
+def stats_from_trace(trace, burn, batch, proposal0=0, resume=None, loss=None):
+    """ChainStats.update run over a kept trace of FIELDS [P + 1, C, n]: row 0 is the start point, row j + 1 the state after the
+    proposal with global index proposal0 + j.  loss [P + 1, C] (optional) fills `misfit` (NaN otherwise); `accepted` is whether the
+    row differs from the one before (an accepted proposal moves every node)."""
+    trace = np.asarray(trace, dtype=np.float64)
+    P, C = trace.shape[0] - 1, trace.shape[1]
+    loss = np.full((P + 1, C), np.nan) if loss is None else np.asarray(loss, dtype=np.float64)
+    s = ChainStats(burn, batch, resume=resume).begin(trace[0], loss[0], proposal0, P)
+    for j in range(P):
+        s.update(trace[j + 1], loss[j + 1], np.any(trace[j + 1] != trace[j], axis=1), proposal0 + j)
+    return s
+
+
+def _restore_chain(stats, K, U, dU):
+    """A device run given stats=ChainStats(resume=r) that starts from r's end state, to the bit, takes that state's potential U and
+    gradient dU from r.chain in place of evaluation 0's.  The fused step forms the sub-fin averages of a trajectory's first point
+    directly and those of the later ones from the previous momentum update's partial sums, so evaluation 0 of a continued run
+    rounds differently from the evaluation that produced the state inside the first run (the continued chain then agrees with the
+    uninterrupted one to 1e-9, tests/test_gpu_hmc_rng.py, not to the bit); with the saved values the continued run is the
+    uninterrupted one bit for bit, and so are its sums."""
+    import torch
+    r = stats.resume if stats is not None else None
+    if r is None or r.chain is None:
+        return
+    K0, U0, dU0 = r.chain
+    if K0.shape == tuple(K.shape) and np.array_equal(K0, K.cpu().numpy()):
+        U.copy_(torch.as_tensor(U0, dtype=U.dtype, device=U.device))
+        dU.copy_(torch.as_tensor(dU0, dtype=dU.dtype, device=dU.device))
+
+
+class _DeviceStats:
+    """The buffers of finrom_hmc_stats_update as torch tensors on `dev`, started from the start point's field and misfit (device
+    tensors [C, n], [C]); pt, acc: the chain state's counters (device tensors, acc at its start value)."""
+
+    def __init__(self, spec, field0, loss0, proposal0, n_prop, pt, acc):
+        import torch
+        from .. import _ffi
+        self._ffi, self._L, self.n_prop = _ffi, _ffi.lib(), n_prop
+        self.host = spec.begin(field0.cpu().numpy(), loss0.cpu().numpy(), proposal0, n_prop)
+        dev, h = field0.device, self.host
+        Cn, n = field0.shape
+        self.cur, self.cur_loss = (torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous() for a in (h.cur, h.cur_loss))
+        self.acc_prev = torch.stack([acc, acc]).contiguous()
+        self.sums = [torch.as_tensor(getattr(h, name), dtype=torch.float64, device=dev).contiguous() for name in h.SUMS]
+        self.misfit = torch.full((n_prop + 1, Cn), float("nan"), dtype=torch.float64, device=dev)
+        self.misfit[0].copy_(self.cur_loss)
+        self.accepted = torch.zeros(n_prop + 1, Cn, dtype=torch.int32, device=dev)
+        self.desc = _ffi.HmcStats(C=Cn, n=n, proposal0=proposal0, burn=h.burn, batch=h.batch, pt=pt.data_ptr(), accept=acc.data_ptr(),
+                                  cur=self.cur.data_ptr(), cur_loss=self.cur_loss.data_ptr(), acc_prev=self.acc_prev.data_ptr(),
+                                  misfit=self.misfit.data_ptr(), accepted=self.accepted.data_ptr(),
+                                  **{name: t.data_ptr() for name, t in zip(h.SUMS, self.sums)})
+
+    def buffers(self):
+        """Everything the launch writes: saved before a warm-up proposal and restored after the capture, with the chain state."""
+        return [self.cur, self.cur_loss, self.acc_prev, self.misfit, self.accepted] + self.sums
+
+    def update(self, cand, cand_loss):
+        """One launch on torch's current stream: cand [C, n], cand_loss [C] (contiguous float64 device tensors) at the end point."""
+        import ctypes as C
+        import torch
+        assert cand.is_contiguous() and cand.dtype == torch.float64 and cand.shape == self.cur.shape and cand_loss.dtype == torch.float64
+        self.desc.cand, self.desc.cand_loss = cand.data_ptr(), cand_loss.data_ptr()
+        self._ffi.check(self._L.finrom_hmc_stats_update(C.byref(self.desc), torch.cuda.current_stream().cuda_stream),
+                        "finrom_hmc_stats_update")
+
+    def result(self, K, U, dU):
+        """The started host ChainStats with the device's sums and the chain's end state K, U, dU (synchronises)."""
+        h = self.host
+        h.chain = (K.cpu().numpy(), U.cpu().numpy(), dU.cpu().numpy())
+        for name, t in zip(h.SUMS, self.sums):
+            setattr(h, name, t.cpu().numpy())
+        h.cur, h.cur_loss = self.cur.cpu().numpy(), self.cur_loss.cpu().numpy()
+        if self.n_prop:
+            h.misfit[h._row + 1:] = self.misfit[1:].cpu().numpy()
+            h.accepted[h._row + 1:] = self.accepted[1:].cpu().numpy()
+        h._row += self.n_prop
+        h.next += self.n_prop
+        return h
 
 
 def potential(loss, grad, K, mean, sigma, tau):
@@ -103,7 +345,7 @@ def _check_metric(metric, n):
 
 
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0):
+               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
@@ -118,6 +360,8 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     key = seed, counter = (proposal, pair index, 0) for the Box-Muller pairs of the momentum and (proposal, 0, 1) for the uniform;
     seeds in [0, 2^64)).  Continuation: a run of p1 proposals, then a run from its end state (K, or V under a prior) with
     proposal0=p1 and the first run's mean passed explicitly, is the uninterrupted run.  proposal0 != 0 needs rng="philox".
+    stats: None or a ChainStats (module docstring): `stats` of the result is then the started ChainStats of this run -- the moments
+    of the chains' FIELDS after every proposal with global index >= burn, misfit and accept flag per proposal.
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
     trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
     with a prior also V [C, n], the whitened final states)."""
@@ -143,10 +387,12 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         assert len(seeds64) == C
     recorded = []
     evals = 0
+    last = {}                                                        # field and misfit of the last evaluation (stats=)
 
     def evaluate(Kq):
         nonlocal evals
         U, dU, Fq, loss, grad, bad = pot(Kq)
+        last["field"], last["loss"] = Fq, loss
         if record is not None and evals in record:
             recorded.append((evals, Fq.copy(), np.array(loss, copy=True), np.array(grad, copy=True)))
         evals += 1
@@ -161,6 +407,7 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     trace = [K.copy()] if keep_trace else None
     accept = np.zeros(C, np.int64)
     proposals = 0
+    cs = None if stats is None else stats.begin(last["field"], last["loss"], proposal0, max(0, (n_evals - 1) // n_leapfrog))
     while evals + n_leapfrog <= n_evals:
         if seeds64 is None:
             P = np.stack([r.standard_normal(n) for r in rngs])
@@ -182,14 +429,16 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             ok = np.isfinite(H1) & (lu < H0 - H1)
         K = np.where(ok[:, None], Kq, K); U = np.where(ok, Uq, U); dU = np.where(ok[:, None], dUq, dU)
         accept += ok
+        if cs is not None:                                           # (the last evaluation was the end point's)
+            cs.update(last["field"], np.asarray(last["loss"], dtype=np.float64), ok, proposal0 + proposals)
         proposals += 1
         if keep_trace:
             trace.append(K.copy())
     if prior is not None:                                            # the states are v: report fields, and v beside them
         return HmcResult(K=prior.field(K), V=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
-                         trace=prior.field(np.stack(trace)) if keep_trace else None)
+                         trace=prior.field(np.stack(trace)) if keep_trace else None, stats=cs)
     return HmcResult(K=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
-                     trace=np.stack(trace) if keep_trace else None)
+                     trace=np.stack(trace) if keep_trace else None, stats=cs)
 
 
 def romml_value_and_grad(solver_r):
@@ -201,7 +450,8 @@ def romml_value_and_grad(solver_r):
 
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0):
+                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
+                     stats=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -216,7 +466,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     back): finrom_hmc_begin_metric, finrom_hmc_leapfrog_field_metric (one launch more per step: the velocity M^-1 p), _end_metric.
     rng, proposal0: as for run_chains.  Under "philox" nothing is drawn on the host or uploaded: one finrom_hmc_draw launch per block,
     in stream order between two blocks' replays, writes the draws of proposals proposal0 + done .. into the block buffers the
-    graph reads (standard normals, also under a metric); the chain does not depend on `block`."""
+    graph reads (standard normals, also under a metric); the chain does not depend on `block`.
+    stats: a ChainStats -- one finrom_hmc_stats_update launch behind finrom_hmc_end / _end_metric in every proposal (captured with
+    it), on the step's field buffer under a prior and on the end point's position buffer otherwise: no triangular product more."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
     import ctypes as C
     import torch
@@ -318,6 +570,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             _ffi.check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
         else:
             _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
+        if ds is not None:                                           # (F holds the field of the trajectory's last step: the end point's)
+            ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss)
 
     # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
     Kq[0].copy_(K)
@@ -331,9 +585,12 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     dU.copy_(dUq)
     if trace is not None:
         trace[0].copy_(K)
+    _restore_chain(stats, K, U, dU)
+    ds = None if stats is None else _DeviceStats(stats, F if prior is not None else K, loss, proposal0, n_prop, pt, acc)
     g = None
     if graph and n_prop > 0:
-        state = [t.clone() for t in (K, U, dU, acc, jt, pt)]
+        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else [])
+        state = [t.clone() for t in moved]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                               # warm-up on a side stream, as torch's graph recipe asks
@@ -342,7 +599,7 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             proposal()
-        for t, t0 in zip((K, U, dU, acc, jt, pt), state):           # (the warm-up moved the state; the capture does not run)
+        for t, t0 in zip(moved, state):                             # (the warm-up moved the state; the capture does not run)
             t.copy_(t0)
         if trace is not None:
             trace[1].zero_()
@@ -369,10 +626,11 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                 g.replay() if g is not None else proposal()
                 evals += n_leapfrog
         done += nb
+    cs = ds.result(K, U, dU) if ds is not None else None
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs)
 
 
 def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
@@ -387,7 +645,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0):
+                      proposal0=0, stats=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -410,6 +668,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     rng, proposal0: as for run_chains (the same stream, the same continuation rule).  Under "philox" the host loop and the two uploads
     per block are one finrom_hmc_draw launch per block, with first_proposal = proposal0 + the proposals done; the chain is then the
     same for any `block`.
+    stats: a ChainStats -- one finrom_hmc_stats_update launch behind the state update of every proposal (captured with it), on the
+    last evaluation's field under a prior and on Kq otherwise; `stats` of the result as for run_chains, the device's sums.
     Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
@@ -422,7 +682,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0)
+                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -509,6 +769,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         jt.add_(1); pt.add_(1)
         if trace is not None:
             trace.index_copy_(0, pt, K[None])
+        if ds is not None:                                          # (out holds the last evaluation: the end point's)
+            ds.update(out["field"], out["loss"])
 
     Kq.copy_(K); Pq.zero_()
     evaluate()                                                      # evaluation 0: the starting point (also warms the library up)
@@ -519,9 +781,12 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     dU.copy_(dUq)
     if trace is not None:
         trace[0].copy_(K)
+    _restore_chain(stats, K, U, dU)
+    ds = None if stats is None else _DeviceStats(stats, out["field"], out["loss"], proposal0, n_prop, pt, acc)
     g = None
     if graph and n_prop > 0:
-        state = [t.clone() for t in (K, U, dU, acc, jt, pt)]
+        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else [])
+        state = [t.clone() for t in moved]
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -531,13 +796,13 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 proposal()
-            for t, t0 in zip((K, U, dU, acc, jt, pt), state):       # (the warm-up moved the state; the capture does not run)
+            for t, t0 in zip(moved, state):                         # (the warm-up moved the state; the capture does not run)
                 t.copy_(t0)
         except Exception as exc:                                    # no graph support for this sequence: plain stream order
             import warnings
             warnings.warn(f"hmc: HIP graph capture failed ({exc!r}); the proposals are launched kernel by kernel")
             g = None
-            for t, t0 in zip((K, U, dU, acc, jt, pt), state):
+            for t, t0 in zip(moved, state):
                 t.copy_(t0)
     done = 0
     while done < n_prop:
@@ -562,7 +827,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
                 g.replay() if g is not None else proposal()
                 evals += n_leapfrog
         done += nb
+    cs = ds.result(K, U, dU) if ds is not None else None
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs)

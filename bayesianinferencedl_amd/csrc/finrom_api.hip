@@ -2125,6 +2125,22 @@ int finrom_hmc_draw(const uint64_t* seeds, int64_t C, int32_t n, int64_t first_p
   }
   return launch_hmc_draw((const unsigned long long*)seeds, C, n, first_proposal, B, P_block, lu_block, (hipStream_t)stream);
 }
+int finrom_hmc_stats_update(const finrom_hmc_stats* s, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (!s) { set_error("hmc_stats_update: null descriptor"); return FINROM_ERR_ARG; }
+  if (s->C < 0) { set_error("hmc_stats_update: C < 0"); return FINROM_ERR_ARG; }
+  if (s->n < 1) { set_error("hmc_stats_update: n < 1"); return FINROM_ERR_ARG; }
+  if (s->batch < 1) { set_error("hmc_stats_update: batch < 1"); return FINROM_ERR_ARG; }
+  if (s->burn < 0) { set_error("hmc_stats_update: burn < 0"); return FINROM_ERR_ARG; }
+  if (s->proposal0 < 0) { set_error("hmc_stats_update: proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (s->C == 0) return 0;
+  if (s->C > 65535) { set_error("hmc_stats_update: C > 65535 (one grid row per chain)"); return FINROM_ERR_ARG; }
+  if (!s->pt || !s->accept || !s->cand || !s->cand_loss || !s->cur || !s->cur_loss || !s->acc_prev || !s->mean || !s->m2 ||
+      !s->bsum || !s->bm_mean || !s->bm_m2) {
+    set_error("hmc_stats_update: null pointer in finrom_hmc_stats (only misfit and accepted may be NULL)"); return FINROM_ERR_ARG;
+  }
+  return launch_hmc_stats(*s, (hipStream_t)stream);
+}
 int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const finrom_hmc_state* a, int32_t step,
                         const double* data, int32_t data_per_sample, double* grad_out, double* qoi_r, double* e_nn, void* stream) {
   CallGuard cg((hipStream_t)stream);

@@ -94,6 +94,7 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 };
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
+int launch_hmc_stats(const finrom_hmc_stats& s, hipStream_t st);      // hmc_stats.hip (the descriptor holds device pointers only)
 
 // ---- low-rank metric M = I + V diag(lambda) V^T (hmc_metric.hip, finrom_metric_*, finrom_hmc_*_metric) -----------------------
 constexpr int METRIC_MAX_RHO = 64;

@@ -534,6 +534,38 @@ int finrom_hmc_end_metric(const finrom_hmc_state* st, finrom_metric_t metric, in
  * message): C, B or first_proposal negative, n < 1, a null pointer with B x C > 0.  B == 0 or C == 0: returns 0, no launch. */
 int finrom_hmc_draw(const uint64_t* seeds, int64_t C, int32_t n, int64_t first_proposal, int64_t B, double* P_block, double* lu_block,
                     void* stream);
+/* The chains' posterior summaries accumulated ON THE DEVICE (hmc.py stats=): one launch behind finrom_hmc_end / _end_metric (or the
+ * caller's own state update), grid (ceil(n / 256), C), one thread per (chain, node), no workspace and no allocation: legal while
+ * the stream is capturing.  What the reference's drivers take from a kept trace after the run (bayesian_inference/inference.py:
+ * 175-214: np.mean / np.std of the trace, the misfit per draw), without the trace.  With q = *pt >= 1 the proposals done in this
+ * call (this one included) and g = proposal0 + q - 1 the proposal's global index:
+ *   accepted   chain c was accepted iff accept[c] != acc_prev[(q - 1) & 1][c]; the chain's first workgroup alone writes accept[c]
+ *              into slot q & 1 (the caller fills slot 0 with the counters before the first proposal);
+ *   state      accepted: cur[c, :] = cand[c, :], cur_loss[c] = cand_loss[c];  misfit[q, c] = cur_loss[c], accepted[q, c] = the flag;
+ *   draws      g >= burn: t = g - burn + 1, x = cur[c, i]:
+ *                d = x - mean;  mean = mean + d / t;  m2 = m2 + d * (x - mean);  bsum = bsum + x;
+ *                t % batch == 0:  b = t / batch, bm = bsum / batch,
+ *                                 d = bm - bm_mean;  bm_mean = bm_mean + d / b;  bm_m2 = bm_m2 + d * (bm - bm_mean);  bsum = 0.
+ * No fused multiply-add, IEEE division, t and b converted exactly: the sums are the bits of hmc.ChainStats.update (NumPy), whatever
+ * the cut into blocks, graph or stream order, or the point at which a run was interrupted and continued (everything is indexed
+ * by g; the caller hands the sums of the first run to the second).  The statistics are of FIELDS: under the latent Gaussian-field
+ * prior `cand` is the step's field buffer, not the whitened state (the variance of a field needs Cov(v) in full).
+ * Checks before any device call (FINROM_ERR_ARG, with a message): C, burn or proposal0 negative, n < 1, batch < 1, C > 65535, a
+ * null pointer other than misfit / accepted with C > 0.  C == 0: returns 0, no launch. */
+typedef struct {
+  int64_t C; int32_t n;
+  int64_t proposal0;            /* global index of this call's first proposal */
+  int64_t burn, batch;          /* draws are the states after proposals with global index >= burn; batch length >= 1 */
+  const int64_t* pt;            /* the chain state's counter, already advanced by finrom_hmc_end */
+  const int64_t* accept;        /* [C] the chain state's accept counters */
+  const double* cand;           /* [C x n] FIELD at the end point of the proposal just tested */
+  const double* cand_loss;      /* [C] misfit there */
+  double* cur; double* cur_loss;/* [C x n], [C]: field and misfit of the CURRENT state (caller fills them for the start point) */
+  int64_t* acc_prev;            /* [2 x C] ping-pong copy of accept */
+  double *mean, *m2, *bsum, *bm_mean, *bm_m2;   /* [C x n] each */
+  double* misfit; int32_t* accepted;            /* [(proposals + 1) x C] or NULL; row 0 is the start */
+} finrom_hmc_stats;
+int finrom_hmc_stats_update(const finrom_hmc_stats* s, void* stream);
 
 /* ---- batched multi-start MAP estimation: a projected L-BFGS on the device ------------------------------------------------------- *
  * The reference minimises 0.5 |y(k) - d|^2 + reg(k) with SciPy's L-BFGS-B, one start after another (bayesian_inference/
