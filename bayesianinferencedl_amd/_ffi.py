@@ -153,6 +153,7 @@ SIGNATURES = {
     "finrom_rom_mirror_validate": (C.c_int, [C.POINTER(RomDesc), C.c_int32, c_i32p, c_f64p, c_i32p]),
     "finrom_rom_mirror_tables": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, c_f64p, c_i32p]),
     "finrom_rom_last_form": (C.c_int, [C.c_void_p]),
+    "finrom_rom_last_epilogue": (C.c_int, [C.c_void_p]),
     "finrom_rom_destroy": (None, [C.c_void_p]),
     "finrom_rom_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -219,6 +220,8 @@ FOM_PATHS = {0: "none", 1: "small_lds", 2: "small_global", 3: "interpreter", 4: 
              7: "band_registers_qoi", 8: "band_lds_4wave_qoi"}
 # finrom_rom_last_form codes (include/finrom.h)
 ROM_FORMS = {0: "none", 1: "full", 2: "half"}
+# finrom_rom_last_epilogue codes (include/finrom.h)
+ROM_EPILOGUES = {0: "none", 1: "standard", 2: "roomy"}
 
 _lib = None
 

@@ -149,6 +149,7 @@ static void drain_pending() {
 int launch_subfin_avg(const double*, int, int, const double*, int64_t, double*, hipStream_t);
 int launch_sampler(const double*, int, const double*, int64_t, double*, hipStream_t);
 int launch_sub(const double*, const double*, int64_t, double*, hipStream_t);
+int launch_sub_flagged(const double*, double*, const int*, int, int64_t, double*, hipStream_t);
 int launch_philox_normal(unsigned long long, int64_t, int64_t, int, double*, hipStream_t);
 int launch_hmc_draw(const unsigned long long*, int64_t, int, int64_t, int64_t, double*, double*, hipStream_t);
 
@@ -179,6 +180,8 @@ struct finrom_rom_s {
   int projection = FINROM_PROJECTION_DIRECT;
   std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
   int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
+  int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
+  bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
   hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's
@@ -1532,6 +1535,11 @@ int finrom_rom_last_form(finrom_rom_t h) {
   return h->last_form;
 }
 
+int finrom_rom_last_epilogue(finrom_rom_t h) {
+  if (!h) { set_error("rom_last_epilogue: null handle"); return FINROM_ERR_ARG; }
+  return h->last_epilogue;
+}
+
 void finrom_rom_destroy(finrom_rom_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);
@@ -1602,23 +1610,27 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
 // A_r, B_r (or, with factor > 0, the factor / the solution) by the form of the reduced operator the handle is set to
 // (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
-                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false) {
+                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false) {
   h->last_form = FINROM_ROM_FORM_FULL;
+  roomy = roomy && h->projection == FINROM_PROJECTION_DIRECT && rom_roomy_applies(h->d, factor, w_r, qoi_r);
+  h->last_epilogue = roomy ? FINROM_ROM_EPILOGUE_ROOMY : FINROM_ROM_EPILOGUE_STANDARD;
   if (h->projection == FINROM_PROJECTION_GRAM)
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
   RomDev d = h->d;
   d.ext = nullptr;
   if (!mirror) d.nkg_m = 0;
-  if (d.nkg > 0 && S > 0 && !rom_splitk_applies(d, S)) {      // the grouped main loop: room for the samples' scalars
+  if (d.nkg > 0 && S > 0 && (roomy || !rom_splitk_applies(d, S))) {      // the grouped main loop: room for the samples' scalars
     if (int rc = h->ext.reserve((size_t)S * d.n_ext * sizeof(double))) return rc;
     d.ext = (double*)h->ext.p;
     if (d.nkg_m > 0) h->last_form = FINROM_ROM_FORM_HALF;
   }
-  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
+  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy);
 }
 
-int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
-                     double* B_r, int32_t* info, void* stream) {
+// roomy: finrom_solve_pairs beside the FOM's half sweep -- QoI-only calls at r <= 80 then take the 256-register one-wave kernel at
+// every batch size (rom_roomy_applies); finrom_rom_solve itself never does
+static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
+                          double* B_r, int32_t* info, void* stream, bool roomy) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!theta || (!qoi_r && h->d.n_obs > 0)))) { set_error("rom_solve: bad argument"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
@@ -1631,7 +1643,9 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     int rc;
     // one-sample call patterns (MAP / HMC: a handful of samples, latency): contraction over several workgroups per sample, then
     // the MFMA-form factorisation + substitutions (rom_onesample.hip)
-    if (A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
+    const bool rm = roomy && A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_roomy_applies(d, 2, w_r, qoi_r);
+    if (!rm && A_r == nullptr && B_r == nullptr && h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
+      h->last_epilogue = FINROM_ROM_EPILOGUE_STANDARD;
       if ((rc = h->part.reserve(rom_onesample_scratch_bytes(d, Sc)))) return rc;
       h->last_form = FINROM_ROM_FORM_FULL;
       if ((rc = launch_rom_onesample(d, theta + s0 * d.P, Sc, (double*)h->part.p, 0, RomGradArgs(), w_r ? w_r + s0 * d.r : nullptr,
@@ -1653,7 +1667,7 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
         qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
-                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true))) return rc;
+                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm))) return rc;
     if (factor >= 2) continue;
     int factored = factor;
     if (want_factor && d.NB > 6) {                                     // wider bases: blocked MFMA Cholesky kernel
@@ -1665,6 +1679,11 @@ int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r
                                B_r ? B_r + s0 * d.r : nullptr, info ? info + s0 : nullptr, factored, st))) return rc;
   }
   return 0;
+}
+
+int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
+                     double* B_r, int32_t* info, void* stream) {
+  return rom_solve_impl(h, theta, S, w_r, qoi_r, A_r, B_r, info, stream, false);
 }
 
 int finrom_rom_set_gradient(finrom_rom_t h, int32_t npairs, const int32_t* pair_p, const int32_t* pair_i, const double* G) {
@@ -1883,7 +1902,10 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
     FR_HIP(hipStreamWaitEvent(side, rom->ev_fork, 0));
     if (fst != st) FR_HIP(hipStreamWaitEvent(fst, rom->ev_fork, 0));
   }
-  if ((rc = finrom_rom_solve(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst))) return fail(rc);
+  // Beside the HALF sweep (154 registers, 11.8 KB of LDS per wave) a QoI-only projection at r <= 80 takes the roomy one-wave kernel:
+  // 256 + 154 registers still share a SIMD.  The choice depends on the two handles and on what the caller wants back, never on
+  // batch size, stream or mask.  FINROM_PROJ_NO_ROOMY=1 at handle creation: the 200-register kernel, as everywhere else.
+  if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy))) return fail(rc);
   // With a masked FOM stream only the SWEEP runs on it: pack + assembly go to an unmasked stream (they take 0.1 ms there against
   // 2.0 ms on 96 CUs beside the projection's start, and since the grouped projection loop the FOM half is the one that ends
   // last: step 20.46 -> 20.26 ms).  FINROM_FOM_PREPASS_MASKED=1: the whole FOM half on the masked stream, as before.
@@ -1893,7 +1915,11 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
     if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 2))) return fail(rc);
   } else if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 3))) return fail(rc);
   join();
-  if (err && (rc = launch_sub(qoi, qoi_r, S * (int64_t)fom->d.n_obs, err, st))) return rc;
+  // a roomy call returns a sample that either half flagged as NaN in qoi_r and err (launch_sub_flagged); every other call keeps
+  // what its kernels wrote
+  if (rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY && info != nullptr) {
+    if ((rc = launch_sub_flagged(qoi, qoi_r, info, fom->d.n_obs, S * (int64_t)fom->d.n_obs, err, st))) return rc;
+  } else if (err && (rc = launch_sub(qoi, qoi_r, S * (int64_t)fom->d.n_obs, err, st))) return rc;
   if (tracing) {
     if (fom->d.trace) trace_dump("fom", g_trace_buf[0], (size_t)((S + 63) / 64));
     if (rom->d.trace) trace_dump("proj", g_trace_buf[1], (size_t)S);

@@ -894,7 +894,7 @@ __device__ __forceinline__ void fused_solve_mw(const RomDev& p, d4 (&acc)[(NB * 
 // ---------------------------------------------------------------------------------------
 constexpr int ROM_SW_LDS = 16 * 5;      // doubles of LDS per wave (B_r)
 constexpr int ROM_SW_MFMA_DIAG_TILES = 6;      // block rows with at most this many live tiles factor their diagonal tile on the matrix cores
-template <int NB>
+template <int NB, bool RM = false>
 __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (NB + 1) / 2], const double (&bacc)[NB], int q, int c,
                                               double* __restrict__ mt, double& qout) {
   // The extra column is formed LEFT-looking -- G_kb -= sum_{j < kb} U(j, kb)^T Z_j when block row kb is reached -- so that at most
@@ -947,7 +947,9 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
     // (the first block rows of a wide basis keep the shuffle steps: with 15 or 10 tiles live, diag_tile_inverse's working set does
     //  not fit beside them under the kernel's 200-register cap -- hipcc spills, and spill code beside inline-asm MFMAs is not
     //  hazard-safe; with <= 6 live tiles it does)
-    constexpr bool kMfmaDiag = (NB - kb) * (NB - kb + 1) / 2 <= ROM_SW_MFMA_DIAG_TILES;
+    // (RM, the roomy variant beside the FOM's half sweep: 256 registers, every block row factors its diagonal tile this way and
+    //  the shuffle steps are not instantiated)
+    constexpr bool kMfmaDiag = RM || (NB - kb) * (NB - kb + 1) / 2 <= ROM_SW_MFMA_DIAG_TILES;
     if constexpr (kMfmaDiag) {
       // Round 4: the diagonal tile 4 x 4-blocked on the matrix cores (diag_tile_inverse, as the other two epilogues since round 3)
       // instead of the 16 shuffle steps below.  It returns M in the C/D layout; the A operand of M T is M^T in that layout --
@@ -956,6 +958,9 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       // would cost the co-resident band sweep a quarter of its waves), no shuffles (16 of them spilled 140 registers).
       d4 D = acc[tidx<NB>(kb, kb)];
       const d4 Mc = diag_tile_inverse(D, q, c, q * 16 + c, bad);
+      // (the pivot tests are settled HERE: left to itself hipcc sinks them to the end of the epilogue and keeps all 16 NB pivots in
+      //  registers until then -- that, not the tiles, is what overflowed the register file with five matrix-core block rows)
+      if constexpr (RM) asm volatile("" : "+v"(bad));
       d4 MT = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int g = 0; g < 4; ++g) MT = __builtin_amdgcn_mfma_f64_16x16x4f64(Mc[g], c == q + 4 * g ? 1.0 : 0.0, MT, 0, 0, 0);
@@ -1006,9 +1011,31 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       }
       T = n[0];
     };
-    sfor<kb + 1, NB>([&](auto jc) { solve_tile(acc[tidx<NB>(kb, decltype(jc)::value)]); });
-    solve_tile(e[0]);
-    z[kb] = e[0];
+    if constexpr (RM) {
+      // the roomy variant has the registers for all results of the block row at once: the four-MFMA chains of its NB - kb
+      // independent tiles (the extra column last) run interleaved, ONE wait per round instead of one per MFMA; every product and
+      // every sum keeps its place in its own chain, so the bits are those of solve_tile
+      constexpr int NP = NB - kb;
+      d4 n[NP];
+#pragma unroll
+      for (int t = 0; t < NP; ++t) n[t] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int t = 0; t < NP; ++t) {
+          const double b = t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)][g] : e[0][g];
+          asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(n[t]) : "v"(Am[g]), "v"(b));
+        }
+        mfma_drain(n);
+      }
+#pragma unroll
+      for (int t = 0; t + 1 < NP; ++t) acc[tidx<NB>(kb, kb + 1 + t)] = n[t];
+      z[kb] = n[NP - 1];
+    } else {
+      sfor<kb + 1, NB>([&](auto jc) { solve_tile(acc[tidx<NB>(kb, decltype(jc)::value)]); });
+      solve_tile(e[0]);
+      z[kb] = e[0];
+    }
     if constexpr (kb + 1 < NB) {                           // (c)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -1047,7 +1074,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
   return bad;
 }
 
-template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false>
+template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false, bool RM = false>
 __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw, int64_t s, int lane,
                                               double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                               int* __restrict__ info, double* __restrict__ w_r = nullptr,
@@ -1104,8 +1131,9 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
   int bad = 0;
   // factor == 2 with nothing but qoi_r wanted (the sample-pair path): factorisation, both substitutions and the reduced QoI as
   // MFMA-form panel operations (fused_solve_sw), after B_r below
-  const bool qoi_only = NW == 1 && NB <= 5 && !SK && factor == 2 && w_r == nullptr && qoi_r != nullptr && mt_lds != nullptr &&
-                        p.n_obs <= 15;
+  // (RM: the roomy kernel is launched for exactly these calls and instantiates nothing else -- launch_rom_proj_single)
+  const bool qoi_only = RM || (NW == 1 && NB <= 5 && !SK && factor == 2 && w_r == nullptr && qoi_r != nullptr && mt_lds != nullptr &&
+                               p.n_obs <= 15);
   if constexpr (NW == 1 && NB <= 6) {
     if (factor && !qoi_only) {      // A_r = U^T U in registers; what is written below is then U^T (= L, packed by columns)
       bad = chol_tiles<NB>(acc, q, c, p.r);
@@ -1115,7 +1143,7 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
   // factor == 2: substitutions + QoI below, nothing stored but w_r, qoi_r (r <= 80)
   // factor == 3 (multi-wave kernels): factorisation + QoI in registers, nothing stored but qoi_r (fused_solve_mw)
   // factor == 4 (split-K kernel, SK): also the adjoint solve; v_r, w_r go to RomGradArgs::vw for rom_grad_contract_small_kernel
-  const bool fused_solve = (NW == 1 && (NB <= 5 || SK) && (factor == 2 || (SK && factor == 4))) || (NW > 1 && factor == 3);
+  const bool fused_solve = RM || (NW == 1 && (NB <= 5 || SK) && (factor == 2 || (SK && factor == 4))) || (NW > 1 && factor == 3);
   // C/D layout of v_mfma_f64_16x16x4_f64: lane holds D[row = (lane>>4) + 4*g][col = lane&15].
   // A_r is symmetric: tile (ti <= tj) element (row, col) is written as the LOWER element
   // (i = col, k = row) of the packed column-major lower triangle the solve kernel reads.
@@ -1173,7 +1201,7 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
     if constexpr (NW == 1 && NB <= 5 && !SK) {
       if (qoi_only) {
         double qv;
-        bad = fused_solve_sw<NB>(p, acc, bacc, q, c, mt_lds, qv);
+        bad = fused_solve_sw<NB, RM>(p, acc, bacc, q, c, mt_lds, qv);
         if (bad && info != nullptr && lane == 0) atomicOr(&info[s], 2);
         if (lane >= 1 && lane <= p.n_obs) qoi_r[s * p.n_obs + lane - 1] = bad ? __builtin_nan("") : qv;
         return;
@@ -1283,7 +1311,7 @@ __device__ __forceinline__ void rom_proj_entry_splitk(RomDev p, const double* __
 
 // NW waves share one sample (each owns every NW-th tile of the upper block triangle); a
 // workgroup is max(4, NW) waves = max(4, NW)/NW samples.
-template <int NB, int NW, bool GR = false, bool HF = false>
+template <int NB, int NW, bool GR = false, bool HF = false, bool RM = false>
 __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restrict__ theta, int64_t S,
                                                        double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                                        int* __restrict__ info, double* __restrict__ w_r, double* __restrict__ qoi_r,
@@ -1327,7 +1355,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
         }
       }
     }
-    rom_proj_body<NB, 1, 0, false, GR>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
+    rom_proj_body<NB, 1, 0, false, GR, false, RM>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
                                        half ? kpat + __builtin_amdgcn_readfirstlane(p.kmg_m) : kpat, 0, 1, nullptr,
                                        NB <= 5 ? mt_sw + wave * ROM_SW_LDS : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {

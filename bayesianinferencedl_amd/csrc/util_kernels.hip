@@ -508,4 +508,26 @@ int launch_sub(const double* a, const double* b, int64_t count, double* out, hip
   return 0;
 }
 
+// the pair path beside the roomy projection kernel: err = qoi - qoi_r, and a sample that EITHER half flagged (info != 0) comes
+// back as NaN in qoi_r and err -- the reduced solve of a sample whose FOM solve failed (every conductivity zero: A_r from the Robin
+// terms alone is still positive definite and B_r = 0) would otherwise return a finite row beside the flag.  out may be null.
+__global__ void sub_flagged_kernel(const double* __restrict__ a, double* __restrict__ b, const int* __restrict__ info, int n_obs,
+                                   int64_t count, double* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    const bool bad = info[i / n_obs] != 0;
+    if (bad) b[i] = __builtin_nan("");
+    if (out != nullptr) out[i] = bad ? __builtin_nan("") : a[i] - b[i];
+  }
+}
+
+int launch_sub_flagged(const double* a, double* b, const int* info, int n_obs, int64_t count, double* out, hipStream_t st) {
+  if (count == 0 || n_obs <= 0) return 0;
+  ScopedKernelTimer t(K_MISC, st);
+  int64_t blocks = (count + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(sub_flagged_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, info, n_obs, count, out);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace finrom

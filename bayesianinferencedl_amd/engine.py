@@ -597,6 +597,14 @@ class RomEngine:
             check(rc, "finrom_rom_last_form")
         return _ffi.ROM_FORMS[rc]
 
+    def last_epilogue(self):
+        """'roomy' when the most recent projection launch ran the 256-register one-wave kernel (the pair path beside the FOM's half
+        sweep, QoI-only, r <= 80), 'standard' for every other kernel, 'none' before the first call (finrom_rom_last_epilogue)."""
+        rc = lib().finrom_rom_last_epilogue(self._h)
+        if rc < 0:
+            check(rc, "finrom_rom_last_epilogue")
+        return _ffi.ROM_EPILOGUES[rc]
+
     def solve(self, theta, want_state=False, want_w=True):
         """want_w=False: only the reduced QoI comes back; bases wider than 96 then factor and solve inside the projection
         kernel's registers (no A_r in memory)."""

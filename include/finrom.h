@@ -372,6 +372,13 @@ int finrom_rom_mirror_tables(const finrom_rom_desc* desc, const double* row_weig
 #define FINROM_ROM_FORM_FULL 1
 #define FINROM_ROM_FORM_HALF 2
 int finrom_rom_last_form(finrom_rom_t h);
+/* Which epilogue the most recent projection launch on this handle ran (tests assert on it): FINROM_ROM_EPILOGUE_ROOMY = the
+ * 256-register one-wave kernel that finrom_solve_pairs launches beside the FOM's half sweep for QoI-only calls at r <= 80
+ * (FINROM_PROJ_NO_ROOMY=1 when the handle is created: never); FINROM_ROM_EPILOGUE_STANDARD = any other kernel. */
+#define FINROM_ROM_EPILOGUE_NONE 0
+#define FINROM_ROM_EPILOGUE_STANDARD 1
+#define FINROM_ROM_EPILOGUE_ROOMY 2
+int finrom_rom_last_epilogue(finrom_rom_t h);
 /* theta [S x P] -> w_r [S x r] (NULL to skip), qoi_r [S x n_obs], info [S] (NULL ok);
  * optional A_r [S x r x r] and B_r [S x r] (the state the reference keeps in
  * self._A_r / self._B_r for its gradients, :296-297) -- NULL to skip. */
