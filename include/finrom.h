@@ -465,7 +465,10 @@ int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, con
  * a latent Gaussian field k = mean + U^T v with v ~ N(0, I), is finrom_hmc_leapfrog_field below: the same state in whitened
  * coordinates, mean = 0 and c_pri = 1, so that finrom_hmc_begin / _end compute its Hamiltonian unchanged.)  All arrays are DEVICE
  * pointers owned by the caller; C <= 64 chains advance in lockstep (one sample of the batch each); needs finrom_rom_set_gradient,
- * the direct projection, P <= 16 and a basis the one-sample pipeline serves (r <= 96) -- FINROM_ERR_UNSUPPORTED otherwise. */
+ * the direct projection, P <= 16 and a basis the one-sample pipeline serves (r <= 96) -- FINROM_ERR_UNSUPPORTED otherwise.
+ * finrom_hmc_end / _end_metric reject a chain whose info is not 0, whose potential is NaN or beyond +-1.7e308, or whose kinetic
+ * energy is not finite; a rejected chain's K, U and dU keep their bits.  C == 0: finrom_hmc_begin / _end / _begin_metric /
+ * _end_metric return 0 and touch nothing, the counters *jt and *pt included. */
 typedef struct {
   int64_t C; int32_t n;                 /* chains, nodes of the field */
   double eps, c_lik, c_pri;             /* leapfrog step, 1 / sigma^2, 1 / tau^2 */
