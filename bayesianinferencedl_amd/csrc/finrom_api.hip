@@ -2037,6 +2037,11 @@ int32_t finrom_mlp_stage_reach(int32_t n_layers, int32_t n_w, int32_t n_out, int
   return mlp_stage_reach(n_layers, n_w, n_out);
 }
 int32_t finrom_mlp_forward_max_in(void) { return MLP_FORWARD_MAX_IN; }
+// clears the caller's info for the forms of romml_grad_impl whose kernels only ever flag in (a kernel node, not a memset node: below)
+__global__ __launch_bounds__(256) static void clear_info_kernel(int32_t* __restrict__ info, int64_t S) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < S) info[i] = 0;
+}
 // (hs: the call is a leapfrog step -- finrom_hmc_leapfrog: position update in front, momentum update behind; one-sample form only)
 struct HmcStep { const double* mom; double eps; double* k_out; HmcTail tail; const double* theta_parts_in; };
 static int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,
@@ -2089,7 +2094,12 @@ static int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop
     bf.g0_out = (float*)mlp->g0.p;
   }
   // info is this call's alone: stored by the one-sample solve kernel, cleared here for the other forms (whose kernels or flags in)
-  if (info != nullptr && !one) FR_HIP(hipMemsetAsync(info, 0, (size_t)S * sizeof(int32_t), st));
+  // (by a kernel, not hipMemsetAsync: inside a captured graph the memset node cleared info in the first replay only, and the
+  // chains of every later replay kept the flags they came with -- tests/test_gpu_hmc_leapfrog_field.py starts them at 5)
+  if (info != nullptr && !one) {
+    hipLaunchKernelGGL(clear_info_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, info, S);
+    FR_HIP(hipGetLastError());
+  }
   rom->defer_gsum = one; rom->last_gpart = nullptr; rom->fuse = fm.on ? &fm : nullptr; rom->back = bf.on ? &bf : nullptr;
   rom->info_store = one;
   rc = finrom_rom_grad(rom, (const double*)mlp->theta.p, (const double*)mlp->shift.p, 1, S, loss, (double*)mlp->gth.p, nullptr,

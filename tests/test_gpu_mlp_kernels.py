@@ -370,6 +370,39 @@ def test_leapfrog_steps_are_exact_where_they_are_fma_and_replay_bit_for_bit(spac
         assert np.max(np.abs(a[idx] - b[idx])) <= 2 * K.bound(r32, r64)
 
 
+@pytest.mark.parametrize("poison", ["finite", "nan"])
+@pytest.mark.parametrize("name", ["one-staged-ref", "one-unstaged-size-50x7"])
+def test_a_flagged_chain_keeps_its_momentum_through_the_leapfrog_form(spaces, name, poison):
+    """Chain 1 starts at a field the reduced model cannot factor -- finite: -1e200 times its positive field (A_r = psi^T psi cannot
+    be indefinite; at this size it is beyond the largest double, tests/leap_field_cases.py); nan: one NaN entry -- and stays
+    flagged through three steps, the two that take the carried averages included: info != 0 for it alone, dU = 0 exactly, its
+    momentum's bits kept, its position still moved by the rule; every other chain bitwise as in the clean run."""
+    c = K.FUSED_BY_NAME[name]
+    j, steps = 1, {"clean": [], "dirty": []}
+
+    def recorder(tag):
+        def watch(i, before, k_out, p_new, dUq, grad, info, loss, e, q):
+            steps[tag].append(dict(k_in=before[0], p_in=before[1], k_out=k_out, P=p_new, dUq=dUq, grad=grad, info=info, loss=loss, e=e, q=q))
+        return watch
+    _Leap(spaces, c).stream_order(recorder("clean"))
+    dirty = _Leap(spaces, c)
+    if poison == "finite":
+        dirty.K0[j] = -1e200 * dirty.K0[j]
+    else:
+        dirty.K0[j, 7] = np.nan
+    dirty.stream_order(recorder("dirty"))
+    keep = np.arange(c.S) != j
+    assert len(steps["dirty"]) == len(steps["clean"]) == _Leap.STEPS
+    for i, (a, b) in enumerate(zip(steps["dirty"], steps["clean"])):
+        assert a["info"][j] != 0 and (a["info"][keep] == 0).all() and (b["info"] == 0).all(), (name, poison, i, a["info"])
+        assert np.array_equal(a["dUq"][j], np.zeros_like(a["dUq"][j])), (name, poison, i, "dU of the flagged chain")
+        assert np.array_equal(a["P"][j].view(np.uint64), a["p_in"][j].view(np.uint64)), (name, poison, i, "the flagged chain's momentum moved")
+        assert np.array_equal(a["k_out"][j], _fma(dirty.EPS, a["p_in"][j], a["k_in"][j]), equal_nan=True), (name, poison, i, "position")
+        assert np.isnan(a["k_out"][j]).sum() == (1 if poison == "nan" else 0)
+        for k in ("k_out", "P", "dUq", "grad", "loss", "e", "q"):
+            assert np.isfinite(a[k][keep]).all() and np.array_equal(a[k][keep], b[k][keep]), (name, poison, i, k)
+
+
 def test_the_leapfrog_form_refuses_a_batched_model(spaces):
     """The probe behind the table's "one" column: a model the one-sample form does not take is FINROM_ERR_UNSUPPORTED for
     finrom_hmc_leapfrog, and the rows named "one" above were taken (their steps ran)."""
