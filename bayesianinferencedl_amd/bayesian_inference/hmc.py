@@ -43,7 +43,16 @@ pooled mean, standard deviation, R-hat, batch-means effective sample size and Mo
 states after the proposals with GLOBAL index >= burn; everything is indexed by the global proposal index, so the sums do not depend
 on `block`, on graph or stream order, or on where a run was interrupted: `stats=ChainStats(resume=first.stats)` with the
 continuation rule above (rng="philox", proposal0 = the proposals already made) continues every sum.  stats=None: every path and bit
-as before, no launch and no buffer more."""
+as before, no launch and no buffer more.
+
+`model="romml" | "rom" | "fom"` on the two device chain functions: the inverse problem's three models (the reference's driver
+instantiates the full-order operator, pymc_func_bayes_inverse.py:174; the reduced ones are the alternatives beside it, :175-176).
+"fom" takes solver=Fin and data=; "rom" is the plain reduced model, without the learned correction.  The torch-op form evaluates
+through one adapter per model (the calls of estimate_MAP.objective(kind).device); the fused form through finrom_hmc_leapfrog_fom /
+_field_fom / _rom, built from two model-agnostic kernels (finrom_hmc_drift, finrom_hmc_kick).  The plain reduced model sees the
+field only through its sub-fin averages, so under a prior its fused step stays in whitened coordinates: theta = Sop m + (Sop U^T) v,
+grad_v = (Sop U^T)^T g_theta, no triangular product and no field during a trajectory.  `fom_value_and_grad` / `rom_value_and_grad`
+are the host callables for run_chains.  model="romml" (the default): every path, launch and bit as before."""
 from __future__ import annotations
 
 import numpy as np
@@ -449,9 +458,71 @@ def romml_value_and_grad(solver_r):
     return f
 
 
+def fom_value_and_grad(solver, data):
+    """The evaluation the reference's SqErrorOpFOM performs (pymc_func_bayes_inverse.py:174), batched over chains: Fin.gradient_batch
+    at nodal fields against the observations `data`."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+
+    def f(K):
+        res = solver.gradient_batch(np.ascontiguousarray(K, dtype=np.float64), data)
+        return np.asarray(res["J"]), np.asarray(res["grad"]), np.asarray(res["info"]) != 0
+    return f
+
+
+def rom_value_and_grad(solver_r, data=None):
+    """The plain reduced model's evaluation (SqErrorOpROM), batched over chains: AffineROMFin.grad_reduced_batch and the chain rule
+    through the sub-fin averages, dJ/dk = g_theta @ dsigma_dk.  data: None = solver_r.data."""
+    def f(K):
+        res = solver_r.grad_reduced_batch(np.ascontiguousarray(K, dtype=np.float64), data=data)
+        return np.asarray(res["J"]), np.asarray(res["g_theta"]) @ solver_r.dsigma_dk, np.asarray(res["info"]) != 0
+    return f
+
+
+MODELS = ("romml", "rom", "fom")
+
+
+def _check_model(model, solver_r, solver, data, who):
+    """ValueError for a model the chains do not know and for a model without what it evaluates with."""
+    if model not in MODELS:
+        raise ValueError(f"{who}: unknown model {model!r} (romml, rom, fom)")
+    if model == "fom":
+        if solver is None:
+            raise ValueError(f"{who}: model='fom' needs solver=Fin")
+        if data is None:
+            raise ValueError(f"{who}: model='fom' needs data= (the observations)")
+    else:
+        if solver is not None:
+            raise ValueError(f"{who}: solver= belongs to model='fom'; model={model!r} evaluates with solver_r")
+        if solver_r is None:
+            raise ValueError(f"{who}: model={model!r} needs solver_r=AffineROMFin")
+        if data is None and getattr(solver_r, "data", None) is None:
+            raise ValueError(f"{who}: model={model!r} needs data= (or solver_r.data)")
+    return model
+
+
+def _device_model(model, solver_r, solver, data_t):
+    """f(F [C, n] device tensor) -> dict(loss [C], grad [C, n], info [C]) on torch's current stream: the calls that
+    estimate_MAP.objective(kind).device makes, one adapter per model."""
+    if model == "romml":
+        return lambda Fq: solver_r.grad_romml_batch(Fq, data=data_t)
+    if model == "fom":
+        def f(Fq):
+            r = solver.gradient_batch(Fq, data_t)
+            return {"loss": r["J"], "grad": r["grad"], "info": r["info"]}
+        return f
+    import torch
+    S_t = torch.as_tensor(np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64), dtype=torch.float64, device=data_t.device)
+
+    def f(Fq):
+        r = solver_r.grad_reduced_batch(None, data=data_t, theta=solver_r._avg(Fq))
+        # g_theta @ dsigma_dk as one broadcast product and one reduction over the nine averages (no BLAS call inside a captured graph)
+        return {"loss": r["J"], "grad": (r["g_theta"][:, :, None] * S_t[None]).sum(dim=1), "info": r["info"]}
+    return f
+
+
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None):
+                     stats=None, model="romml", solver=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -468,16 +539,27 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     in stream order between two blocks' replays, writes the draws of proposals proposal0 + done .. into the block buffers the
     graph reads (standard normals, also under a metric); the chain does not depend on `block`.
     stats: a ChainStats -- one finrom_hmc_stats_update launch behind finrom_hmc_end / _end_metric in every proposal (captured with
-    it), on the step's field buffer under a prior and on the end point's position buffer otherwise: no triangular product more."""
+    it), on the step's field buffer under a prior and on the end point's position buffer otherwise: no triangular product more.
+    model, solver: "fom" (solver=Fin, data= required) -- a step is finrom_hmc_leapfrog_fom (drift kernel, finrom_fom_gradient's
+    launches, kick kernel), under a prior finrom_hmc_leapfrog_field_fom; "rom" -- finrom_hmc_leapfrog_rom for both priors: A = Sop
+    under the i.i.d. prior, A = Sop U^T and theta0 = Sop mean in whitened coordinates, where no field exists during a trajectory
+    (stats= adds one finrom_sampler_field launch on the end point per proposal; recorded evaluations form field and field-space
+    gradient step by step).  No metric forms (FINROM_ERR_UNSUPPORTED: fused=None falls back)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
+    _check_model(model, solver_r, solver, data, "run_chains_fused")
     import ctypes as C
     import torch
     from .. import _ffi
     L = _ffi.lib()
-    rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
-    if mlp is None:
-        raise _ffi.FinromError("run_chains_fused needs the error model on the device (a ResBnFcModel)")
-    solver_r._ensure_gradient()
+    if model == "fom":
+        fom = solver._engine("field")
+        fom._enable_gradient()
+        rom = mlp = Sop = None
+    else:
+        rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
+        if model == "romml" and mlp is None:
+            raise _ffi.FinromError("run_chains_fused needs the error model on the device (a ResBnFcModel)")
+        solver_r._ensure_gradient()
     dev = torch.device("cuda", torch.cuda.current_device())
     f64 = dict(dtype=torch.float64, device=dev)
     i64 = dict(dtype=torch.int64, device=dev)
@@ -486,6 +568,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if metric is not None and prior is None:
         raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog step under the i.i.d. "
                                "prior has no metric form (pass prior=, or fused=False)")
+    if metric is not None and model != "romml":
+        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog steps of model={model!r} "
+                               "have no metric form (pass fused=False)")
     K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
     Cn, n = K.shape
     if prior is not None:                                            # whitened: N(0, I), c_pri = 1
@@ -500,6 +585,15 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     data_np = np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64)
     data_t = torch.as_tensor(data_np, **f64)
     per_sample = 1 if data_np.ndim == 2 else 0
+    whitened_rom = model == "rom" and prior is not None              # the step never forms the field
+    if model == "rom":                                               # theta = theta0 + A x, gradient A^T g_theta (x: k, or v under a prior)
+        S_np = np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64)
+        if not np.array_equal(S_np, solver_r.ops.S):                 # (one map serves theta and the chain rule)
+            raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the reduced model's averaging operator "
+                                   "and dsigma_dk differ (pass fused=False)")
+        A_t = torch.as_tensor(np.ascontiguousarray(S_np @ prior.U.T) if prior is not None else S_np, **f64)
+        th0 = torch.as_tensor(S_np @ prior.mean, **f64) if prior is not None else None
+        theta_b, gth_b = torch.zeros(Cn, S_np.shape[0], **f64), torch.zeros(Cn, S_np.shape[0], **f64)
     if seeds64 is None:
         rngs = [np.random.default_rng(s) for s in seeds]
         assert len(rngs) == Cn
@@ -529,6 +623,21 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         return torch.cuda.current_stream().cuda_stream
 
     def leap(state, step, want_grad=False):
+        if model == "fom":
+            if prior is not None:
+                _ffi.check(L.finrom_hmc_leapfrog_field_fom(fom._h, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
+                                                           C.byref(state), step, data_t.data_ptr(), per_sample, None, stream()),
+                           "finrom_hmc_leapfrog_field_fom")
+            else:                                                    # (the gradient between the model's launches and the kick: grad_rec)
+                _ffi.check(L.finrom_hmc_leapfrog_fom(fom._h, C.byref(state), step, data_t.data_ptr(), per_sample, grad_rec.data_ptr(),
+                                                     None, stream()), "finrom_hmc_leapfrog_fom")
+            return
+        if model == "rom":
+            _ffi.check(L.finrom_hmc_leapfrog_rom(rom._h, A_t.data_ptr(), th0.data_ptr() if th0 is not None else None, C.byref(state),
+                                                 step, data_t.data_ptr(), per_sample, theta_b.data_ptr(), gth_b.data_ptr(),
+                                                 grad_rec.data_ptr() if want_grad and prior is None else None, None, stream()),
+                       "finrom_hmc_leapfrog_rom")
+            return
         if metric is not None:
             _ffi.check(L.finrom_hmc_leapfrog_field_metric(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(),
                                                           grad_f.data_ptr(), C.byref(state), step, data_t.data_ptr(), per_sample,
@@ -546,12 +655,18 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                                          grad_rec.data_ptr() if want_grad else None, None, None, stream()), "finrom_hmc_leapfrog")
         Sop.used_on(stream())
 
+    def field_of(V):
+        _ffi.check(L.finrom_sampler_field(fs._h, fmean.data_ptr(), V.data_ptr(), Cn, F.data_ptr(), stream()), "finrom_sampler_field")
+
     recorded, evals = [], 0
 
     def note(step):
         nonlocal evals
         if record is not None and evals in record:
-            if prior is not None:
+            if whitened_rom:                                         # field and field-space gradient, formed for the record alone
+                recorded.append((evals, fs.field(Kq[(step + 1) & 1], mean=fmean).cpu().numpy().copy(), loss.cpu().numpy().copy(),
+                                 gth_b.cpu().numpy() @ S_np))
+            elif prior is not None:
                 recorded.append((evals, F.cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_f.cpu().numpy().copy()))
             else:
                 recorded.append((evals, Kq[(step + 1) & 1].cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_rec.cpu().numpy().copy()))
@@ -571,6 +686,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         else:
             _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
         if ds is not None:                                           # (F holds the field of the trajectory's last step: the end point's)
+            if whitened_rom:                                         # (no step formed it: the end point's field, for the sums alone)
+                field_of(Kq[n_leapfrog & 1])
             ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss)
 
     # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
@@ -586,6 +703,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if trace is not None:
         trace[0].copy_(K)
     _restore_chain(stats, K, U, dU)
+    if whitened_rom and stats is not None:                           # the start point's field (also the field kernel's workspace, before a capture)
+        field_of(K)
     ds = None if stats is None else _DeviceStats(stats, F if prior is not None else K, loss, proposal0, n_prop, pt, acc)
     g = None
     if graph and n_prop > 0:
@@ -628,9 +747,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         done += nb
     cs = ds.result(K, U, dU) if ds is not None else None
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs, model=model)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs, model=model)
 
 
 def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
@@ -645,7 +764,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0, stats=None):
+                      proposal0=0, stats=None, model="romml", solver=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -670,9 +789,17 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     same for any `block`.
     stats: a ChainStats -- one finrom_hmc_stats_update launch behind the state update of every proposal (captured with it), on the
     last evaluation's field under a prior and on Kq otherwise; `stats` of the result as for run_chains, the device's sums.
-    Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates.
+    model, solver: which of the inverse problem's three models the chains evaluate -- "romml" (solver_r with a device error model),
+    "rom" (solver_r, the plain reduced model) or "fom" (solver=Fin and data= required; solver_r may be None).  Here the evaluation
+    is one adapter per model (_device_model: the calls of estimate_MAP.objective(kind).device), everything around it unchanged, so
+    prior=, metric=, rng=, stats=, record=, keep_trace= and graph= serve all three; fused: run_chains_fused's steps (no metric forms
+    for "fom" and "rom": fused=None then takes this form).  ValueError for an unknown model, "fom" without solver= or data=, solver=
+    with another model.  `model` of the result names it.
+    Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates (model=
+    "fom": fom_value_and_grad(solver, data); "rom": rom_value_and_grad(solver_r, data)).
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
+    _check_model(model, solver_r, solver, data, "run_chains_device")
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
@@ -682,7 +809,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats)
+                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -698,6 +825,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     else:
         mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
     data_t = torch.as_tensor(np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64), **f64)
+    model_eval = _device_model(model, solver_r, solver, data_t)
     if seeds64 is None:
         rngs = [np.random.default_rng(s) for s in seeds]
         assert len(rngs) == C
@@ -722,7 +850,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     def evaluate():
         """dUq (= grad U / c_pri), out <- value and gradient at Kq (all static tensors: the same buffers at every call once captured)."""
         Fq = fs.field(Kq, mean=fmean) if prior is not None else Kq  # (with a prior, Kq is v and the misfit is taken at its field)
-        res = solver_r.grad_romml_batch(Fq, data=data_t)
+        res = model_eval(Fq)
         gq = fs.pullback(res["grad"]) if prior is not None else res["grad"]
         torch.sub(Kq, mean_t, out=D)
         torch.add(D, gq, alpha=c_lik / c_pri, out=dUq)              # dU / c_pri (one kernel; c_pri rides in the momentum updates' alpha)
@@ -829,6 +957,6 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         done += nb
     cs = ds.result(K, U, dU) if ds is not None else None
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs, model=model)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs, model=model)

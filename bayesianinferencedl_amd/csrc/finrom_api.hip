@@ -169,6 +169,7 @@ struct finrom_fom_s {
   const BandDev& band_for(bool want_w) const { return !want_w && band_m.on ? band_m : band; }
   std::vector<void*> owned;
   Scratch xT, Gw, gradT, qtmp;
+  Scratch hgrad;                       // finrom_hmc_leapfrog_fom without grad_out: the gradient between the FOM's launches and the kick
   int last_path = FINROM_FOM_PATH_NONE;   // finrom_fom_last_path
 };
 struct finrom_rom_s {
@@ -547,7 +548,7 @@ int finrom_fom_create(const finrom_fom_desc* a, finrom_fom_t* out) {
 void finrom_fom_destroy(finrom_fom_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);                 // (queued while a stream capture is open: finrom_internal.h)
-  h->xT.release(); h->Gw.release(); h->gradT.release(); h->qtmp.release();
+  h->xT.release(); h->Gw.release(); h->gradT.release(); h->qtmp.release(); h->hgrad.release();
   delete h;
 }
 
@@ -2240,6 +2241,136 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
   CallGuard cg((hipStream_t)stream);
   return hmc_leapfrog_field_impl(rom, mlp, Sop, prior, field_mean, field, grad_field, a, step, data, data_per_sample, qoi_r, e_nn,
                                  nullptr, nullptr, stream);
+}
+
+// ---- the chains under the full-order and the plain reduced model (hmc_model.hip; hmc.py model="fom" | "rom") ----------------------
+static int hmc_model_map_check(const char* who, const double* A, int32_t P) {
+  if (A != nullptr && (P < 1 || P > HMC_MODEL_MAXP)) {
+    set_error(std::string(who) + ": P = " + std::to_string(P) + " is outside 1 .. " + std::to_string(HMC_MODEL_MAXP));
+    return FINROM_ERR_ARG;
+  }
+  return 0;
+}
+static int hmc_drift_impl(const finrom_hmc_state* a, int32_t step, const double* A, const double* theta0, int32_t P, double* theta_out,
+                          void* stream, const char* who) {
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, who)) return rc;
+  if (step < 0) { set_error(std::string(who) + ": step < 0"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_model_map_check(who, A, P)) return rc;
+  if (A != nullptr && !theta_out) { set_error(std::string(who) + ": A without theta_out"); return FINROM_ERR_ARG; }
+  if (a->C > INT32_MAX) { set_error(std::string(who) + ": C > 2^31 - 1 (one workgroup per chain)"); return FINROM_ERR_ARG; }
+  return launch_hmc_drift(h, a->Kq[step & 1], a->Kq[(step + 1) & 1], A, theta0, P, theta_out, (hipStream_t)stream);
+}
+static int hmc_kick_impl(const finrom_hmc_state* a, int32_t step, const double* grad, const double* g_theta, const double* A, int32_t P,
+                         double* grad_out, void* stream, const char* who) {
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, who)) return rc;
+  if (step < 0) { set_error(std::string(who) + ": step < 0"); return FINROM_ERR_ARG; }
+  if ((grad != nullptr) == (g_theta != nullptr)) {
+    set_error(std::string(who) + ": exactly one of grad and g_theta must be given"); return FINROM_ERR_ARG;
+  }
+  if (g_theta != nullptr && !A) { set_error(std::string(who) + ": g_theta without A"); return FINROM_ERR_ARG; }
+  if (g_theta != nullptr) { if (int rc = hmc_model_map_check(who, A, P)) return rc; }
+  if (a->c_pri == 0.0) { set_error(std::string(who) + ": c_pri = 0"); return FINROM_ERR_ARG; }
+  if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_ARG; }
+  return launch_hmc_kick(h, a->Kq[(step + 1) & 1], grad, g_theta, A, P, grad_out, (hipStream_t)stream);
+}
+int finrom_hmc_drift(const finrom_hmc_state* a, int32_t step, const double* A, const double* theta0, int32_t P, double* theta_out,
+                     void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  return hmc_drift_impl(a, step, A, theta0, P, theta_out, stream, "hmc_drift");
+}
+int finrom_hmc_kick(const finrom_hmc_state* a, int32_t step, const double* grad, const double* g_theta, const double* A, int32_t P,
+                    double* grad_out, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  return hmc_kick_impl(a, step, grad, g_theta, A, P, grad_out, stream, "hmc_kick");
+}
+// info is this step's alone: finrom_fom_gradient's and finrom_rom_grad's kernels flag into it (a kernel node: see romml_grad_impl)
+static int hmc_clear_info(int32_t* info, int64_t S, hipStream_t st) {
+  hipLaunchKernelGGL(clear_info_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, info, S);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+static int hmc_fom_check(finrom_fom_t fom, const finrom_hmc_state* a, const double* data, const char* who) {
+  if (!fom || !data) { set_error(std::string(who) + ": null fom handle or data"); return FINROM_ERR_ARG; }
+  if (fom->d.xdim != a->n) {
+    set_error(std::string(who) + ": n = " + std::to_string(a->n) + " is not the full-order model's parameter count (" +
+              std::to_string(fom->d.xdim) + "): the chains move nodal fields");
+    return FINROM_ERR_UNSUPPORTED;
+  }
+  if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_UNSUPPORTED; }
+  return 0;
+}
+int finrom_hmc_leapfrog_fom(finrom_fom_t fom, const finrom_hmc_state* a, int32_t step, const double* data, int32_t data_per_sample,
+                            double* grad_out, double* qoi, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_leapfrog_fom")) return rc;
+  if (step < 0) { set_error("hmc_leapfrog_fom: step < 0"); return FINROM_ERR_ARG; }
+  if (a->c_pri == 0.0) { set_error("hmc_leapfrog_fom: c_pri = 0"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_fom_check(fom, a, data, "hmc_leapfrog_fom")) return rc;
+  if (a->C == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  double* g = grad_out;
+  if (!g) { if (int rc = fom->hgrad.reserve((size_t)a->C * a->n * sizeof(double))) return rc; g = (double*)fom->hgrad.p; }
+  double* kq = a->Kq[(step + 1) & 1];
+  int rc = hmc_drift_impl(a, step, nullptr, nullptr, 0, nullptr, stream, "hmc_leapfrog_fom");
+  if (!rc) rc = hmc_clear_info(a->info, a->C, st);
+  if (!rc) rc = finrom_fom_gradient(fom, kq, data, data_per_sample, a->C, g, a->loss, qoi, a->info, stream);
+  if (!rc) rc = hmc_kick_impl(a, step, g, nullptr, nullptr, 0, nullptr, stream, "hmc_leapfrog_fom");
+  return rc;
+}
+int finrom_hmc_leapfrog_field_fom(finrom_fom_t fom, finrom_sampler_t prior, const double* field_mean, double* field, double* grad_field,
+                                  const finrom_hmc_state* a, int32_t step, const double* data, int32_t data_per_sample, double* qoi,
+                                  void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_leapfrog_field_fom")) return rc;
+  if (a->c_pri != 1.0) { set_error("hmc_leapfrog_field_fom: c_pri must be 1 (whitened coordinates: the prior of v is N(0, I))"); return FINROM_ERR_ARG; }
+  if (step < 0) { set_error("hmc_leapfrog_field_fom: step < 0"); return FINROM_ERR_ARG; }
+  if (!prior || !field || !grad_field) { set_error("hmc_leapfrog_field_fom: null prior handle, field or grad_field"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_fom_check(fom, a, data, "hmc_leapfrog_field_fom")) return rc;
+  if (a->n != prior->n) {
+    set_error("hmc_leapfrog_field_fom: n = " + std::to_string(a->n) + " is not the prior's (" + std::to_string(prior->n) + ")");
+    return FINROM_ERR_ARG;
+  }
+  if (a->C == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = field_prior_ws(prior, a->C)) return rc;
+  double* vq = a->Kq[(step + 1) & 1];
+  int rc = launch_field_prior(prior->U, prior->n, 0, a->Kq[step & 1], a->P, a->eps, field_mean, field, vq, nullptr, a->C,
+                              (double*)prior->fpart.p, (int*)prior->ftick.p, st);
+  if (!rc) rc = hmc_clear_info(a->info, a->C, st);
+  if (!rc) rc = finrom_fom_gradient(fom, field, data, data_per_sample, a->C, grad_field, a->loss, qoi, a->info, stream);
+  if (rc) return rc;
+  FieldPriorTail tl;
+  tl.vq = vq; tl.c_lik = a->c_lik; tl.info = a->info; tl.mom = a->P; tl.dU = a->dUq; tl.eps = a->eps;
+  return launch_field_prior(prior->U, prior->n, 1, grad_field, nullptr, 0.0, nullptr, nullptr, nullptr, &tl, a->C,
+                            (double*)prior->fpart.p, (int*)prior->ftick.p, st);
+}
+int finrom_hmc_leapfrog_rom(finrom_rom_t rom, const double* A, const double* theta0, const finrom_hmc_state* a, int32_t step,
+                            const double* data, int32_t data_per_sample, double* theta, double* g_theta, double* grad_out,
+                            double* qoi_r, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_leapfrog_rom")) return rc;
+  if (step < 0) { set_error("hmc_leapfrog_rom: step < 0"); return FINROM_ERR_ARG; }
+  if (a->c_pri == 0.0) { set_error("hmc_leapfrog_rom: c_pri = 0"); return FINROM_ERR_ARG; }
+  if (!rom || !A || !data || !theta || !g_theta) { set_error("hmc_leapfrog_rom: null rom handle, A, data, theta or g_theta"); return FINROM_ERR_ARG; }
+  if (rom->g_npairs == 0) { set_error("hmc_leapfrog_rom: finrom_rom_set_gradient has not been called"); return FINROM_ERR_ARG; }
+  if (rom->d.P < 1 || rom->d.P > HMC_MODEL_MAXP) {
+    set_error("hmc_leapfrog_rom: the reduced model has " + std::to_string(rom->d.P) + " averages; the step serves 1 .. " +
+              std::to_string(HMC_MODEL_MAXP));
+    return FINROM_ERR_UNSUPPORTED;
+  }
+  if (a->C > 65535) { set_error("hmc_leapfrog_rom: C > 65535 (one grid row per chain)"); return FINROM_ERR_UNSUPPORTED; }
+  if (a->C == 0) return 0;
+  const int P = rom->d.P;
+  int rc = hmc_drift_impl(a, step, A, theta0, P, theta, stream, "hmc_leapfrog_rom");
+  if (!rc) rc = hmc_clear_info(a->info, a->C, (hipStream_t)stream);
+  if (!rc) rc = finrom_rom_grad(rom, theta, data, data_per_sample, a->C, a->loss, g_theta, nullptr, qoi_r, a->info, stream);
+  if (!rc) rc = hmc_kick_impl(a, step, nullptr, g_theta, A, P, grad_out, stream, "hmc_leapfrog_rom");
+  return rc;
 }
 
 // ---- low-rank metric (hmc_metric.hip) --------------------------------------------------------------------------------------------

@@ -95,6 +95,14 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
 int launch_hmc_stats(const finrom_hmc_stats& s, hipStream_t st);      // hmc_stats.hip (the descriptor holds device pointers only)
+// hmc_model.hip (finrom_hmc_drift / _kick): the model-agnostic halves of a leapfrog step.  A [P x n] (optional, P <= HMC_MODEL_MAXP):
+// drift: k_out = k + eps h.P and theta_out [C x P] = theta0 + A k_out;  kick: the gradient at kq is grad [C x n] or A^T g_theta,
+// then h.dUq and h.P as HmcTail states them (flagged chains: dUq 0, momentum untouched); grad_out (optional): the gradient itself
+constexpr int HMC_MODEL_MAXP = 16;
+int launch_hmc_drift(const HmcDev& h, const double* k, double* k_out, const double* A, const double* theta0, int P, double* theta_out,
+                     hipStream_t st);
+int launch_hmc_kick(const HmcDev& h, const double* kq, const double* grad, const double* g_theta, const double* A, int P,
+                    double* grad_out, hipStream_t st);
 
 // ---- low-rank metric M = I + V diag(lambda) V^T (hmc_metric.hip, finrom_metric_*, finrom_hmc_*_metric) -----------------------
 constexpr int METRIC_MAX_RHO = 64;

@@ -497,6 +497,52 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
                               const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* st,
                               int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
                               void* stream);
+/* The chains under the OTHER two models of the inverse problem (hmc.py model="fom" | "rom"): the reference's sampler instantiates the
+ * full-order operator (bayesian_inference/pymc_func_bayes_inverse.py:174 `SqErrorOpFOM`), the reduced ones are the alternatives
+ * beside it (:175-176).  The two halves of a leapfrog step that do not depend on the model are kernels of their own, with the
+ * ping-pong convention of finrom_hmc_leapfrog (k = Kq[step & 1], k' = Kq[(step + 1) & 1]); all arithmetic in double, every fused
+ * multiply-add written here as fma(a, b, c) = round(a b + c), nothing else contracted:
+ *   finrom_hmc_drift  k'[c][i] = fma(eps, P[c][i], k[c][i]).  With A [P x n] row-major (1 <= P <= 16; DEVICE) also
+ *                     theta_out[c][p] = theta0[p] + s_p (theta0 [P] or NULL = 0; ONE rounded addition), s_p = sum_i A[p][i] k'[c][i]
+ *                     in block_reduce.h's order: thread t = 0 .. 255 chains s = fma(A[p][i], k'[c][i], s) over i = t, t + 256, ...
+ *                     from 0; inside each wave of 64 a butterfly (lane l adds lane l ^ off, off = 32, 16, 8, 4, 2, 1); then
+ *                     (w0 + w1) + (w2 + w3).  One 256-thread workgroup per chain: a row's bits depend on that row alone.
+ *                     A == NULL: the position update alone (theta0, P, theta_out ignored).
+ *   finrom_hmc_kick   the gradient at k' is g[c][i] = grad[c][i], or (grad NULL) fma-chained from 0 over p = 0 .. P - 1:
+ *                     g = fma(g_theta[c][p], A[p][i], g); exactly one of grad and g_theta is given (A and P with g_theta).
+ *                     grad_out[c][i] = g (optional: the field-space gradient, c_lik / c_pri left out).  For a chain with
+ *                     info[c] == 0:  d = k'[c][i] - mean[c][i];  dUq = fma(c_lik / c_pri, g, d);  P = fma(-(eps c_pri), dUq, P)
+ *                     (both coefficients formed in double first).  For a chain with info[c] != 0: dUq = 0, P untouched.
+ *                     Grid (ceil(n / 256), C): one thread per (chain, node); C <= 65535.
+ * Neither has a workspace or allocates: legal while the stream is capturing.  Checks before any device call (FINROM_ERR_ARG, with a
+ * message): a null state or field of it, step < 0, P outside 1 .. 16 where A is used, a null theta_out with A, both or neither of
+ * grad and g_theta, g_theta without A, c_pri == 0 (kick).  C == 0: returns 0, no launch.
+ * The fused steps composed from them -- the graph of a proposal stays one linear chain; loss and info of the state are this step's
+ * alone (info is cleared by a kernel in front of the model's launches, which flag into it):
+ *   finrom_hmc_leapfrog_fom        drift (no A); finrom_fom_gradient's launches at k' (x = the nodal field: fom's xdim must be n)
+ *                                  -> st->loss, st->info, gradient into grad_out (or the handle's own buffer: grad_out NULL); kick.
+ *   finrom_hmc_leapfrog_field_fom  finrom_hmc_leapfrog_field with finrom_fom_gradient in the place of finrom_romml_grad (c_pri == 1,
+ *                                  mean zeros): field kernel with the position update, the FOM at the field, pullback kernel with
+ *                                  the momentum update.
+ *   finrom_hmc_leapfrog_rom        drift with A into theta [C x P]; finrom_rom_grad's launches at theta -> st->loss, st->info,
+ *                                  g_theta [C x P] (theta, g_theta: caller's buffers); kick with (g_theta, A).  The plain reduced
+ *                                  model sees the field through theta = Sop k alone, so ONE entry point serves both priors: i.i.d.
+ *                                  A = Sop, theta0 NULL; whitened (k = m + U^T v): A = Sop U^T, theta0 = Sop m, mean zeros,
+ *                                  c_pri = 1 -- neither n x n triangular product runs in a step, and no field exists.
+ * What the model allocates on first use (workspaces that grow with C) it allocates in the first call: run one step with the same C
+ * before a capture.  There are no metric forms of these steps. */
+int finrom_hmc_drift(const finrom_hmc_state* st, int32_t step, const double* A, const double* theta0, int32_t P, double* theta_out,
+                     void* stream);
+int finrom_hmc_kick(const finrom_hmc_state* st, int32_t step, const double* grad, const double* g_theta, const double* A, int32_t P,
+                    double* grad_out, void* stream);
+int finrom_hmc_leapfrog_fom(finrom_fom_t fom, const finrom_hmc_state* st, int32_t step, const double* data, int32_t data_per_sample,
+                            double* grad_out, double* qoi, void* stream);
+int finrom_hmc_leapfrog_field_fom(finrom_fom_t fom, finrom_sampler_t prior, const double* field_mean, double* field, double* grad_field,
+                                  const finrom_hmc_state* st, int32_t step, const double* data, int32_t data_per_sample, double* qoi,
+                                  void* stream);
+int finrom_hmc_leapfrog_rom(finrom_rom_t rom, const double* A, const double* theta0, const finrom_hmc_state* st, int32_t step,
+                            const double* data, int32_t data_per_sample, double* theta, double* g_theta, double* grad_out,
+                            double* qoi_r, void* stream);
 
 /* ---- Laplace-preconditioned HMC: a low-rank metric at the MAP point ------------------------------------------------------------- *
  * The reference's working sampler builds a low-rank Gauss-Newton Hessian of the misfit at the MAP point in prior-whitened
