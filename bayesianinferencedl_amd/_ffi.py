@@ -152,6 +152,9 @@ SIGNATURES = {
     "finrom_rom_set_mirror": (C.c_int, [C.c_void_p, C.POINTER(RomDesc), c_i32p, c_f64p, c_i32p]),
     "finrom_rom_mirror_validate": (C.c_int, [C.POINTER(RomDesc), C.c_int32, c_i32p, c_f64p, c_i32p]),
     "finrom_rom_mirror_tables": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, c_f64p, c_i32p]),
+    "finrom_rom_set_mirror_short": (C.c_int, [C.c_void_p, C.POINTER(RomDesc), c_f64p, C.c_double, C.c_double]),
+    "finrom_rom_mirror_counts": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p]),
+    "finrom_rom_mirror_info": (C.c_int, [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]),
     "finrom_rom_last_form": (C.c_int, [C.c_void_p]),
     "finrom_rom_last_epilogue": (C.c_int, [C.c_void_p]),
     "finrom_rom_destroy": (None, [C.c_void_p]),

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <iterator>
 #include <mutex>
 #include <numeric>
 
@@ -180,6 +181,8 @@ struct finrom_rom_s {
   RomGramDev gram;                     // offline/online form (finrom_rom_set_gram); gram.h is filled at create
   int projection = FINROM_PROJECTION_DIRECT;
   std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
+  int mirror_n = 0;                    // rows of the installed half descriptor
+  int mirror_counts[2][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / the short list
   int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
   int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
   bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
@@ -1178,31 +1181,128 @@ std::vector<int> rows_by_term_count(const finrom_rom_desc* a) {
 
 // pattern-uniform k-steps (RomDev::tvu): four rows that share ONE list of theta indices; sorted by term count, descending
 struct KStep { std::vector<int> pat; int rows[4]; };
-std::vector<KStep> uniform_ksteps(const finrom_rom_desc* a, const std::vector<int>& order) {
+// How the rows that do not fill a k-step of their own pattern are packed.  PACK_CONSECUTIVE: rows that follow each other in pattern
+// order share a k-step while the union of their patterns has at most kMaxTerms entries -- every list but the short half list.
+// PACK_FEWEST (the half list with dropped rows, finrom_rom_set_mirror, DESIGN 4b''): the leftovers are a tenth to a third of such a
+// list, so of three packings -- consecutive, nested (below), padded (every remainder alone in a k-step of its own pattern) -- the
+// one with the fewest k-steps wins, among equals the one with the fewest k-steps that need vector arithmetic in the grouped loop,
+// then the one with the fewest multiply-adds, then the earlier in this order.
+enum { PACK_CONSECUTIVE = 0, PACK_FEWEST = 1 };
+constexpr int kMaxTerms = 4;      // terms per row of a k-step (rom_proj_device.h: the loops' slot count)
+// multiplies / multiply-adds per block that proj_main_grouped's `finish` spends on a k-step of this pattern (build_grouped_tables)
+int kstep_vector_ops(const std::vector<int>& pat) {
+  const int nt = (int)pat.size();
+  if (nt == 1) return 0;                                                         // T_d or T_0 as loaded
+  if (nt == 2 && (pat[0] == 0) != (pat[1] == 0)) return 1;                       // group d: T_d + (1 / theta_d) T_0
+  return nt - (std::find(pat.begin(), pat.end(), 0) == pat.begin() ? 1 : 0);     // group 0: the first coefficient is 1 only for T_0
+}
+struct PackCost {
+  int ksteps = 0, fma_ksteps = 0, fma = 0;
+  bool operator<(const PackCost& o) const { return ksteps != o.ksteps ? ksteps < o.ksteps : fma_ksteps != o.fma_ksteps ? fma_ksteps < o.fma_ksteps : fma < o.fma; }
+};
+PackCost pack_cost(const std::vector<KStep>& ks) {
+  PackCost c;
+  for (const KStep& k : ks) { const int ops = kstep_vector_ops(k.pat); ++c.ksteps; c.fma_ksteps += ops > 0; c.fma += ops; }
+  return c;
+}
+typedef std::vector<std::pair<std::vector<int>, std::vector<int>>> LeftClasses;      // (pattern, its 1..3 left-over rows)
+std::vector<KStep> pack_consecutive(const LeftClasses& cls) {
+  std::vector<KStep> out;
+  KStep cur{{}, {-1, -1, -1, -1}};
+  int fill = 0;
+  auto flush = [&]() { if (fill) out.push_back(cur); cur = KStep{{}, {-1, -1, -1, -1}}; fill = 0; };
+  for (const auto& c : cls)
+    for (int row : c.second) {
+      std::vector<int> u = cur.pat;
+      for (int pp : c.first) if (std::find(u.begin(), u.end(), pp) == u.end()) u.push_back(pp);
+      if (fill == 4 || (int)u.size() > kMaxTerms) { flush(); u = c.first; }
+      cur.pat = u; cur.rows[fill++] = row;
+    }
+  flush();
+  return out;
+}
+std::vector<KStep> pack_padded(const LeftClasses& cls) {
+  std::vector<KStep> out;
+  for (const auto& c : cls) {
+    KStep k{c.first, {-1, -1, -1, -1}};
+    for (size_t i = 0; i < c.second.size() && i < 4; ++i) k.rows[i] = c.second[i];
+    out.push_back(k);
+  }
+  return out;
+}
+// nested: the classes with the longest patterns open k-steps; a class joins the k-step with room whose pattern CONTAINS its own
+// (the shortest such pattern, then the tightest room) -- the k-step then costs what it cost before, the guest's missing terms are
+// zero rows -- and is split over several if need be; what stays partly filled is then merged pairwise, smallest union first,
+// while the union has at most kMaxTerms entries and the rows fit.
+std::vector<KStep> pack_nested(const LeftClasses& cls_in) {
+  struct Bin { std::vector<int> pat, rows; };
+  LeftClasses cls(cls_in);
+  for (auto& c : cls) std::sort(c.first.begin(), c.first.end());
+  std::stable_sort(cls.begin(), cls.end(), [](const auto& x, const auto& y) { return x.first.size() > y.first.size(); });
+  std::vector<Bin> bins;
+  for (const auto& c : cls) {
+    size_t next = 0;
+    while (next < c.second.size()) {
+      const int pending = (int)(c.second.size() - next);
+      int best = -1;
+      for (int b = 0; b < (int)bins.size(); ++b) {
+        const int room = 4 - (int)bins[b].rows.size();
+        if (room <= 0 || !std::includes(bins[b].pat.begin(), bins[b].pat.end(), c.first.begin(), c.first.end())) continue;
+        if (best < 0) { best = b; continue; }
+        const int broom = 4 - (int)bins[best].rows.size();
+        if (bins[b].pat.size() != bins[best].pat.size()) { if (bins[b].pat.size() < bins[best].pat.size()) best = b; continue; }
+        const bool fits = room >= pending, bfits = broom >= pending;
+        if (fits != bfits ? fits : (fits ? room < broom : room > broom)) best = b;
+      }
+      if (best < 0) { bins.push_back({c.first, {}}); best = (int)bins.size() - 1; }
+      while (next < c.second.size() && bins[best].rows.size() < 4) bins[best].rows.push_back(c.second[next++]);
+    }
+  }
+  for (;;) {
+    int bi = -1, bj = -1; size_t bu = 0;
+    for (int i = 0; i < (int)bins.size(); ++i)
+      for (int j = i + 1; j < (int)bins.size(); ++j) {
+        if (bins[i].rows.size() + bins[j].rows.size() > 4) continue;
+        std::vector<int> u;
+        std::set_union(bins[i].pat.begin(), bins[i].pat.end(), bins[j].pat.begin(), bins[j].pat.end(), std::back_inserter(u));
+        if ((int)u.size() > kMaxTerms) continue;
+        if (bi < 0 || u.size() < bu) { bi = i; bj = j; bu = u.size(); }
+      }
+    if (bi < 0) break;
+    std::vector<int> u;
+    std::set_union(bins[bi].pat.begin(), bins[bi].pat.end(), bins[bj].pat.begin(), bins[bj].pat.end(), std::back_inserter(u));
+    bins[bi].pat = u;
+    bins[bi].rows.insert(bins[bi].rows.end(), bins[bj].rows.begin(), bins[bj].rows.end());
+    bins.erase(bins.begin() + bj);
+  }
+  std::vector<KStep> out;
+  for (const Bin& b : bins) {
+    KStep k{b.pat, {-1, -1, -1, -1}};
+    for (size_t i = 0; i < b.rows.size(); ++i) k.rows[i] = b.rows[i];
+    out.push_back(k);
+  }
+  return out;
+}
+std::vector<KStep> uniform_ksteps(const finrom_rom_desc* a, const std::vector<int>& order, int rule = PACK_CONSECUTIVE) {
   std::vector<KStep> ksteps;
   auto pattern = [&](int row) { return std::vector<int>(a->term_p + a->row_ptr[row], a->term_p + a->row_ptr[row + 1]); };
   std::vector<int> byp(order);
   std::stable_sort(byp.begin(), byp.end(), [&](int x, int y) { return pattern(x) < pattern(y); });
-  std::vector<int> left;
+  LeftClasses left;
   for (size_t i0 = 0; i0 < byp.size();) {
     size_t i1 = i0;
     while (i1 < byp.size() && pattern(byp[i1]) == pattern(byp[i0])) ++i1;
     size_t i = i0;
     for (; i + 4 <= i1; i += 4) ksteps.push_back({pattern(byp[i]), {byp[i], byp[i + 1], byp[i + 2], byp[i + 3]}});
-    for (; i < i1; ++i) left.push_back(byp[i]);
+    if (i < i1) left.push_back({pattern(byp[i]), std::vector<int>(byp.begin() + i, byp.begin() + i1)});
     i0 = i1;
   }
-  // leftovers: consecutive rows share a k-step as long as the union of their patterns has at most ROM_MAX_NT entries
-  KStep cur{{}, {-1, -1, -1, -1}};
-  int fill = 0;
-  auto flush = [&]() { if (fill) ksteps.push_back(cur); cur = KStep{{}, {-1, -1, -1, -1}}; fill = 0; };
-  for (int row : left) {
-    std::vector<int> u = cur.pat;
-    for (int pp : pattern(row)) if (std::find(u.begin(), u.end(), pp) == u.end()) u.push_back(pp);
-    if (fill == 4 || (int)u.size() > 4) { flush(); u = pattern(row); }
-    cur.pat = u; cur.rows[fill++] = row;
+  std::vector<KStep> packed = pack_consecutive(left);
+  if (rule == PACK_FEWEST) {
+    for (const std::vector<KStep>& cand : {pack_nested(left), pack_padded(left)})
+      if (pack_cost(cand) < pack_cost(packed)) packed = cand;
   }
-  flush();
+  ksteps.insert(ksteps.end(), packed.begin(), packed.end());
   std::stable_sort(ksteps.begin(), ksteps.end(), [](const KStep& x, const KStep& y) { return x.pat.size() > y.pat.size(); });
   return ksteps;
 }
@@ -1214,7 +1314,7 @@ std::vector<KStep> uniform_ksteps(const finrom_rom_desc* a, const std::vector<in
 // one the ungrouped loop forms, up to rounding.  Everything else (rows that touch two parameters, merged leftovers) comes
 // first, at scale 1, with the usual coefficients.  The per-sample scalars (1, theta, 1 / theta, the rescale factors) are
 // one row of RomDev::ext, filled by rom_ext_kernel ahead of the projection kernel; the records name them by index.
-struct GroupedTables { std::vector<double> tvg; std::vector<int> kmg, def; int nkg = 0, n_ext = 0, ext_final = 0; };
+struct GroupedTables { std::vector<double> tvg; std::vector<int> kmg, def; int nkg = 0, n_ext = 0, ext_final = 0, live = 0, fma_ksteps = 0; };
 // kclass (the half list of a mirror-symmetric ROM, DESIGN 4b'): per k-step 0 = rows that count twice (left of the symmetry line),
 // 1 = rows that count once (on it).  The k-steps that count twice all come first; the factor of the record that opens the first
 // k-step that counts once -- or the final factor if there is none -- carries an exact 2 (bit 1 of its ext_def flags), so the
@@ -1289,6 +1389,8 @@ bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ks
   while (nkg % 3) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); ++nkg; }
   for (int k = 0; k < 8; ++k) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); }
   out.def = def; out.nkg = nkg; out.n_ext = n_ext; out.ext_final = base + nfac - 1;
+  out.live = (int)gs.size(); out.fma_ksteps = 0;
+  for (const GStep& g : gs) out.fma_ksteps += kstep_vector_ops(g.pat) > 0;
   return true;
 }
 
@@ -1317,15 +1419,18 @@ int validate_rom_mirror(const finrom_rom_desc* a, int n_full, const int32_t* row
   return 0;
 }
 
-// the half list's k-steps: rows that count twice and rows that count once never share a k-step
+// the half list's k-steps: rows that count twice and rows that count once never share a k-step.  A descriptor with rows that have no
+// terms is the SHORT list (engine.py: mirror_skip_rows dropped them): its leftovers are packed for the fewest k-steps (PACK_FEWEST);
+// a descriptor without such rows keeps the list it always had.
 std::vector<KStep> mirror_ksteps(const finrom_rom_desc* a, const double* row_weight, std::vector<int>& kclass) {
   std::vector<KStep> ksteps;
   kclass.clear();
   const std::vector<int> order = rows_by_term_count(a);
+  const int rule = (int)order.size() < a->n ? PACK_FEWEST : PACK_CONSECUTIVE;
   for (int cls = 0; cls < 2; ++cls) {
     std::vector<int> part;
     for (int row : order) if ((row_weight[row] == 2.0) == (cls == 0)) part.push_back(row);
-    for (const KStep& ks : uniform_ksteps(a, part)) { ksteps.push_back(ks); kclass.push_back(cls); }
+    for (const KStep& ks : uniform_ksteps(a, part, rule)) { ksteps.push_back(ks); kclass.push_back(cls); }
   }
   return ksteps;
 }
@@ -1367,6 +1472,23 @@ int finrom_rom_mirror_tables(const finrom_rom_desc* a, const double* row_weight,
   if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
   if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
   if (ext_def) std::memcpy(ext_def, g.def.data(), g.def.size() * sizeof(int));
+  return 0;
+}
+
+// Host only: what the half list of this descriptor multiplies -- rows with terms, k-steps before the padding to a multiple of three,
+// and how many of those need vector arithmetic (0, 0, 0 where finrom_rom_mirror_tables reports no grouped form).
+int finrom_rom_mirror_counts(const finrom_rom_desc* a, const double* row_weight, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps) {
+  if (!a || !row_weight || !live_rows || !ksteps || !fma_ksteps) { set_error("rom_mirror_counts: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  for (int i = 0; i < a->n; ++i)
+    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
+  const int NB = (a->r + 15) / 16, rp = 16 * NB;
+  GroupedTables g;
+  std::vector<int> kclass;
+  const std::vector<KStep> ks = mirror_ksteps(a, row_weight, kclass);
+  *live_rows = 0; *ksteps = 0; *fma_ksteps = 0;
+  if (NB > 5 || !build_grouped_tables(a, ks, rp, g, &kclass)) return 0;
+  *live_rows = (int32_t)rows_by_term_count(a).size(); *ksteps = g.live; *fma_ksteps = g.fma_ksteps;
   return 0;
 }
 
@@ -1449,6 +1571,7 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
     // ---- the same k-steps grouped by their leading parameter (build_grouped_tables above; proj_main_grouped, NB <= 5) ------
     d.n_ext = 0; d.nkg = 0; d.ext_final = 0; d.ext = nullptr;
     d.nkg_m = 0; d.kmg_m = 0; d.ext_final_m = 0; d.twin = nullptr;
+    d.nkg_s = 0; d.kmg_s = 0; d.ext_final_s = 0; d.short_lo = 0.0; d.short_hi = 0.0;
     if (NB <= 5 && getenv("FINROM_PROJ_UNGROUPED") == nullptr) {
       GroupedTables gt;
       if (build_grouped_tables(a, ksteps, rp, gt)) {
@@ -1501,6 +1624,29 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
   return 0;
 }
 
+// a half list (finrom_rom_set_mirror / _short) appended behind the handle's grouped tables: records, rows and factors go behind
+// what is there, everything is uploaded again; nd gets the new arrays and n_ext, kmg0 = where the list's records start
+struct HostTables { std::vector<double> tvg; std::vector<int> kmg, def; };
+static int append_half_list(finrom_rom_t h, const finrom_rom_desc* a, const double* row_weight, RomDev& nd, GroupedTables& g, int& kmg0,
+                            HostTables& next, const char* who) {
+  std::vector<int> kclass;
+  const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
+  const int slot0 = (int)(h->tvg_host.size() / ((size_t)4 * nd.rp));
+  if (!build_grouped_tables(a, ksteps, nd.rp, g, &kclass, slot0, nd.n_ext)) { set_error(std::string(who) + ": the half descriptor has no grouped form"); return FINROM_ERR_UNSUPPORTED; }
+  std::vector<double> tvg(h->tvg_host); tvg.insert(tvg.end(), g.tvg.begin(), g.tvg.end());
+  std::vector<int> kmg(h->kmg_host); kmg.insert(kmg.end(), g.kmg.begin(), g.kmg.end());
+  std::vector<int> def(h->def_host); def.insert(def.end(), g.def.begin(), g.def.end());
+  if (tvg.size() * sizeof(double) > (size_t)0x7FFFFFF0) { set_error(std::string(who) + ": tables too large"); return FINROM_ERR_UNSUPPORTED; }
+  int rc = up(h->owned, &nd.tvg, tvg.data(), tvg.size());
+  if (!rc) rc = up(h->owned, &nd.kmg, kmg.data(), kmg.size());
+  if (!rc) rc = up(h->owned, &nd.ext_def, def.data(), def.size());
+  if (rc) return rc;
+  kmg0 = (int)h->kmg_host.size();
+  nd.tvg_bytes = (int)(tvg.size() * sizeof(double)); nd.n_ext = g.n_ext;
+  next.tvg.swap(tvg); next.kmg.swap(kmg); next.def.swap(def);      // (the caller commits them with nd once nothing can fail any more)
+  return 0;
+}
+
 int finrom_rom_set_mirror(finrom_rom_t h, const finrom_rom_desc* a, const int32_t* row_node, const double* row_weight,
                           const int32_t* theta_twin) {
   if (!h || !a) { set_error("rom_set_mirror: null argument"); return FINROM_ERR_ARG; }
@@ -1511,23 +1657,44 @@ int finrom_rom_set_mirror(finrom_rom_t h, const finrom_rom_desc* a, const int32_
   // the one-wave grouped kernel is the only form that walks the half list
   if (d.NB > 5 || d.nkg == 0) { set_error("rom_set_mirror: the handle has no grouped form (r > 80, FINROM_PROJ_UNGROUPED, nothing to group)"); return FINROM_ERR_UNSUPPORTED; }
   GroupedTables g;
-  std::vector<int> kclass;
-  const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
-  const int slot0 = (int)(h->tvg_host.size() / ((size_t)4 * d.rp));
-  if (!build_grouped_tables(a, ksteps, d.rp, g, &kclass, slot0, d.n_ext)) { set_error("rom_set_mirror: the half descriptor has no grouped form"); return FINROM_ERR_UNSUPPORTED; }
-  std::vector<double> tvg(h->tvg_host); tvg.insert(tvg.end(), g.tvg.begin(), g.tvg.end());
-  std::vector<int> kmg(h->kmg_host); kmg.insert(kmg.end(), g.kmg.begin(), g.kmg.end());
-  std::vector<int> def(h->def_host); def.insert(def.end(), g.def.begin(), g.def.end());
-  if (tvg.size() * sizeof(double) > (size_t)0x7FFFFFF0) { set_error("rom_set_mirror: tables too large"); return FINROM_ERR_UNSUPPORTED; }
+  int kmg0 = 0;
   RomDev nd = d;
-  int rc = up(h->owned, &nd.tvg, tvg.data(), tvg.size());
-  if (!rc) rc = up(h->owned, &nd.kmg, kmg.data(), kmg.size());
-  if (!rc) rc = up(h->owned, &nd.ext_def, def.data(), def.size());
-  if (!rc) rc = up(h->owned, &nd.twin, theta_twin, (size_t)d.P);
-  if (rc) return rc;                                     // (the handle keeps its tables; what was uploaded is freed with it)
-  nd.tvg_bytes = (int)(tvg.size() * sizeof(double));
-  nd.kmg_m = (int)h->kmg_host.size(); nd.nkg_m = g.nkg; nd.n_ext = g.n_ext; nd.ext_final_m = g.ext_final;
+  HostTables next;
+  if (int rc = append_half_list(h, a, row_weight, nd, g, kmg0, next, "rom_set_mirror")) return rc;
+  if (int rc = up(h->owned, &nd.twin, theta_twin, (size_t)d.P)) return rc;      // (the handle keeps its tables; what was uploaded is freed with it)
+  nd.kmg_m = kmg0; nd.nkg_m = g.nkg; nd.ext_final_m = g.ext_final;
   d = nd;
+  h->tvg_host.swap(next.tvg); h->kmg_host.swap(next.kmg); h->def_host.swap(next.def);
+  h->mirror_n = a->n;
+  h->mirror_counts[0][0] = (int)rows_by_term_count(a).size(); h->mirror_counts[0][1] = g.live; h->mirror_counts[0][2] = g.fma_ksteps;
+  return 0;
+}
+
+int finrom_rom_set_mirror_short(finrom_rom_t h, const finrom_rom_desc* a, const double* row_weight, double theta_lo, double theta_hi) {
+  if (!h || !a || !row_weight) { set_error("rom_set_mirror_short: null argument"); return FINROM_ERR_ARG; }
+  RomDev& d = h->d;
+  if (d.nkg_m == 0) { set_error("rom_set_mirror_short: finrom_rom_set_mirror comes first"); return FINROM_ERR_ARG; }
+  if (d.nkg_s > 0) { set_error("rom_set_mirror_short: already installed"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  if (a->r != d.r || a->P != d.P || a->n != h->mirror_n) { set_error("rom_set_mirror_short: sizes differ from the half descriptor's"); return FINROM_ERR_ARG; }
+  if (!(theta_lo > 0.0 && theta_lo <= theta_hi)) { set_error("rom_set_mirror_short: need 0 < theta_lo <= theta_hi"); return FINROM_ERR_ARG; }
+  for (int i = 0; i < a->n; ++i)
+    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
+  GroupedTables g;
+  int kmg0 = 0;
+  RomDev nd = d;
+  HostTables next;
+  if (int rc = append_half_list(h, a, row_weight, nd, g, kmg0, next, "rom_set_mirror_short")) return rc;
+  nd.kmg_s = kmg0; nd.nkg_s = g.nkg; nd.ext_final_s = g.ext_final; nd.short_lo = theta_lo; nd.short_hi = theta_hi;
+  d = nd;
+  h->tvg_host.swap(next.tvg); h->kmg_host.swap(next.kmg); h->def_host.swap(next.def);
+  h->mirror_counts[1][0] = (int)rows_by_term_count(a).size(); h->mirror_counts[1][1] = g.live; h->mirror_counts[1][2] = g.fma_ksteps;
+  return 0;
+}
+
+int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps) {
+  if (!h || !live_rows || !ksteps || !fma_ksteps || which < 0 || which > 1) { set_error("rom_mirror_info: bad argument"); return FINROM_ERR_ARG; }
+  *live_rows = h->mirror_counts[which][0]; *ksteps = h->mirror_counts[which][1]; *fma_ksteps = h->mirror_counts[which][2];      // (zeros: not installed)
   return 0;
 }
 
@@ -1619,7 +1786,7 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
   RomDev d = h->d;
   d.ext = nullptr;
-  if (!mirror) d.nkg_m = 0;
+  if (!mirror) d.nkg_m = d.nkg_s = 0;
   if (d.nkg > 0 && S > 0 && (roomy || !rom_splitk_applies(d, S))) {      // the grouped main loop: room for the samples' scalars
     if (int rc = h->ext.reserve((size_t)S * d.n_ext * sizeof(double))) return rc;
     d.ext = (double*)h->ext.p;

@@ -179,6 +179,12 @@ struct RomDev {
   int nkg_m;                            // multiple of 3; 0: no half list (on this handle, or in this call)
   int kmg_m, ext_final_m;
   const int* twin;                      // [P]
+  // the SHORT half list (finrom_rom_set_mirror_short, DESIGN 4b''): a third list, the half list without the rows that are zero up
+  // to rounding, behind the half list in the same arrays; a mirror-symmetric sample walks it instead of the half list when every
+  // parameter lies in [short_lo, short_hi], the range over which the caller's gate measured what leaving those rows out costs
+  int nkg_s;                            // multiple of 3; 0: no short list (on this handle, or in this call)
+  int kmg_s, ext_final_s;
+  double short_lo, short_hi;
   // rows with a non-zero load F (root nodes): slot-major padded r-vectors (4 per slot) with the theta index of each
   // (0 = the constant 1), a runtime term count
   int rhs_nk, rhs_nt;

@@ -1081,9 +1081,9 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
                                               double* __restrict__ qoi_r = nullptr, double* slab = nullptr,
                                               const double* __restrict__ theta_s = nullptr, const int* __restrict__ kpat = nullptr,
                                               int kpart = 0, int kparts = 1, const RomGradArgs* ga = nullptr, double* mt_lds = nullptr,
-                                              const double* __restrict__ ext_s = nullptr, bool half = false) {
+                                              const double* __restrict__ ext_s = nullptr, int half = 0) {
   // GR with ext_s: the grouped main loop -- kpat is then RomDev::kmg and ext_s the sample's row of RomDev::ext
-  // (half: kpat is the half list of a mirror-symmetric sample, RomDev::kmg + kmg_m)
+  // (half: 1 = kpat is the half list of a mirror-symmetric sample, RomDev::kmg + kmg_m; 2 = its short list, kmg + kmg_s)
   // kparts > 1 (NW == 1, small batches): the sample's k-steps are split over the kparts waves of the workgroup, the partial
   // block triangles are summed through LDS (`slab`) in a fixed order and wave 0 alone runs the epilogue
   constexpr int NTL = (NB * (NB + 1) / 2 + NW - 1) / NW;
@@ -1099,7 +1099,8 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
     proj_main_uniform_mw<NB, NW, W, HF>(p, kpat, theta_s, q, c, lane, slab, acc);
   } else {
     if constexpr (NW == 1 && GR) {
-      if (ext_s != nullptr) proj_main_grouped<NB>(p, kpat, ext_s, q, c, acc, half ? p.nkg_m : p.nkg, half ? p.ext_final_m : p.ext_final);
+      if (ext_s != nullptr) proj_main_grouped<NB>(p, kpat, ext_s, q, c, acc, half == 2 ? p.nkg_s : half ? p.nkg_m : p.nkg,
+                                                       half == 2 ? p.ext_final_s : half ? p.ext_final_m : p.ext_final);
       else proj_main_uniform<NB>(p, p.ext != nullptr ? p.kmeta : kpat, theta_s, q, c, acc, p.nku);      // (kpat is RomDev::kmg when the launch is a grouped one)
     } else if constexpr (NW == 1) {
       const int per = ((p.nku + kparts - 1) / kparts + 1) / 2 * 2, k0 = kpart * per;
@@ -1337,7 +1338,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
   const double* theta_u = theta_s;
   if constexpr (NW == 1) {
     const double* ext_s = nullptr;
-    bool half = false;
+    int half = 0;
     if constexpr (GR) {
       // (the grouped form divides by the conductivities: a sample with a zero, tiny (< 1e-60), huge (> 1e60) or non-finite one
       // takes the ungrouped loop -- same sums as a handle without the grouped tables)
@@ -1351,12 +1352,14 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
         // (the FOM's mirror test; the sub-fin averages of a mirrored field agree to 1.7e-15) walks it; NaN fails the test
         if (p.nkg_m > 0) {
           const double tt = __shfl(tl, lane < p.P ? p.twin[lane] : lane);
-          half = __ballot(!(__builtin_fabs(tl - tt) <= 1e-13 * __builtin_fmax(__builtin_fabs(tl), __builtin_fabs(tt)))) == 0;
+          half = __ballot(!(__builtin_fabs(tl - tt) <= 1e-13 * __builtin_fmax(__builtin_fabs(tl), __builtin_fabs(tt)))) == 0 ? 1 : 0;
+          // ... and the short list when every parameter lies in the range its gate covered (finrom_rom_set_mirror_short)
+          if (half && p.nkg_s > 0 && __ballot(lane < p.P && !(tl >= p.short_lo && tl <= p.short_hi)) == 0) half = 2;
         }
       }
     }
     rom_proj_body<NB, 1, 0, false, GR, false, RM>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
-                                       half ? kpat + __builtin_amdgcn_readfirstlane(p.kmg_m) : kpat, 0, 1, nullptr,
+                                       half ? kpat + __builtin_amdgcn_readfirstlane(half == 2 ? p.kmg_s : p.kmg_m) : kpat, 0, 1, nullptr,
                                        NB <= 5 ? mt_sw + wave * ROM_SW_LDS : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {
     switch (wave % 4) {

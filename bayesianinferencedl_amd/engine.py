@@ -506,20 +506,26 @@ class RomEngine:
         h = C.c_void_p()
         check(lib().finrom_rom_create(C.byref(d), C.byref(h)), "finrom_rom_create")
         self._h = h
-        self.mirror_eps = None                            # set_mirror: the gate's measured value
+        self.mirror_eps = None                            # set_mirror: the gate's measured value (dropped rows counted)
+        self.mirror_eps_all_rows = None                   # ... and the value without dropped rows
+        self.mirror_dropped = 0                           # rows the installed half list leaves out (mirror_skip_rows)
+        self.mirror_dropped_max = 0.0                     # ... and the largest of them, relative to the largest row
         self.mirror = False
 
     # ---- the half form of a mirror-symmetric reduced model (DESIGN 4b', finrom_rom_set_mirror) ----------------------------------
     MIRROR_EPS_GATE = 1e-9       # a hundredth of the rtol (1e-7) at which the tests equate the qoi_r of two projection forms
     MIRROR_PROBES = 16
+    MIRROR_PROBE_RANGE = (0.1, 10.0)       # the dataset's range: where the probes lie, and where the short list is offered
 
     @staticmethod
-    def mirror_probe_eps(tables, perm, theta_twin, nprobe=16, seed=0, low=0.1, high=10.0):
+    def mirror_probe_eps(tables, perm, theta_twin, nprobe=16, seed=0, low=MIRROR_PROBE_RANGE[0], high=MIRROR_PROBE_RANGE[1], drop=None):
         """How far from mirror-symmetric is the basis, in the metric that matters?  tables[p] = A_p Phi (p = 0: the constant
         term); with perm the mesh's mirror permutation and theta_twin the parameters' (0-based), A_p Phi_s = (tables[p] +
         tables[twin p][perm]) / 2 and A_p Phi_a is the rest.  For mirror-symmetric theta psi^T psi = A_s + D with A_s = psi_s^T psi_s
         and D = psi_a^T psi_a (the cross terms vanish); dropping D changes w_r by at most eps = lambda_max(D, A_s) relative in the
-        energy norm.  -> the largest eps over `nprobe` seeded probes, log-uniform over [low, high] per mirror pair."""
+        energy norm.  -> the largest eps over `nprobe` seeded probes, log-uniform over [low, high] per mirror pair.
+        drop (bool per row of the FULL mesh, closed under perm): rows of psi_s the half list leaves out as well (mirror_skip_rows);
+        their sum joins D and leaves A_s: eps = lambda_max(psi_a^T psi_a + psi_s[drop]^T psi_s[drop], psi_s[kept]^T psi_s[kept])."""
         import scipy.linalg as sla
         P = len(theta_twin)
         tw1 = np.concatenate([[0], np.asarray(theta_twin) + 1])
@@ -532,19 +538,25 @@ class RomEngine:
             th = th[np.minimum(np.arange(P), np.asarray(theta_twin))]          # the same value in both of a pair
             th1 = np.concatenate([[1.0], th])
             ps = sum(th1[p] * Ts[p] for p in range(P + 1)); pa = sum(th1[p] * Ta[p] for p in range(P + 1))
+            D = pa.T @ pa
+            if drop is not None:
+                D = D + ps[drop].T @ ps[drop]
+                ps = ps[~drop]
             try:
                 L = np.linalg.cholesky(ps.T @ ps)
             except np.linalg.LinAlgError:                   # psi_s alone is rank-deficient: nothing like a symmetric basis
                 return float("inf"), Ts
-            M = sla.solve_triangular(L, sla.solve_triangular(L, pa.T @ pa, lower=True).T, lower=True)
+            M = sla.solve_triangular(L, sla.solve_triangular(L, D, lower=True).T, lower=True)
             worst = max(worst, float(np.linalg.eigvalsh(0.5 * (M + M.T)).max()))
         return worst, Ts
 
     @staticmethod
-    def mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs):
+    def mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs, dropped=None):
         """The half descriptor: rows `rows` (left of the symmetry line: weight 2, on it: weight 1) of the symmetrised tables Ts,
         the two tables of a mirror pair merged under the smaller index (the samples that use it carry the same value in both);
-        rhs = weight F.  -> (finrom_rom_desc, the arrays it borrows, row_node, row_weight, theta_twin as ctypes pairs)."""
+        rhs = weight F.  dropped (bool per half row, mirror_skip_rows): these rows stay in the descriptor with node and weight but
+        get no terms (row_ptr[i + 1] == row_ptr[i]), so no k-step multiplies them.
+        -> (finrom_rom_desc, the arrays it borrows, row_node, row_weight, theta_twin as ctypes pairs)."""
         rows = np.asarray(rows, np.int64)
         merged = []
         for p in range(P + 1):
@@ -552,6 +564,8 @@ class RomEngine:
             if t < p:
                 continue
             M = Ts[p][rows] if t == p else Ts[p][rows] + Ts[t][rows]
+            if dropped is not None and np.any(dropped):
+                M = np.where(np.asarray(dropped, bool)[:, None], 0.0, M)
             merged.append((p, M))
         row_ptr, term_p, tv = RomEngine.pack_terms(len(rows), r, merged)
         keep = [i32(row_ptr), i32(term_p), f64(tv), f64(np.asarray(weight, float) * np.asarray(rhs, float)[rows]),
@@ -560,17 +574,59 @@ class RomEngine:
                     rhs=keep[3][1], obs_phi=None)
         return d, keep
 
+    MIRROR_SKIP_TAUS = (1e-6, 1e-7, 1e-8, 1e-9)       # row-size thresholds tried in this order (mirror_skip_rows)
+
+    @staticmethod
+    def mirror_skip_rows(tables, Ts, rhs, perm, rows, theta_twin):
+        """Which rows of the half list are zero up to rounding for EVERY theta (DESIGN 4b'', the discrete-harmonic rows: a node whose
+        patch lies inside one sub-domain and off the Robin boundary has (K_d w)_i = 0 for every snapshot w, hence for every POD
+        vector)?  Row size rn_i = sqrt(sum_p |Ts[p][i]|^2); candidates are the rows with rn_i <= tau max rn that carry no load.  The
+        first tau of MIRROR_SKIP_TAUS whose combined probe value -- mirror_probe_eps with the candidates (and their twins) moved
+        from A_s to D -- is at most MIRROR_EPS_GATE decides.  -> (dropped: bool per half row, combined eps, tau, the largest dropped
+        rn_i / max rn) or (all False, None, None, 0.0) when no tau passes or none has a candidate."""
+        rows = np.asarray(rows, np.int64)
+        rn = np.sqrt(sum((np.asarray(T)[rows] ** 2).sum(axis=1) for T in Ts))
+        none = np.zeros(len(rows), bool)
+        if not rn.max() > 0.0:
+            return none, None, None, 0.0
+        loaded = np.asarray(rhs, float)[rows] != 0.0
+        for tau in RomEngine.MIRROR_SKIP_TAUS:
+            cand = (rn <= tau * rn.max()) & ~loaded
+            if not cand.any():
+                break
+            drop = np.zeros(np.asarray(perm).shape[0], bool)
+            drop[rows[cand]] = True
+            drop[np.asarray(perm)[rows[cand]]] = True
+            eps = RomEngine.mirror_probe_eps(tables, perm, theta_twin, nprobe=RomEngine.MIRROR_PROBES, drop=drop)[0]
+            if eps <= RomEngine.MIRROR_EPS_GATE:
+                return cand, eps, tau, float(rn[cand].max() / rn.max())
+        return none, None, None, 0.0
+
     @staticmethod
     def mirror_form(r, P, tables, rhs, perm, rows, weight, theta_twin):
         """Host only.  The half form of one reduced model, gated: (b) r <= 80 (the grouped one-wave kernel), (c) the probes' eps at
         most MIRROR_EPS_GATE, (d) FINROM_ROM_NO_MIRROR not set; (a), the operator's own symmetry, is the caller's test
-        (FomEngine.mirror_rows with col_twin).  -> dict(eps, installs, and when it installs: desc, keep) or None ((b) / (d))."""
+        (FomEngine.mirror_rows with col_twin).  A form that installs also gets a SHORT descriptor without the rows mirror_skip_rows
+        selects, under the same gate (FINROM_ROM_KEEP_ROWS=1: none); the gate's probes lie in MIRROR_PROBE_RANGE, so only samples
+        inside that range walk the short list, every other mirror-symmetric sample the half list with all rows.
+        -> dict(eps: the gated value with the dropped rows counted, eps_all_rows: without them, dropped: their number, dropped_rows,
+        tau, dropped_max: the largest dropped row's size relative to the largest row, installs, and when it installs: desc, keep,
+        with dropped rows also desc_short, keep_short) or None ((b) / (d))."""
         if _os.environ.get("FINROM_ROM_NO_MIRROR") is not None or r > 80:
             return None
         eps, Ts = RomEngine.mirror_probe_eps(tables, perm, theta_twin, nprobe=RomEngine.MIRROR_PROBES)
-        form = {"eps": eps, "installs": bool(eps <= RomEngine.MIRROR_EPS_GATE), "Ts": Ts}
+        form = {"eps": eps, "eps_all_rows": eps, "installs": bool(eps <= RomEngine.MIRROR_EPS_GATE), "Ts": Ts,
+                "dropped": 0, "dropped_rows": np.zeros(len(rows), bool), "tau": None, "dropped_max": 0.0}
         if form["installs"]:
-            form["desc"], form["keep"] = RomEngine.mirror_descriptor(np.asarray(perm).shape[0], r, P, Ts, rows, weight, theta_twin, rhs)
+            if _os.environ.get("FINROM_ROM_KEEP_ROWS") is None:
+                dropped, eps_c, tau, largest = RomEngine.mirror_skip_rows(tables, Ts, rhs, perm, rows, theta_twin)
+                if eps_c is not None:
+                    form.update(eps=eps_c, dropped=int(dropped.sum()), dropped_rows=dropped, tau=tau, dropped_max=largest)
+            n = np.asarray(perm).shape[0]
+            form["desc"], form["keep"] = RomEngine.mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs)
+            if form["dropped"]:
+                form["desc_short"], form["keep_short"] = RomEngine.mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs,
+                                                                                 form["dropped_rows"])
         return form
 
     def set_mirror(self, form):
@@ -579,6 +635,7 @@ class RomEngine:
         if form is None:
             return False
         self.mirror_eps = form["eps"]
+        self.mirror_eps_all_rows = form["eps_all_rows"]
         if not form["installs"]:
             return False
         keep = form["keep"]
@@ -587,7 +644,28 @@ class RomEngine:
             return False
         check(rc, "finrom_rom_set_mirror")
         self.mirror = True
+        if "desc_short" in form:                          # in-range samples walk the list without the dropped rows
+            lo, hi = self.MIRROR_PROBE_RANGE
+            rc = lib().finrom_rom_set_mirror_short(self._h, C.byref(form["desc_short"]), form["keep_short"][5][1],
+                                                   lo * (1.0 - 1e-12), hi * (1.0 + 1e-12))
+            if rc != _ffi.ERR_UNSUPPORTED:                # (no grouped form for the short descriptor: the half list serves everybody)
+                check(rc, "finrom_rom_set_mirror_short")
+                self.mirror_dropped = form["dropped"]
+                self.mirror_dropped_max = form["dropped_max"]
         return True
+
+    def mirror_info(self, short=None):
+        """(rows with terms, k-steps, k-steps with vector arithmetic) of a list on the handle as the native builder counts them
+        (finrom_rom_mirror_info): short=True the short list, False the half list with all rows, None the one in-range samples
+        walk (the short list if installed, else the half list); zeros where none is installed."""
+        def get(which):
+            o = [C.c_int32() for _ in range(3)]
+            check(lib().finrom_rom_mirror_info(self._h, which, *[C.byref(x) for x in o]), "finrom_rom_mirror_info")
+            return tuple(x.value for x in o)
+        if short is None:
+            s = get(1)
+            return s if s[1] else get(0)
+        return get(1 if short else 0)
 
     def last_form(self):
         """'half' when the most recent projection launch of solve / solve_pairs offered its samples the half list (each sample

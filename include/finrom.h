@@ -365,6 +365,23 @@ int finrom_rom_mirror_validate(const finrom_rom_desc* desc, int32_t n_full, cons
  * a flag word, bit 0 = squared, bit 1 = times two. */
 int finrom_rom_mirror_tables(const finrom_rom_desc* desc, const double* row_weight, int32_t* nkg, int32_t* n_ext, int32_t* ext_final,
                              int64_t* n_slots, int32_t* kmg, double* tvg, int32_t* ext_def);
+/* The SHORT half list (DESIGN.md 4b''; additive): a THIRD list beside the half list, from a copy of the half descriptor in which a
+ * row that is zero up to rounding for every theta has no terms (row_ptr[i + 1] == row_ptr[i]) -- engine.py's
+ * RomEngine.mirror_skip_rows selects such rows under the half form's gate, which probes parameters in [theta_lo, theta_hi].  A
+ * sample that would walk the half list walks the short one instead when every parameter lies in that range; outside it the rows
+ * left out are not covered by the gate (a conductivity contrast of 1e4 moves qoi_r by 1e-6), and the sample keeps the half list.
+ * finrom_rom_set_mirror comes first; `desc` has its row count and `row_weight` its weights.  A descriptor with term-less rows packs
+ * the rows that do not fill a k-step of their own pattern for the fewest k-steps, among equal counts for the fewest k-steps with
+ * vector arithmetic; one without them keeps the packing of every other list (FINROM_ROM_KEEP_ROWS=1, read by engine.py when the
+ * handle is created: no short descriptor is made).
+ * The counts of what a list multiplies: rows with terms, k-steps before the padding to a multiple of three, k-steps that need a
+ * multiply or multiply-add per block.  finrom_rom_mirror_counts: HOST ONLY, for a descriptor (zeros where it has no grouped
+ * form); finrom_rom_mirror_info: of a list installed on a handle, which = 0 the half list, 1 the short list (zeros: not installed).
+ * (finrom_rom_mirror_tables keeps its signature: its nkg is the padded k-step count, these calls give the rest.) */
+int finrom_rom_set_mirror_short(finrom_rom_t h, const finrom_rom_desc* desc, const double* row_weight, double theta_lo, double theta_hi);
+int finrom_rom_mirror_counts(const finrom_rom_desc* desc, const double* row_weight, int32_t* live_rows, int32_t* ksteps,
+                             int32_t* fma_ksteps);
+int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps);
 /* Which list the most recent projection launch of finrom_rom_solve / finrom_solve_pairs on this handle OFFERED its samples
  * (tests assert on it, like finrom_fom_last_path): FINROM_ROM_FORM_HALF = the launch carried the half list and every sample that
  * passed the per-sample mirror test walked it; FINROM_ROM_FORM_FULL = every sample ran the handle's own tables. */

@@ -1,0 +1,209 @@
+"""The SHORT half list on the device (DESIGN 4b'', RomEngine.mirror_skip_rows): the half list of a mirror-symmetric reduced model
+without the rows of psi that are zero up to rounding for every theta.  Against a handle created with FINROM_ROM_KEEP_ROWS=1 (the
+half list with all its rows) and against the oracle: mirror-symmetric batches inside and outside the probes' range, samples that do
+not mirror, the pair path with five parameters, and a sample with every conductivity zero.
+One cell of the grid runs another kernel: at r = 80 a batch of 64 takes the split-K projection (batches up to 64, r = 49..96), which
+keeps the full list on every handle; there the two handles must return the same bits and say 'full'.  A third size, 301, runs the
+short list at a second batch size for both bases and carries the 32 corners of the gate's range (the probes are log-uniform inside).
+That the short list RAN is shown by the handle's own counts (finrom_rom_mirror_info: fewer k-steps) in every case, and by A_r bits
+that differ wherever they can: a dropped row of relative size x adds at most x^2 relative to an entry of A_r, and below half an ulp
+(x^2 < 2^-53: m = 4, r = 16, whose dropped rows are 1.2e-13 and whose other k-steps are the same ones in the same order) the sum
+rounds to the same bits as the one without it -- measured so; at m = 12, r = 80 (5.8e-8) the bits must differ.
+The short list is offered to samples inside the range the gate probed, [0.1, 10]; see test_extreme_thetas."""
+import itertools
+import os
+
+import numpy as np
+import pytest
+
+from oracle import fin_oracle as O
+from test_gpu_rom_mirror import TWIN, _basis
+
+pytestmark = pytest.mark.gpu
+CASES = [(4, 16, 30), (12, 80, 506)]
+SIZES = [64, 256, 301]                                    # 301: a last workgroup with a single live wave; its first 32 samples are corners
+
+
+def _keeping_rows(make):
+    old = os.environ.get("FINROM_ROM_KEEP_ROWS")
+    os.environ["FINROM_ROM_KEEP_ROWS"] = "1"
+    try:
+        return make()
+    finally:
+        if old is None:
+            del os.environ["FINROM_ROM_KEEP_ROWS"]
+        else:
+            os.environ["FINROM_ROM_KEEP_ROWS"] = old
+
+
+def _mirrored(rng, S, low, high):
+    TH = np.exp(rng.uniform(np.log(low), np.log(high), (S, 9)))
+    return TH[:, np.minimum(np.arange(9), TWIN)]
+
+
+@pytest.fixture(scope="module")
+def cases(problems, spaces):
+    """Per (m, r), once: the basis of five-parameter oracle snapshots, the model with the short list, the model created with the
+    switch set, and per batch size a mirror-symmetric batch in [0.1, 10] with both results."""
+    from bayesianinferencedl_amd.rom.averaged_affine_ROM import AffineROMFin
+    made = {}
+
+    def get(m, r):
+        if (m, r) not in made:
+            prob, V = problems(m), spaces(m)
+            phi = _basis(prob, r, "five")
+            rom = AffineROMFin(V, None, phi)
+            allrows = _keeping_rows(lambda: AffineROMFin(V, None, phi))
+            assert rom._rom.mirror and allrows._rom.mirror
+            runs = {}
+            for S in SIZES:
+                TH = _mirrored(np.random.default_rng(100 * m + r + S), S, 0.1, 10.0)
+                if S == 301:                                 # the 32 corners of the gate's range: every mirror pair at 0.1 or 10
+                    TH[:32] = np.array(list(itertools.product((0.1, 10.0), repeat=5)))[:, np.minimum(np.arange(9), TWIN)]
+                res = rom.forward_nine_param_reduced_batch(TH, want_state=True)
+                ref = allrows.forward_nine_param_reduced_batch(TH, want_state=True)
+                splitk = r >= 49 and S <= 64                 # (the split-K kernel's range: the full list, as before)
+                assert rom._rom.last_form() == allrows._rom.last_form() == ("full" if splitk else "half")
+                runs[S] = (TH, res, ref)
+            made[(m, r)] = (prob, phi, rom, allrows, runs)
+        return made[(m, r)]
+    return get
+
+
+def _compare(res, ref, rom):
+    """info equal; norm(A_r - A_r0) <= 1e-12 norm(A_r0) per sample, not the same bits (see above); qoi_r to rtol 1e-7.
+    -> the two maxima."""
+    assert np.array_equal(np.asarray(res["info"]), np.asarray(ref["info"])) and not np.asarray(res["info"]).any()
+    A, A0 = np.asarray(res["A_r"]), np.asarray(ref["A_r"])
+    dA = np.max(np.linalg.norm(A - A0, axis=(1, 2)) / np.linalg.norm(A0, axis=(1, 2)))
+    dq = np.max(np.abs(np.asarray(res["qoi_r"]) / np.asarray(ref["qoi_r"]) - 1.0))
+    assert dA <= 1e-12, dA
+    assert rom._rom.mirror_info()[1] < (rom._rom.mirror_info()[0] + rom._rom.mirror_dropped + 3) // 4      # the short list ran
+    if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
+        assert not np.array_equal(A, A0)                     # another sum
+    assert np.allclose(np.asarray(res["qoi_r"]), np.asarray(ref["qoi_r"]), rtol=1e-7, atol=0.0), dq
+    return dA, dq
+
+
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_counts_and_gate_on_the_handle(cases, m, r, ndrop):
+    _, _, rom, allrows, _ = cases(m, r)
+    e, e0 = rom._rom, allrows._rom
+    rows, ksteps, fma = e.mirror_info()
+    rows0, ksteps0, fma0 = e0.mirror_info()
+    assert e.mirror_info(short=False) == (rows0, ksteps0, fma0) and e0.mirror_info(short=True) == (0, 0, 0)
+    print(f"m = {m}, r = {r}: dropped {e.mirror_dropped}, eps {e.mirror_eps:.3e} (all rows {e.mirror_eps_all_rows:.3e}); "
+          f"short list {ksteps} k-steps ({fma} with arithmetic) for {rows} rows, all rows {ksteps0} ({fma0}) for {rows0}")
+    assert e.mirror_dropped == ndrop and e0.mirror_dropped == 0
+    assert e.mirror_eps_all_rows <= e.mirror_eps <= 1e-9 and e0.mirror_eps == e0.mirror_eps_all_rows == e.mirror_eps_all_rows
+    assert rows0 - rows == ndrop and (rows + 3) // 4 <= ksteps <= (rows + 3) // 4 + 12 and ksteps < ksteps0
+
+
+@pytest.mark.parametrize("S", SIZES)
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_short_list_matches_all_rows_and_oracle(cases, m, r, ndrop, S):
+    prob, phi, rom, _, runs = cases(m, r)
+    TH, res, ref = runs[S]
+    if r >= 49 and S <= 64:                                  # split-K: no half list on either handle
+        for key in ("A_r", "B_r", "w_r", "qoi_r", "info"):
+            assert np.array_equal(np.asarray(res[key]), np.asarray(ref[key])), key
+        dA = dq = 0.0
+    else:
+        dA, dq = _compare(res, ref, rom)
+    print(f"m = {m}, r = {r}, S = {S}: short vs all rows: max norm(dA_r)/norm(A_r) {dA:.3e}, max rel qoi_r {dq:.3e}")
+    if S == 301:
+        dqc = np.max(np.abs(np.asarray(res["qoi_r"])[:32] / np.asarray(ref["qoi_r"])[:32] - 1.0))
+        print(f"    the 32 corners of [0.1, 10]: max rel qoi_r {dqc:.3e}")
+    ro = O.AffineROMOracle(prob, phi)
+    A, q = np.asarray(res["A_r"]), np.asarray(res["qoi_r"])
+    for s in (0, S // 3, S - 1):
+        w, Ar, _, _ = ro.forward_nine_param_reduced(TH[s], return_parts=True)
+        qo = ro.qoi_reduced(w)
+        assert np.linalg.norm(A[s] - Ar) <= 1e-12 * np.linalg.norm(Ar), s
+        assert np.allclose(q[s], qo, rtol=1e-7, atol=0.0), s
+
+
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_extreme_thetas(cases, m, r, ndrop):
+    """Conductivities between 0.01 and 100, outside the probes' [0.1, 10]: the same comparison holds.  The dropped rows do NOT scale
+    with theta as the kept ones do -- a dropped row of sub-domain d grows with theta_d, the kept rows of another sub-domain with
+    theirs, and walked at a contrast of 1e4 the short list moved qoi_r by 1e-6 at m = 12, r = 80 (measured; bound 1e-7) -- so a
+    sample with a parameter outside the range the gate probed keeps the half list with all rows, decided per sample in the kernel:
+    such samples return the bits of the FINROM_ROM_KEEP_ROWS=1 handle, the samples of the batch inside the range walk the short
+    list."""
+    _, _, rom, allrows, _ = cases(m, r)
+    rng = np.random.default_rng(7 * m + r)
+    TH = _mirrored(rng, 128, 0.01, 100.0)
+    TH[:16] = np.where(rng.random((16, 9)) < 0.5, 0.01, 100.0)[:, np.minimum(np.arange(9), TWIN)]
+    TH[16], TH[17] = 0.01, 100.0
+    TH[18:26] = _mirrored(rng, 8, 0.1, 10.0)
+    TH[26, [0, 8]] = 10.0 * (1.0 + 1e-9)                     # one parameter just outside
+    res = rom.forward_nine_param_reduced_batch(TH, want_state=True)
+    ref = allrows.forward_nine_param_reduced_batch(TH, want_state=True)
+    assert rom._rom.last_form() == allrows._rom.last_form() == "half"
+    dA, dq = _compare(res, ref, rom)
+    print(f"m = {m}, r = {r}, theta in [0.01, 100]: max norm(dA_r)/norm(A_r) {dA:.3e}, max rel qoi_r {dq:.3e}")
+    inside = ((TH >= 0.1) & (TH <= 10.0)).all(axis=1)
+    assert inside[18:26].all() and not inside[:18].any() and not inside[26] and inside.sum() < 64
+    for key in ("A_r", "B_r", "w_r", "qoi_r"):
+        assert np.array_equal(np.asarray(res[key])[~inside], np.asarray(ref[key])[~inside]), key
+    if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
+        assert not np.array_equal(np.asarray(res["A_r"])[inside], np.asarray(ref["A_r"])[inside])
+
+
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_samples_that_do_not_mirror_keep_their_bits(cases, m, r, ndrop):
+    _, _, rom, allrows, runs = cases(m, r)
+    X = runs[256][0][:128].copy()
+    X[1, 8] = X[1, 0] * (1.0 + 1e-10)
+    X[2] = np.random.default_rng(9).uniform(0.1, 10.0, 9)
+    X[40:64] = np.random.default_rng(10).uniform(0.1, 10.0, (24, 9))
+    away = [1, 2] + list(range(40, 64))
+    a = rom.forward_nine_param_reduced_batch(X, want_state=True)
+    b = allrows.forward_nine_param_reduced_batch(X, want_state=True)
+    assert np.array_equal(np.asarray(a["info"]), np.asarray(b["info"]))
+    for key in ("A_r", "B_r", "w_r", "qoi_r"):
+        assert np.array_equal(np.asarray(a[key])[away], np.asarray(b[key])[away]), key
+    assert rom._rom.last_form() == "half"
+    if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
+        assert not np.array_equal(np.asarray(a["A_r"])[0], np.asarray(b["A_r"])[0])
+
+
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_pair_path_with_five_parameters(spaces, cases, m, r, ndrop):
+    from bayesianinferencedl_amd.pairs import FinPairSolver
+    _, phi, rom, allrows, _ = cases(m, r)
+    V = spaces(m)
+    X = np.random.default_rng(3).uniform(0.1, 10.0, (256, 5))
+    ps = FinPairSolver(V, phi, params="five", solver_r=rom)
+    a = ps.solve_pairs(X)
+    assert rom._rom.last_form() == "half" and rom._rom.last_epilogue() == "roomy"
+    b = FinPairSolver(V, phi, params="five", solver=ps.solver, solver_r=allrows).solve_pairs(X)
+    assert allrows._rom.last_form() == "half" and allrows._rom.last_epilogue() == "roomy"
+    for key in ("qoi", "theta", "info"):
+        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), key
+    assert not np.asarray(a["info"]).any()
+    qa, qb = np.asarray(a["qoi_r"]), np.asarray(b["qoi_r"])
+    print(f"m = {m}, r = {r}: pair path, max rel qoi_r {np.max(np.abs(qa / qb - 1.0)):.3e}")
+    assert np.allclose(qa, qb, rtol=1e-7, atol=0.0)
+    if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
+        assert not np.array_equal(qa, qb)
+
+
+@pytest.mark.parametrize("m,r,ndrop", CASES)
+def test_all_zero_conductivities_are_flagged_as_before(cases, m, r, ndrop):
+    """A sample with every conductivity zero cannot be divided by its conductivities: it takes the ungrouped full loop on every
+    handle, so its flag and every output are the bits of the FINROM_ROM_KEEP_ROWS=1 handle.  (Whether it IS flagged depends on the
+    basis: psi is then the Robin term alone, which at m = 4, r = 16 is still positive definite -- info 0 on both handles, measured.)"""
+    _, _, rom, allrows, runs = cases(m, r)
+    X = runs[256][0][:128].copy()
+    X[5] = 0.0
+    a = rom.forward_nine_param_reduced_batch(X, want_state=True)
+    b = allrows.forward_nine_param_reduced_batch(X, want_state=True)
+    ia, ib = np.asarray(a["info"]), np.asarray(b["info"])
+    print(f"m = {m}, r = {r}: info of the all-zero sample {ia[5]} (all rows {ib[5]})")
+    assert np.array_equal(ia, ib) and not np.delete(ia, 5).any()
+    for key in ("A_r", "B_r", "w_r", "qoi_r"):
+        assert np.array_equal(np.asarray(a[key])[5], np.asarray(b[key])[5], equal_nan=True), key
+    ok = np.delete(np.arange(128), 5)
+    assert np.allclose(np.asarray(a["qoi_r"])[ok], np.asarray(b["qoi_r"])[ok], rtol=1e-7, atol=0.0)
