@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 #include <iterator>
+#include <map>
 #include <mutex>
 #include <numeric>
 
@@ -185,6 +186,7 @@ struct finrom_rom_s {
   int mirror_counts[2][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / the short list
   int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
   int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
+  bool short_grouped = getenv("FINROM_ROM_SHORT_GROUPED") != nullptr;      // (A/B, read at creation: the short half list keeps a group per leading parameter, as before group_pays)
   bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
   hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -1190,12 +1192,24 @@ struct KStep { std::vector<int> pat; int rows[4]; };
 enum { PACK_CONSECUTIVE = 0, PACK_FEWEST = 1 };
 constexpr int kMaxTerms = 4;      // terms per row of a k-step (rom_proj_device.h: the loops' slot count)
 // multiplies / multiply-adds per block that proj_main_grouped's `finish` spends on a k-step of this pattern (build_grouped_tables)
-int kstep_vector_ops(const std::vector<int>& pat) {
+// (group0: the k-step sits in segment 0 with its usual coefficients -- a lone theta_d then multiplies its rows)
+int kstep_vector_ops(const std::vector<int>& pat, bool group0 = false) {
   const int nt = (int)pat.size();
-  if (nt == 1) return 0;                                                         // T_d or T_0 as loaded
+  if (nt == 1) return group0 && pat[0] != 0 ? 1 : 0;                             // T_d or T_0 as loaded
   if (nt == 2 && (pat[0] == 0) != (pat[1] == 0)) return 1;                       // group d: T_d + (1 / theta_d) T_0
   return nt - (std::find(pat.begin(), pat.end(), 0) == pat.begin() ? 1 : 0);     // group 0: the first coefficient is 1 only for T_0
 }
+// When a leading parameter is worth a group (build_grouped_tables, scale_free).  The grouped form pays for itself on the k-steps
+// whose pattern is {theta_d} ALONE: divided by theta_d their rows are the slab as loaded, NB multiplies saved each.  A k-step
+// {1, theta_d} costs NB multiply-adds either way, T_d + (1 / theta_d) T_0 in the group or theta_d T_d + T_0 at scale 1.  Every group
+// costs a rescale of the accumulators, 4 multiplies on each of the NB (NB + 1) / 2 tiles behind a drain of the matrix pipe (five
+// s_nop 15 and a fence: about as long as kRescaleDrainOps multiplies).  So d becomes a group only if
+//   NB x (its {theta_d}-alone k-steps)  >  2 NB (NB + 1) + kRescaleDrainOps;
+// otherwise its k-steps go to segment 0 with their usual coefficients.  The rule is applied per weight class (a group is a run
+// of one class) and only to a descriptor with term-less rows, the short half list (the trigger of PACK_FEWEST): that list has lost
+// the interior rows that carry {theta_d} alone.  Every other list is built as it always was.
+constexpr int kRescaleDrainOps = 20;
+bool group_pays(int alone_ksteps, int NB) { return alone_ksteps * NB > 2 * NB * (NB + 1) + kRescaleDrainOps; }
 struct PackCost {
   int ksteps = 0, fma_ksteps = 0, fma = 0;
   bool operator<(const PackCost& o) const { return ksteps != o.ksteps ? ksteps < o.ksteps : fma_ksteps != o.fma_ksteps ? fma_ksteps < o.fma_ksteps : fma < o.fma; }
@@ -1320,8 +1334,10 @@ struct GroupedTables { std::vector<double> tvg; std::vector<int> kmg, def; int n
 // k-step that counts once -- or the final factor if there is none -- carries an exact 2 (bit 1 of its ext_def flags), so the
 // weights act on the accumulators and no row is scaled by sqrt(2).  slot0 / ext0: the list's rows and factors sit behind
 // another list's (slot0 table slots, ext0 scalars, of which the first 1 + 2 P are shared); `def` then holds the factors only.
+// scale_free (the short half list, group_pays above): a leading parameter whose group would not pay for its rescale stays at scale 1;
+// what is left of the factors is the exact 2 where the weight class changes and the final one.
 bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ksteps, int rp, GroupedTables& out,
-                          const std::vector<int>* kclass = nullptr, int slot0 = 0, int ext0 = 0) {
+                          const std::vector<int>* kclass = nullptr, int slot0 = 0, int ext0 = 0, bool scale_free = false) {
   const int r = a->r;
   struct GStep { int cls, group; std::vector<int> pat; const int* rows; };
   std::vector<GStep> gs;
@@ -1334,6 +1350,17 @@ bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ks
     else if (pat.size() == 2 && (pat[0] == 0) != (pat[1] == 0)) { group = pat[0] ? pat[0] : pat[1]; pat = {group, 0}; }
     gs.push_back({kclass ? (*kclass)[k] : 0, group, pat, ks.rows});
   }
+  if (scale_free) {
+    std::map<std::pair<int, int>, int> alone;      // (class, group) -> k-steps with the pattern {theta_group} alone
+    for (const GStep& g : gs) if (g.group != 0 && g.pat.size() == 1) ++alone[{g.cls, g.group}];
+    for (GStep& g : gs) {
+      if (g.group == 0) continue;
+      const auto it = alone.find({g.cls, g.group});
+      if (group_pays(it == alone.end() ? 0 : it->second, rp / 16)) continue;
+      if (g.pat.size() == 2) g.pat = {0, g.group};      // (T_0 first: `finish` then does fma(theta_d, T_d, T_0), NB operations)
+      g.group = 0;
+    }
+  }
   std::stable_sort(gs.begin(), gs.end(), [](const GStep& x, const GStep& y) { return x.cls != y.cls ? x.cls < y.cls : x.group < y.group; });
   // segments: runs of one (class, group); segment 0 is the scale-1 start (group 0 of the first class, possibly empty)
   struct Seg { int cls, group; };
@@ -1345,7 +1372,7 @@ bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ks
     any_group = any_group || g.group != 0;
   }
   const int P = a->P, nfac = (int)segs.size(), base = ext0 ? ext0 : 1 + 2 * P, n_ext = base + nfac;
-  if (!any_group || n_ext > 64) return false;
+  if ((!any_group && !scale_free) || n_ext > 64) return false;      // (a scale-free list may have no group at all)
   // ext[0] = 1, ext[p] = theta_p, ext[P + p] = 1 / theta_p, then one factor per change of segment and the final one; as
   // (numerator, denominator, flags: 1 squared, 2 times two)
   std::vector<int> def(ext0 ? 0 : 3 * (size_t)base, 0);
@@ -1390,7 +1417,7 @@ bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ks
   for (int k = 0; k < 8; ++k) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); }
   out.def = def; out.nkg = nkg; out.n_ext = n_ext; out.ext_final = base + nfac - 1;
   out.live = (int)gs.size(); out.fma_ksteps = 0;
-  for (const GStep& g : gs) out.fma_ksteps += kstep_vector_ops(g.pat) > 0;
+  for (const GStep& g : gs) out.fma_ksteps += kstep_vector_ops(g.pat, g.group == 0) > 0;
   return true;
 }
 
@@ -1434,6 +1461,8 @@ std::vector<KStep> mirror_ksteps(const finrom_rom_desc* a, const double* row_wei
   }
   return ksteps;
 }
+// the short half list (a descriptor with term-less rows) is built scale-free unless the A/B switch asks for the groups it had
+bool short_scale_free(const finrom_rom_desc* a, bool short_grouped) { return !short_grouped && (int)rows_by_term_count(a).size() < a->n; }
 }  // namespace
 
 // Host only (no device needed): the grouped tables finrom_rom_create builds for r <= 80, for tests of the host logic.
@@ -1467,7 +1496,7 @@ int finrom_rom_mirror_tables(const finrom_rom_desc* a, const double* row_weight,
   GroupedTables g;
   std::vector<int> kclass;
   const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
-  if (NB > 5 || !build_grouped_tables(a, ksteps, rp, g, &kclass)) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
+  if (NB > 5 || !build_grouped_tables(a, ksteps, rp, g, &kclass, 0, 0, short_scale_free(a, getenv("FINROM_ROM_SHORT_GROUPED") != nullptr))) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
   *nkg = g.nkg; *n_ext = g.n_ext; *ext_final = g.ext_final; *n_slots = (int64_t)(g.tvg.size() / ((size_t)4 * rp));
   if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
   if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
@@ -1487,7 +1516,7 @@ int finrom_rom_mirror_counts(const finrom_rom_desc* a, const double* row_weight,
   std::vector<int> kclass;
   const std::vector<KStep> ks = mirror_ksteps(a, row_weight, kclass);
   *live_rows = 0; *ksteps = 0; *fma_ksteps = 0;
-  if (NB > 5 || !build_grouped_tables(a, ks, rp, g, &kclass)) return 0;
+  if (NB > 5 || !build_grouped_tables(a, ks, rp, g, &kclass, 0, 0, short_scale_free(a, getenv("FINROM_ROM_SHORT_GROUPED") != nullptr))) return 0;
   *live_rows = (int32_t)rows_by_term_count(a).size(); *ksteps = g.live; *fma_ksteps = g.fma_ksteps;
   return 0;
 }
@@ -1632,7 +1661,7 @@ static int append_half_list(finrom_rom_t h, const finrom_rom_desc* a, const doub
   std::vector<int> kclass;
   const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
   const int slot0 = (int)(h->tvg_host.size() / ((size_t)4 * nd.rp));
-  if (!build_grouped_tables(a, ksteps, nd.rp, g, &kclass, slot0, nd.n_ext)) { set_error(std::string(who) + ": the half descriptor has no grouped form"); return FINROM_ERR_UNSUPPORTED; }
+  if (!build_grouped_tables(a, ksteps, nd.rp, g, &kclass, slot0, nd.n_ext, short_scale_free(a, h->short_grouped))) { set_error(std::string(who) + ": the half descriptor has no grouped form"); return FINROM_ERR_UNSUPPORTED; }
   std::vector<double> tvg(h->tvg_host); tvg.insert(tvg.end(), g.tvg.begin(), g.tvg.end());
   std::vector<int> kmg(h->kmg_host); kmg.insert(kmg.end(), g.kmg.begin(), g.kmg.end());
   std::vector<int> def(h->def_host); def.insert(def.end(), g.def.begin(), g.def.end());

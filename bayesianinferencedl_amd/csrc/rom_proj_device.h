@@ -674,8 +674,20 @@ __device__ __forceinline__ void proj_main_uniform_mw(const RomDev& p, const int*
 // Factorisation of a 16 x 16 SPD diagonal tile D = U^T U and M = U^-T, 4 x 4-blocked, on the matrix cores (round 3; it replaces
 // 16 shuffle steps of ~75 instructions in the one-sample solve kernel and in fused_solve_mw).  D: C/D layout, destroyed.
 // Returns M in C/D layout (lane (q, c), register g: M[4 g + q][c]); bad |= 1 where a pivot is not positive.
+// LDS (round 9, fused_solve_sw<NB, true> only: a throughput form, the callers that wait for this routine keep the other): the
+// scalar traffic leaves the vector pipe.  The lanes that hold the 4 x 4 block write it to sl[0 .. 16) -- the wave's own area -- and
+// every lane reads the ten entries back at uniform addresses (a broadcast) instead of twenty v_readlane; the ten entries of Ib go
+// to the table sl[16 .. 32) and each lane reads its own instead of twenty v_cndmask.  A wave's LDS instructions execute in order,
+// so a wave-level fence between writes and reads is all the ordering there is; the arithmetic, and so every bit, is unchanged.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ d4 diag_tile_inverse(d4& D, int q, int c, int lane, int& bad) {
+constexpr int ROM_SW_LDS_DIAG = 32;      // doubles of LDS per wave for the LDS form (the block, the table of Ib)
+__device__ __forceinline__ void lds_wave_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <bool LDS = false>
+__device__ __forceinline__ d4 diag_tile_inverse(d4& D, int q, int c, int lane, int& bad, double* __restrict__ sl = nullptr) {
   auto mma_ = [](double a, double b, d4 cacc) -> d4 { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, cacc, 0, 0, 0); };
   // 4 x 4-blocked: in C/D layout block row b of the tile IS register b.  Per block: the 4 x 4 diagonal block S is read out
   // (ten v_readlanes), factored S = R^T R and inverted (Ib = R^-1) in wave-uniform arithmetic -- four 1/sqrt chains, no
@@ -688,11 +700,18 @@ __device__ __forceinline__ d4 diag_tile_inverse(d4& D, int q, int c, int lane, i
   const d4 zero4 = (d4){0.0, 0.0, 0.0, 0.0};
   sfor<0, 4>([&](auto bc) {
     constexpr int b = decltype(bc)::value;
-    const double s00 = read_lane_f64(D[b], 0 * 16 + 4 * b + 0), s01 = read_lane_f64(D[b], 0 * 16 + 4 * b + 1),
-                 s02 = read_lane_f64(D[b], 0 * 16 + 4 * b + 2), s03 = read_lane_f64(D[b], 0 * 16 + 4 * b + 3),
-                 s11 = read_lane_f64(D[b], 1 * 16 + 4 * b + 1), s12 = read_lane_f64(D[b], 1 * 16 + 4 * b + 2),
-                 s13 = read_lane_f64(D[b], 1 * 16 + 4 * b + 3), s22 = read_lane_f64(D[b], 2 * 16 + 4 * b + 2),
-                 s23 = read_lane_f64(D[b], 2 * 16 + 4 * b + 3), s33 = read_lane_f64(D[b], 3 * 16 + 4 * b + 3);
+    double s00, s01, s02, s03, s11, s12, s13, s22, s23, s33;
+    if constexpr (LDS) {
+      if ((c >> 2) == b) sl[4 * q + (c & 3)] = D[b];      // lane (q, 4 b + j): S[q][j]
+      lds_wave_order();
+      s00 = sl[0]; s01 = sl[1]; s02 = sl[2]; s03 = sl[3]; s11 = sl[5]; s12 = sl[6]; s13 = sl[7]; s22 = sl[10]; s23 = sl[11]; s33 = sl[15];
+    } else {
+      s00 = read_lane_f64(D[b], 0 * 16 + 4 * b + 0); s01 = read_lane_f64(D[b], 0 * 16 + 4 * b + 1);
+      s02 = read_lane_f64(D[b], 0 * 16 + 4 * b + 2); s03 = read_lane_f64(D[b], 0 * 16 + 4 * b + 3);
+      s11 = read_lane_f64(D[b], 1 * 16 + 4 * b + 1); s12 = read_lane_f64(D[b], 1 * 16 + 4 * b + 2);
+      s13 = read_lane_f64(D[b], 1 * 16 + 4 * b + 3); s22 = read_lane_f64(D[b], 2 * 16 + 4 * b + 2);
+      s23 = read_lane_f64(D[b], 2 * 16 + 4 * b + 3); s33 = read_lane_f64(D[b], 3 * 16 + 4 * b + 3);
+    }
     // 1/sqrt: the hardware estimate (relative error 5e-8 measured) and ONE third-order step, e = 1 - p r^2,
     // r <- r + r e (1/2 + 3/8 e): four dependent operations instead of the six of two Newton steps, and 1.4e-16 instead of
     // 2.4e-16 maximum relative error over 1e6 arguments in [1e-13, 1e13] (these chains are the tile's critical path)
@@ -713,10 +732,20 @@ __device__ __forceinline__ d4 diag_tile_inverse(d4& D, int q, int c, int lane, i
     const double i02 = -fma(r01, i12, r02 * i22) * i00, i13 = -fma(r12, i23, r13 * i33) * i11;
     const double i03 = -fma(r01, i13, fma(r02, i23, r03 * i33)) * i00;
     double AI = 0.0;                                 // lane (q, c): Ib[q][c] for c < 4, q <= c
-    AI = lane == 0 * 16 + 0 ? i00 : AI; AI = lane == 0 * 16 + 1 ? i01 : AI; AI = lane == 0 * 16 + 2 ? i02 : AI;
-    AI = lane == 0 * 16 + 3 ? i03 : AI; AI = lane == 1 * 16 + 1 ? i11 : AI; AI = lane == 1 * 16 + 2 ? i12 : AI;
-    AI = lane == 1 * 16 + 3 ? i13 : AI; AI = lane == 2 * 16 + 2 ? i22 : AI; AI = lane == 2 * 16 + 3 ? i23 : AI;
-    AI = lane == 3 * 16 + 3 ? i33 : AI;
+    if constexpr (LDS) {
+      double* __restrict__ tb = sl + 16;             // (every lane stores the same value; the entries below the diagonal are never read)
+      tb[0] = i00; tb[1] = i01; tb[2] = i02; tb[3] = i03; tb[5] = i11; tb[6] = i12; tb[7] = i13; tb[10] = i22; tb[11] = i23; tb[15] = i33;
+      lds_wave_order();
+      const bool mine = c < 4 && q <= c;
+      const double t_ = tb[mine ? 4 * q + c : 0];
+      AI = mine ? t_ : 0.0;
+      lds_wave_order();                              // (the next block's writes stay behind these reads)
+    } else {
+      AI = lane == 0 * 16 + 0 ? i00 : AI; AI = lane == 0 * 16 + 1 ? i01 : AI; AI = lane == 0 * 16 + 2 ? i02 : AI;
+      AI = lane == 0 * 16 + 3 ? i03 : AI; AI = lane == 1 * 16 + 1 ? i11 : AI; AI = lane == 1 * 16 + 2 ? i12 : AI;
+      AI = lane == 1 * 16 + 3 ? i13 : AI; AI = lane == 2 * 16 + 2 ? i22 : AI; AI = lane == 2 * 16 + 3 ? i23 : AI;
+      AI = lane == 3 * 16 + 3 ? i33 : AI;
+    }
     // block row b of U = Ib^T D[b, :] (columns left of the block are not part of U)
     const d4 ur = mma_(AI, D[b], zero4);
     const double Ub = c >= 4 * b ? ur[0] : 0.0;
@@ -893,6 +922,12 @@ __device__ __forceinline__ void fused_solve_mw(const RomDev& p, d4 (&acc)[(NB * 
 // needs no backward substitution.  ~2.4 k vector instructions + 180 MFMAs per sample at r = 80.
 // ---------------------------------------------------------------------------------------
 constexpr int ROM_SW_LDS = 16 * 5;      // doubles of LDS per wave (B_r)
+// the roomy variant factors its diagonal tiles through LDS (diag_tile_inverse<true>: ROM_SW_LDS_DIAG doubles behind B_r);
+// -DROM_ROOMY_LDS_DIAG=0 (FINROM_EXTRA_FLAGS) builds it with the register form, for A/B runs
+#ifndef ROM_ROOMY_LDS_DIAG
+#define ROM_ROOMY_LDS_DIAG 1
+#endif
+template <bool RM> constexpr int rom_sw_lds() { return ROM_SW_LDS + (RM && ROM_ROOMY_LDS_DIAG ? ROM_SW_LDS_DIAG : 0); }
 constexpr int ROM_SW_MFMA_DIAG_TILES = 6;      // block rows with at most this many live tiles factor their diagonal tile on the matrix cores
 template <int NB, bool RM = false>
 __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (NB + 1) / 2], const double (&bacc)[NB], int q, int c,
@@ -957,7 +992,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       // M^T = sum_g X_g^T E_g with the identity's rows as B operands: FOUR MFMAs transpose the tile, no LDS (2 KB per wave here
       // would cost the co-resident band sweep a quarter of its waves), no shuffles (16 of them spilled 140 registers).
       d4 D = acc[tidx<NB>(kb, kb)];
-      const d4 Mc = diag_tile_inverse(D, q, c, q * 16 + c, bad);
+      const d4 Mc = diag_tile_inverse<RM && ROM_ROOMY_LDS_DIAG>(D, q, c, q * 16 + c, bad, mt + ROM_SW_LDS);
       // (the pivot tests are settled HERE: left to itself hipcc sinks them to the end of the epilogue and keeps all 16 NB pivots in
       //  registers until then -- that, not the tiles, is what overflowed the register file with five matrix-core block rows)
       if constexpr (RM) asm volatile("" : "+v"(bad));
@@ -1320,7 +1355,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
   constexpr int WPB = NW > 4 ? NW : 4;
   static_assert(NW == 1 || NW == 4 || NW == 8, "a workgroup is one sample when its waves share the slab (uniform early exit, barriers)");
   __shared__ double th[WPB][32];
-  __shared__ double mt_sw[NW == 1 && NB <= 5 ? WPB * ROM_SW_LDS : 1];      // fused_solve_sw: B_r, per wave
+  __shared__ double mt_sw[NW == 1 && NB <= 5 ? WPB * rom_sw_lds<RM>() : 1];      // fused_solve_sw: B_r (and the roomy variant's diagonal blocks), per wave
   __shared__ double slab_lds[NW > 1 ? (3 * NB * 64 > fused_mw_lds_doubles<NB>() ? 3 * NB * 64 : fused_mw_lds_doubles<NB>()) : 1];
   double* slab = slab_lds;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: say so (scalar branches below)
@@ -1360,7 +1395,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
     }
     rom_proj_body<NB, 1, 0, false, GR, false, RM>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
                                        half ? kpat + __builtin_amdgcn_readfirstlane(half == 2 ? p.kmg_s : p.kmg_m) : kpat, 0, 1, nullptr,
-                                       NB <= 5 ? mt_sw + wave * ROM_SW_LDS : nullptr, ext_s, half);
+                                       NB <= 5 ? mt_sw + wave * rom_sw_lds<RM>() : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {
     switch (wave % 4) {
       case 0: rom_proj_body<NB, 4, 0, false, false, HF>(p, thw, s, lane, Ar, Br, factor, info, nullptr, qoi_r, slab, theta_u, kpat); break;
