@@ -143,6 +143,9 @@ SIGNATURES = {
     "finrom_fom_band_validate": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32]),
     "finrom_fom_set_band_mirror": (C.c_int, [C.c_void_p, C.POINTER(FomBandDesc), C.c_int32, C.c_int32, c_i32p, c_i32p]),
     "finrom_fom_band_mirror_validate": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p]),
+    "finrom_fom_band_mirror_functionals": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p,
+                                                     c_i32p, c_f64p, c_i32p, c_i32p]),
+    "finrom_fom_band_mirror_form": (C.c_int, [C.c_void_p]),
     "finrom_fom_solve_rhs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_fom_last_path": (C.c_int, [C.c_void_p]),
     "finrom_fom_set_small_max": (C.c_int, [C.c_void_p, C.c_int32]),

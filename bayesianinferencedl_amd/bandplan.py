@@ -322,13 +322,36 @@ class BandPlan:
         return abmap.astype(np.int32), c0p, ptrp.astype(np.int32), idxp, wp
 
     # ------------------------------------------------------------------------------------------------------------------
-    def replay(self, AB, F, qoi_only=None):
+    def post_functional_tables(self, qoi_only):
+        """The tables the library derives for the functional form of the post (finrom_fom_set_band_mirror, DESIGN 4c'), from the
+        same inputs: cw [npost, n_rows] -- row o's post-only weights, dense --, piv_row [npost] -- the row whose fin has the
+        pivot as an interface node, -1: none --, piv_off [npost] -- f * nif + k, that node is interface node k of fin f."""
+        _, row_fin, qptr, qidx, qw = qoi_only
+        e0, npost = self.post_seg.e0, self.post_seg.npiv
+        cw = np.zeros((npost, len(row_fin)))
+        piv_row = np.full(npost, -1, np.int64); piv_off = np.zeros(npost, np.int64)
+        for o, f in enumerate(row_fin):
+            for t in range(qptr[o], qptr[o + 1]):
+                cw[qidx[t] - e0, o] += qw[t]
+            if f >= 0:
+                nif = len(self.iface_elim[f])
+                for k in range(nif):
+                    pv = self.iface_elim[f][k] - e0
+                    assert piv_row[pv] < 0, "a post node is an interface node of two fins that rows own"
+                    piv_row[pv] = o; piv_off[pv] = f * nif + k
+        return cw, piv_row, piv_off
+
+    def replay(self, AB, F, qoi_only=None, post_functional=False):
         """NumPy execution of the plan with the device kernel's data flow (cyclic window slots, extras, fin Schur targets,
         stored L, backward substitution).  AB: assembled value slots [nAB] of one sample; F: load vector over dofs.
         Returns w over dofs.  Test infrastructure for the tables -- the product path is csrc/fom_band.hip.
         qoi_only = (FgQ, row_fin, qptr, qidx, qw) (engine.FomEngine.qoi_only_tables): the kernel's QoI-only form instead -- the
         fins' sweeps carry their observation row's weights as right-hand side, store nothing and have no backward sweep --
-        and the observables [n_obs] are returned."""
+        and the observables [n_obs] are returned.
+        post_functional (with qoi_only): the post's rows as functionals, in the kernel's order -- c_o (post_functional_tables,
+        plus the fin's g on its interface nodes) rides the post's forward sweep as one more right-hand side per row, carried
+        through the extras like y, and q_o gathers z_p y_p pivot by pivot; nothing of the post is stored, no backward sweep."""
+        assert not post_functional or qoi_only is not None
         AB = np.array(AB, dtype=np.float64, copy=True)
         n = self.n
         L = np.zeros(self.nL); Lx = np.zeros(max(self.nLx, 1)); y = np.zeros(n)
@@ -337,17 +360,27 @@ class BandPlan:
             Fe = Fe * self.rhs_scale
         NX = max(self.NX, 1)
 
-        def sweep(seg, is_post):
+        def sweep(seg, is_post, fn=None):
             NS = seg.NS; B = NS - 1
             win = np.zeros((NS, NS)); yw = np.zeros(NS)
             X = np.zeros((NX, NS)); XD = np.zeros(NX); XX = np.zeros((NX, NX)); XY = np.zeros(NX)
+            if fn is not None:                             # (cw, piv_row, piv_off, the fins' g): windows zw, the extras' XZ, q
+                cw, piv_row, piv_off, gflat = fn
+                NF = cw.shape[1]
+                zw = np.zeros((NF, NS)); XZ = np.zeros((NX, NF)); q = np.zeros(NF)
 
             def enter(t):
                 u = t % NS
                 win[u, :] = 0.0; win[:, u] = 0.0; yw[u] = 0.0
                 X[:, u] = 0.0
+                if fn is not None:
+                    zw[:, u] = cw[t]
+                    if piv_row[t] >= 0:
+                        zw[piv_row[t], u] += gflat[piv_off[t]]
                 if is_post and self.ent_extra[t]:
                     s_ = self.ent_extra[t] - 1
+                    if fn is not None:
+                        zw[:, u] = XZ[s_] + zw[:, u]; XZ[s_] = 0.0
                     for v in range(NS):
                         if v != u:
                             win[u, v] = win[v, u] = X[s_, v]
@@ -385,9 +418,14 @@ class BandPlan:
                     l[s_] = win[(u + s_) % NS, u] * inv
                 base = seg.L0 + p * NS
                 yp = yw[u] * inv
-                if is_post or qoi_only is None:            # (QoI-only: nothing of a fin's factor or y is kept)
+                if (is_post and fn is None) or qoi_only is None:      # (QoI-only: nothing of a fin's factor or y is kept)
                     L[base:base + B] = l[1:]; L[base + B] = inv
                     y[seg.e0 + p] = yp
+                if fn is not None:
+                    zp = zw[:, u] * inv
+                    q += zp * yp
+                    for s_ in range(1, NS):
+                        zw[:, (u + s_) % NS] -= l[s_] * zp
                 for s_ in range(1, NS):
                     a = (u + s_) % NS
                     yw[a] -= l[s_] * yp
@@ -399,7 +437,10 @@ class BandPlan:
                     for s_ in range(NX):
                         if self.act[p] >> s_ & 1:
                             le[s_] = X[s_, u] * inv
-                            Lx[k] = le[s_]; k += 1
+                            if fn is None:
+                                Lx[k] = le[s_]; k += 1
+                            else:
+                                XZ[s_] -= le[s_] * zp
                             XY[s_] -= le[s_] * yp; XD[s_] -= le[s_] ** 2
                             for t_ in range(1, NS):
                                 X[s_, (u + t_) % NS] -= le[s_] * l[t_]
@@ -408,6 +449,10 @@ class BandPlan:
                             XX[a, b_] -= le[a] * le[b_]
                 if p + NS < seg.ntot:
                     enter(p + NS)
+                elif fn is not None:
+                    zw[:, u] = 0.0
+            if fn is not None:
+                return q
             return win, yw
 
         gfun = []                                         # per fin: the functional's weights on the interface values
@@ -417,6 +462,8 @@ class BandPlan:
                 a, b_ = (seg.npiv + t) % seg.NS, (seg.npiv + s_) % seg.NS
                 AB[off] += win[a, b_]
             gfun.append([yw[(seg.npiv + t) % seg.NS] for t in range(seg.ntot - seg.npiv)])
+        if post_functional:
+            return sweep(self.post_seg, True, self.post_functional_tables(qoi_only) + (np.concatenate(gfun) if gfun else np.zeros(0),))
         sweep(self.post_seg, True)
 
         # backward substitution, post first (reverse elimination order), then the fins

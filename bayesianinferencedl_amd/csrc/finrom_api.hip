@@ -168,6 +168,7 @@ struct finrom_fom_s {
   // half-domain plan of a mirror-symmetric operator (finrom_fom_set_band_mirror): serves the calls that want no w
   BandDev band_m{};
   FomDev band_m_asm{};
+  BandFnDev band_m_fn{};               // cw != nullptr: band_m is in the functional form of the post (no stored factor; DESIGN 4c')
   const BandDev& band_for(bool want_w) const { return !want_w && band_m.on ? band_m : band; }
   std::vector<void*> owned;
   Scratch xT, Gw, gradT, qtmp;
@@ -562,7 +563,10 @@ void finrom_fom_destroy(finrom_fom_t h) {
 static int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr) {
   // bound the per-call workspace (L values dominate: nnzL * 8 B per sample)
   const size_t per_sample = ((size_t)(band && band->on ? band->gsize : d.gsize) + d.xdim) * sizeof(double);
-  const int64_t chunk = (int64_t)((size_t)48 << 30) / (int64_t)per_sample;
+  // (FINROM_FOM_WORKSPACE_BYTES=<n>, read per call: another bound, so that a test can make a small batch run in pieces)
+  const char* env_ws = getenv("FINROM_FOM_WORKSPACE_BYTES");
+  const int64_t bound = env_ws != nullptr && atoll(env_ws) > 0 ? (int64_t)atoll(env_ws) : (int64_t)((size_t)48 << 30);
+  const int64_t chunk = bound / (int64_t)per_sample;
   return std::max<int64_t>(64, chunk / 64 * 64);
 }
 static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st,
@@ -600,7 +604,8 @@ static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* 
         if ((rc = launch_fom_assemble(basm, (const double*)h->xT.p, nblk, (double*)h->Gw.p, st))) return rc;
       }
       if (stages & 2) {
-        if ((rc = launch_fom_band(b, (double*)h->Gw.p, nblk, Sc, qoi ? qoi + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st, w == nullptr))) return rc;
+        const BandFnDev* fn = &b == &h->band_m && h->band_m_fn.cw != nullptr ? &h->band_m_fn : nullptr;
+        if ((rc = launch_fom_band(b, (double*)h->Gw.p, nblk, Sc, qoi ? qoi + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st, w == nullptr, fn))) return rc;
         if (w && (rc = launch_unpack((const double*)h->Gw.p, Sc, d.n, b.gsize, b.offY, b.perm, w + s0 * d.n, st))) return rc;
       }
     }
@@ -922,7 +927,7 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   BandDev b{};
   if (int rc = build_band(h, a, d.n, d.n_obs, gsize, nL, &b, &h->band_asm)) return rc;
   h->band = b;
-  h->band_m = BandDev{};                  // (a half plan belongs to the plan it was installed beside)
+  h->band_m = BandDev{}; h->band_m_fn = BandFnDev{};      // (a half plan belongs to the plan it was installed beside)
   return 0;
 }
 
@@ -949,9 +954,82 @@ static int validate_band_mirror(const finrom_fom_band_desc* a, int n_half, int x
   return 0;
 }
 
+// The post as functionals (fom_band.hip, DESIGN 4c'): the tables of a VALIDATED half descriptor, host only.
+//   cw [npost][BAND_NF]   row o's post-only weights (qoi_obs_*), dense; rows beyond n_rows are zero
+//   piv_row, piv_off [npost]   post pivot -> the row that owns the fin this pivot is an interface node of (-1: none) and the slot
+//                              f * nif + t in which that fin's sweep leaves its g for the node
+// -> 1: the form fits; 0: it does not -- more than BAND_NF rows, other window sizes than the half plans', a row with weights on two
+// fins, a post node that is an interface node of two fins that rows own -- and the stored-factor form serves the plan;
+// < 0: the derived tables do not describe the operator obs_* describes (an error, like any other validator finding).
+static int derive_post_functionals(const finrom_fom_band_desc* a, int n_half, int n_rows, std::vector<double>& cw, std::vector<int>& piv_row,
+                                   std::vector<int>& piv_off) {
+  auto bad = [&](const char* what) { set_error(std::string("fom_set_band_mirror: invalid ") + what); return (int)FINROM_ERR_ARG; };
+  const bool windows = a->NX <= 2 && ((a->NSF == 3 && a->NSP == 4) || (a->NSF == 4 && a->NSP == 6) || (a->NSF == 5 && a->NSP == 8));
+  if (!windows || n_rows > BAND_NF || !a->qoi_FgQ) return 0;
+  const int post_e0 = a->nfins * a->npf, ntot = a->npf + a->nif;
+  for (int o = 0; o < n_rows; ++o)                        // a row's weights on fin nodes: one fin, the one row_fin names
+    for (int t = a->obs_ptr[o]; t < a->obs_ptr[o + 1]; ++t)
+      if (a->obs_idx[t] < post_e0 && a->obs_w[t] != 0.0 && a->obs_idx[t] / a->npf != a->qoi_row_fin[o]) return 0;
+  cw.assign((size_t)a->npost * BAND_NF, 0.0);
+  piv_row.assign(a->npost, -1); piv_off.assign(a->npost, 0);
+  for (int o = 0; o < n_rows; ++o)
+    for (int t = a->qoi_obs_ptr[o]; t < a->qoi_obs_ptr[o + 1]; ++t) {
+      const int pv = a->qoi_obs_idx[t] - post_e0;
+      if (pv < 0 || pv >= a->npost) return bad("qoi_obs_idx (a weight outside the post)");
+      cw[(size_t)pv * BAND_NF + o] += a->qoi_obs_w[t];
+    }
+  for (int o = 0; o < n_rows; ++o) {
+    const int f = a->qoi_row_fin[o];
+    if (f < 0) continue;
+    for (int t = 0; t < a->nif; ++t) {
+      const int pv = a->iface_elim[f * a->nif + t] - post_e0;
+      if (pv < 0 || pv >= a->npost) return bad("iface_elim (an interface node outside the post)");
+      if (piv_row[pv] >= 0) return 0;
+      piv_row[pv] = o; piv_off[pv] = f * a->nif + t;
+    }
+  }
+  // every index the kernel dereferences, and the operator rebuilt from the tables against obs_*, entry by entry
+  for (int pv = 0; pv < a->npost; ++pv)
+    if (piv_row[pv] < -1 || piv_row[pv] >= n_rows || piv_off[pv] < 0 || piv_off[pv] >= a->nfins * a->nif) return bad("derived pivot map");
+  std::vector<double> full(n_half), rec(n_half);
+  for (int o = 0; o < n_rows; ++o) {
+    std::fill(full.begin(), full.end(), 0.0); std::fill(rec.begin(), rec.end(), 0.0);
+    for (int t = a->obs_ptr[o]; t < a->obs_ptr[o + 1]; ++t) full[a->obs_idx[t]] += a->obs_w[t];
+    for (int pv = 0; pv < a->npost; ++pv) {
+      rec[post_e0 + pv] += cw[(size_t)pv * BAND_NF + o];
+      if (piv_row[pv] == o) {                             // the g slot holds, before the fin's elimination, the row's weight on the node
+        const int f = piv_off[pv] / a->nif, t = piv_off[pv] % a->nif;
+        rec[post_e0 + pv] += a->qoi_FgQ[f * ntot + a->npf + t];
+      }
+    }
+    const int f = a->qoi_row_fin[o];
+    if (f >= 0) for (int t = 0; t < a->npf; ++t) rec[f * a->npf + t] += a->qoi_FgQ[f * ntot + t];
+    for (int i = 0; i < n_half; ++i) if (full[i] != rec[i]) return bad("derived functional tables (not the operator obs_* describes)");
+  }
+  return 1;
+}
+
 int finrom_fom_band_mirror_validate(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
                                     const int32_t* out_ptr, const int32_t* out_col) {
-  return validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr);
+  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
+  std::vector<double> cw; std::vector<int> piv_row, piv_off;
+  const int fits = derive_post_functionals(a, n_half, n_rows, cw, piv_row, piv_off);
+  return fits < 0 ? fits : 0;
+}
+
+// Host only: the tables finrom_fom_set_band_mirror derives for the functional form of the post, for a test to walk.  *fits = 0: the
+// descriptor keeps the stored-factor form and nothing is written; cw [npost * 5], piv_row and piv_off [npost] otherwise.
+int finrom_fom_band_mirror_functionals(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                       const int32_t* out_ptr, const int32_t* out_col, int32_t* fits, double* cw, int32_t* piv_row,
+                                       int32_t* piv_off) {
+  if (!fits || !cw || !piv_row || !piv_off) { set_error("fom_band_mirror_functionals: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
+  std::vector<double> c; std::vector<int> pr, po;
+  const int f = derive_post_functionals(a, n_half, n_rows, c, pr, po);
+  if (f < 0) return f;
+  *fits = f;
+  if (f) { std::copy(c.begin(), c.end(), cw); std::copy(pr.begin(), pr.end(), piv_row); std::copy(po.begin(), po.end(), piv_off); }
+  return 0;
 }
 
 int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* a, int32_t n_half, int32_t n_rows, const int32_t* out_ptr,
@@ -969,8 +1047,31 @@ int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* a, in
   if (!rc) rc = up(h->owned, &b.out_col, out_col, d.n_obs);
   if (rc) return rc;
   b.n_out = d.n_obs;
-  h->band_m = b; h->band_m_asm = q;
+  // The post as functionals, where the descriptor fits (FINROM_FOM_POST_STORED=1: the stored-factor form, the A/B switch).  The
+  // workspace of that form is the value slots and the fins' g: the plan's sizes -- chunking, the pair path's reservation, the
+  // assembly pre-pass's stride -- all follow gsize.
+  BandFnDev fn{};
+  if (getenv("FINROM_FOM_POST_STORED") == nullptr) {
+    std::vector<double> cw; std::vector<int> piv_row, piv_off;
+    const int fits = derive_post_functionals(a, n_half, n_rows, cw, piv_row, piv_off);
+    if (fits < 0) return fits;
+    if (fits) {
+      rc = up(h->owned, &fn.cw, cw.data(), cw.size());
+      if (!rc) rc = up(h->owned, &fn.piv_row, piv_row.data(), piv_row.size());
+      if (!rc) rc = up(h->owned, &fn.piv_off, piv_off.data(), piv_off.size());
+      if (rc) return rc;
+      b.offL = b.offLx = b.offX = b.offV = 0;             // (regions this form does not have)
+      b.offY = a->nAB;
+      b.gsize = q.gsize = a->nAB + a->nfins * a->nif;
+    }
+  }
+  h->band_m = b; h->band_m_asm = q; h->band_m_fn = fn;
   return 0;
+}
+
+int finrom_fom_band_mirror_form(finrom_fom_t h) {
+  if (!h || !h->band_m.on) return 0;
+  return h->band_m_fn.cw != nullptr ? 2 : 1;
 }
 
 int finrom_fom_set_band_gradient(finrom_fom_t h, const finrom_fom_band_grad_desc* a) {

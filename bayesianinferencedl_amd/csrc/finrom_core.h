@@ -208,7 +208,15 @@ constexpr int BAND_LDS_XSIZE = 256;                 // doubles per lane of the e
 constexpr int BAND_LDS_XSIZE_WIDE = 384;            // ... and for the windows beyond NSP = 22 (ten extras of 26 slots + their scalars)
 constexpr int band_xsize(int NSP) { return NSP > 26 ? 512 : NSP > 22 ? BAND_LDS_XSIZE_WIDE : BAND_LDS_XSIZE; }   // (NSP = 30, twelve extras: 462)
 bool band_supported(int NSF, int NSP, int NX);
-int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qoi_only);
+// The half plan's post as functionals (fom_band.hip, DESIGN 4c'): tables derived by finrom_fom_set_band_mirror from the half
+// descriptor, wave-uniform.  cw [npost][BAND_NF]: the distinct rows' post-only weights (rows beyond n_rows: zeros); piv_row /
+// piv_off [npost]: the row whose fin has the pivot as an interface node (-1: none) and where that fin's sweep leaves its g for the
+// node, as an offset into the region at BandDev::offY.  A BandDev that goes with these tables has offY = nAB and
+// gsize = nAB + nfins * nif: value slots and the fins' g are all its workspace holds.
+constexpr int BAND_NF = 5;
+struct BandFnDev { const double* cw = nullptr; const int* piv_row = nullptr; const int* piv_off = nullptr; };
+int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qoi_only,
+                    const BandFnDev* fn = nullptr);
 int launch_fom_band_wide(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qo);   // fom_band_wide.hip
 int band_path(const BandDev& p, bool qoi_only);      // FINROM_FOM_PATH_* of the kernel launch_fom_band picks
 

@@ -26,27 +26,52 @@ namespace {
 // ---- forward: factorisation fused with L y = F over one segment ----------------------------------------------------------
 // (PF: the right-hand side of the entering node travels with its three matrix entries -- for callers that run one wave per SIMD
 // or less, where nothing else hides the load; the m <= 12 kernel is HBM-bound and keeps its register budget)
-// (NOSTORE, fins only: the QoI-only form below -- nothing of the segment's factor or y leaves the registers)
-template <int NS, bool POST, int NXM, bool PF = false, bool NOSTORE = false>
+// (NOSTORE: the QoI-only form below -- nothing of the segment's factor or y leaves the registers)
+// (NF > 0, the post with NOSTORE: the observation rows as functionals.  With c_o the weights of row o on the post -- its post-only
+// part plus, on the interface nodes of its fin, the g that the fin's sweep left -- the observable is
+//     q_o = c_o^T A_post^-1 f = (L^-1 c_o)^T (L^-1 f),
+// so c_o rides the sweep as one more right-hand side: window fs->zw[o] beside yw, an LDS slot per extra beside XY (at XL::SIZE),
+// and q_o gathers z_p y_p pivot by pivot.  No column of L, no y, no coupling to an extra is stored and no backward sweep follows.)
+template <int NS, bool POST, int NXM, bool PF = false, bool NOSTORE = false, int NF = 0>
 __device__ __forceinline__ void band_sweep(const BandDev& p, const Io& io, double* __restrict__ xs, const double* __restrict__ Fg,
                                            const int* __restrict__ abmap, const PostTables& T, int g0, int e0, int npiv, int ntot, int L0,
-                                           double (&win)[NS * (NS + 1) / 2], double (&yw)[NS], int& bad) {
+                                           double (&win)[NS * (NS + 1) / 2], double (&yw)[NS], int& bad,
+                                           FnState<(NF > 0 ? NF : 1), NS>* __restrict__ fs = nullptr) {
   constexpr int B = NS - 1;
   using L = XL<NS, NXM>;
+  constexpr int XZ = L::SIZE;                            // NF > 0: the extras' carried functional values, [NXM][NF]
+  static_assert(NF == 0 || (POST && NOSTORE && !PF), "the functional windows belong to the post's store-free sweep");
   static_for<0, NS*(NS + 1) / 2>([&](auto i) { win[decltype(i)::value] = 0.0; });
   static_for<0, NS>([&](auto i) { yw[decltype(i)::value] = 0.0; });
-  if constexpr (POST) static_for<0, L::SIZE>([&](auto i) { xs[decltype(i)::value * 64] = 0.0; });
+  if constexpr (POST) static_for<0, L::SIZE + NXM * NF>([&](auto i) { xs[decltype(i)::value * 64] = 0.0; });
+  if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+    constexpr int o = decltype(oc)::value;
+    fs->q[o] = 0.0;
+    static_for<0, NS>([&](auto i) { fs->zw[o][decltype(i)::value] = 0.0; });
+  });
 
   // node t enters the window in slot u = t mod NS (the slot its predecessor t - NS has just left)
   auto enter = [&](auto uc, int t, double ab0, double ab1, double ab2, double fpre = 0.0) {
     constexpr int u = decltype(uc)::value;
     static_for<0, NS>([&](auto vc) { constexpr int v = decltype(vc)::value; if constexpr (v != u) win[tri(u, v)] = 0.0; });
     double diag = 0.0, yv = 0.0;
+    double zv[NF > 0 ? NF : 1];
+    if constexpr (NF > 0) {                              // c_o[t]: the row's own weight, plus its fin's g where t is an interface node
+      const int row = fs->T.piv_row[t];
+      double gv = 0.0;
+      if (row >= 0) gv = io.ld(p.offY + fs->T.piv_off[t]);
+      static_for<0, NF>([&](auto oc) { constexpr int o = decltype(oc)::value; zv[o] = fs->T.cw[t * NF + o] + (row == o ? gv : 0.0); });
+    }
     if constexpr (POST) {
       static_for<0, NXM>([&](auto sc) { xs[(L::X + decltype(sc)::value * NS + u) * 64] = 0.0; });
       const int ex = T.ent_extra[t];
       if (ex != 0) {                                     // the node was an extra: its state moves from LDS into the window
         const int sl = ex - 1;
+        if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+          constexpr int o = decltype(oc)::value;
+          zv[o] = xs[(XZ + sl * NF + o) * 64] + zv[o];
+          xs[(XZ + sl * NF + o) * 64] = 0.0;
+        });
         static_for<0, NS>([&](auto vc) {
           constexpr int v = decltype(vc)::value;
           if constexpr (v != u) win[tri(u, v)] = xs[(L::X + sl * NS + v) * 64];
@@ -69,6 +94,7 @@ __device__ __forceinline__ void band_sweep(const BandDev& p, const Io& io, doubl
     win[tri(u, (u + NS - 1) % NS)] += ab1;               // previous node (zero entry where there is none)
     win[tri(u, (u + 1) % NS)] += ab2;                    // the node B positions back
     yw[u] = yv + (PF ? fpre : Fg[g0 + t]);
+    if constexpr (NF > 0) static_for<0, NF>([&](auto oc) { fs->zw[decltype(oc)::value][u] = zv[decltype(oc)::value]; });
     if constexpr (POST) {
       for (int c = T.ecp_ptr[t], c1 = T.ecp_ptr[t + 1]; c < c1; ++c)       // long-range couplings of this node: to extras
         xs[(L::X + T.ecp_slot[c] * NS + u) * 64] += io.ld(T.ecp_off[c]);
@@ -119,6 +145,16 @@ __device__ __forceinline__ void band_sweep(const BandDev& p, const Io& io, doubl
         }
         const double yp = yw[u] * inv;
         if constexpr (!NOSTORE) io.st(yp, p.offY + e0 + pp);
+        double zp[NF > 0 ? NF : 1];
+        if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+          constexpr int o = decltype(oc)::value;
+          zp[o] = fs->zw[o][u] * inv;
+          fs->q[o] = fma(zp[o], yp, fs->q[o]);
+          static_for<1, NS>([&](auto sc) {
+            constexpr int s_ = decltype(sc)::value;
+            fs->zw[o][(u + s_) % NS] = fma(-l[s_], zp[o], fs->zw[o][(u + s_) % NS]);
+          });
+        });
         static_for<1, NS>([&](auto sc) {
           constexpr int s_ = decltype(sc)::value;
           yw[(u + s_) % NS] = fma(-l[s_], yp, yw[(u + s_) % NS]);
@@ -131,15 +167,20 @@ __device__ __forceinline__ void band_sweep(const BandDev& p, const Io& io, doubl
           const int am = T.act[pp];
           if (am != 0) {
             double le[NXM];
-            int k = p.offLx + T.lx_ptr[pp];
+            int k = 0;
+            if constexpr (NF == 0) k = p.offLx + T.lx_ptr[pp];      // (the functional form has no lx_ptr: nothing is stored)
             static_for<0, NXM>([&](auto sc) {
               constexpr int sl = decltype(sc)::value;
               le[sl] = 0.0;
               if (am & (1 << sl)) {
                 const double v = xs[(L::X + sl * NS + u) * 64] * inv;
                 le[sl] = v;
-                io.st(v, k); ++k;
+                if constexpr (NF == 0) { io.st(v, k); ++k; }
                 xs[(L::XY + sl) * 64] = fma(-v, yp, xs[(L::XY + sl) * 64]);
+                if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+                  constexpr int a = (XZ + sl * NF + decltype(oc)::value) * 64;
+                  xs[a] = fma(-v, zp[decltype(oc)::value], xs[a]);
+                });
                 xs[(L::XD + sl) * 64] = fma(-v, v, xs[(L::XD + sl) * 64]);
                 static_for<1, NS>([&](auto tc) {
                   constexpr int t = decltype(tc)::value;
@@ -158,7 +199,10 @@ __device__ __forceinline__ void band_sweep(const BandDev& p, const Io& io, doubl
           }
         }
         if (more) enter(std::integral_constant<int, u>{}, pp + NS, ab0, ab1, ab2, PF ? abf[PF ? rs : 0] : 0.0);
-        else static_for<0, NS>([&](auto vc) { win[tri(u, decltype(vc)::value)] = 0.0; });      // nobody enters: the slot is empty
+        else {
+          static_for<0, NS>([&](auto vc) { win[tri(u, decltype(vc)::value)] = 0.0; });      // nobody enters: the slot is empty
+          if constexpr (NF > 0) static_for<0, NF>([&](auto oc) { fs->zw[decltype(oc)::value][u] = 0.0; });
+        }
       }
       if (sidx < npiv && sidx + NS < ntot) {             // entries of the node that enters after pivot s: in flight for RF steps
         const int g = 3 * (g0 + sidx + NS);      // (physical slots: entries with the same affine record share one)
@@ -473,12 +517,12 @@ __device__ __forceinline__ void band_sweep_ldsr(const BandDev& p, const Io& io, 
 // Host side (engine.py::band_descriptor): FgQ = the observation weights on the fins' segment nodes and the load on the post's;
 // the post-only remainder of B_obs as CSR; row_fin[o] = the fin whose functional belongs to row o (-1: none).
 template <int NSF>
-__device__ __forceinline__ void fin_functional_out(const BandDev& p, const Io& io, const double (&yw)[NSF], int f, int npiv) {
+__device__ __forceinline__ void fin_functional_out(const BandDev& p, const Io& io, const double (&yw)[NSF], int f, int npiv, int stride) {
   for (int t = 0; t < p.nif; ++t) {
     const int su = (npiv + t) % NSF;
     double v = 0.0;
     static_for<0, NSF>([&](auto uc) { constexpr int u = decltype(uc)::value; v = su == u ? yw[u] : v; });
-    io.st(v, p.offY + f * npiv + t);
+    io.st(v, p.offY + f * stride + t);
   }
 }
 // observable o from the post's w: the post-only part of the row + g^T w_G of the row's fin
@@ -530,7 +574,7 @@ __device__ __forceinline__ void fom_band_body(BandDev p, const int* __restrict__
     for (int f = 0; f < p.nfins; ++f) {
       const int npiv = p.npf, ntot = p.npf + p.nif;
       band_sweep<NSF, false, NXM, false, QO>(p, io, xs, Fg, abmap, T, f * ntot, f * npiv, npiv, ntot, f * npiv * NSF, win, yw, bad);
-      if constexpr (QO) fin_functional_out<NSF>(p, io, yw, f, npiv);
+      if constexpr (QO) fin_functional_out<NSF>(p, io, yw, f, npiv, npiv);
       // what is left in the window is the fin's Schur complement on its interface nodes: add it to their entries in the post
       int k = 0;
       for (int t = 0; t < p.nif; ++t)
@@ -570,6 +614,66 @@ __device__ __forceinline__ void fom_band_body(BandDev p, const int* __restrict__
         for (int c = p.out_ptr[o], c1 = p.out_ptr[o + 1]; c < c1; ++c) qoi[s * p.n_out + p.out_col[c]] = bad ? nanv : q;
     } else if (s < S) qoi[s * p.n_obs + o] = bad ? nanv : q;
   }
+}
+
+// ---- the half plan's QoI-only form with the post as functionals (DESIGN 4c') ------------------------------------------------------
+// The fins as in fom_band_body<.., true>, except that a fin's g goes to nif slots of its own right behind the value slots (the
+// workspace of this form is the value slots + nfins x nif doubles: BandDev::offY = nAB, finrom_fom_set_band_mirror); the post by
+// band_sweep<.., NF>, after which the observables sit in registers.
+template <int NSF, int NSP, int NXM, int NF>
+__device__ __forceinline__ void fom_band_fn_body(BandDev p, const int* __restrict__ abmap, const double* __restrict__ Fg,
+                                                 const int* __restrict__ act, const int* __restrict__ ent_extra,
+                                                 const int* __restrict__ ecp_ptr, const int* __restrict__ ecp_slot,
+                                                 const int* __restrict__ ecp_off, const int* __restrict__ schur_off,
+                                                 const double* __restrict__ cw, const int* __restrict__ piv_row,
+                                                 const int* __restrict__ piv_off, double* __restrict__ Gw, int64_t S,
+                                                 double* __restrict__ qoi, int* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) double xlds[];
+  const int lane = threadIdx.x;
+  const int64_t blk = blockIdx.x;
+  double* __restrict__ Gs = Gw + blk * (int64_t)p.gsize * 64;
+  Io io{__builtin_amdgcn_make_buffer_rsrc(Gs, 0, p.gsize * 512, 0x00020000), lane * 8};
+  double* xs = xlds + lane;
+  const PostTables T{act, nullptr, ent_extra, ecp_ptr, ecp_slot, ecp_off};
+  int bad = 0;
+  constexpr int NIFT = (NSF - 1) * NSF / 2;
+  {
+    double win[NSF * (NSF + 1) / 2], yw[NSF];
+    for (int f = 0; f < p.nfins; ++f) {
+      const int npiv = p.npf, ntot = p.npf + p.nif;
+      band_sweep<NSF, false, NXM, false, true>(p, io, xs, Fg, abmap, T, f * ntot, f * npiv, npiv, ntot, f * npiv * NSF, win, yw, bad);
+      fin_functional_out<NSF>(p, io, yw, f, npiv, p.nif);
+      int k = 0;
+      for (int t = 0; t < p.nif; ++t)
+        for (int s = 0; s <= t; ++s, ++k) {
+          const int a = (npiv + t) % NSF, b = (npiv + s) % NSF;
+          double v = 0.0;
+          static_for<0, NSF>([&](auto ac) {
+            static_for<0, decltype(ac)::value + 1>([&](auto bc) {
+              constexpr int ua = decltype(ac)::value, ub = decltype(bc)::value;
+              v = ((a == ua && b == ub) || (a == ub && b == ua)) ? win[tri(ua, ub)] : v;
+            });
+          });
+          const int off = schur_off[f * NIFT + k];
+          io.st(io.ld(off) + v, off);
+        }
+    }
+  }
+  FnState<NF, NSP> fs;
+  fs.T = BandFnDev{cw, piv_row, piv_off};
+  {
+    double win[NSP * (NSP + 1) / 2], yw[NSP];
+    band_sweep<NSP, true, NXM, false, true, NF>(p, io, xs, Fg, abmap, T, p.post_g0, p.post_e0, p.npost, p.npost, p.post_L0, win, yw, bad, &fs);
+  }
+  const int64_t s = blk * 64 + lane;
+  const double nanv = __builtin_nan("");
+  if (bad && info != nullptr && s < S) atomicOr(&info[s], 1);
+  if (s < S)
+    static_for<0, NF>([&](auto oc) {                     // each distinct row once, stored to all its output columns
+      constexpr int o = decltype(oc)::value;
+      if (o < p.n_obs)
+        for (int c = p.out_ptr[o], c1 = p.out_ptr[o + 1]; c < c1; ++c) qoi[s * p.n_out + p.out_col[c]] = bad ? nanv : fs.q[o];
+    });
 }
 
 // ---- the post's backward sweep with the other waves as loaders ----------------------------------------------------------------
@@ -719,7 +823,7 @@ __device__ __forceinline__ void fom_band_ldsw_body(const BandDev& p, const int* 
     for (int f = wv; f < p.nfins; f += WV) {
       const int npiv = p.npf, ntot = p.npf + p.nif;
       band_sweep<NSF, false, NXM, true, QO>(p, io, xs, Fg, abmap, T, f * ntot, f * npiv, npiv, ntot, f * npiv * NSF, win, yw, bad);
-      if constexpr (QO) fin_functional_out<NSF>(p, io, yw, f, npiv);
+      if constexpr (QO) fin_functional_out<NSF>(p, io, yw, f, npiv, npiv);
       int k = 0;
       for (int t = 0; t < p.nif; ++t)
         for (int s = 0; s <= t; ++s, ++k) {
@@ -798,6 +902,18 @@ __global__ __launch_bounds__(64) void fom_band_kernel(FR_BAND_ARGS) { fom_band_b
 #endif
 template <int NSF, int NSP, int NXM, bool QO>
 __global__ __launch_bounds__(64, FINROM_HALF_WPE) void fom_band_half_kernel(FR_BAND_ARGS) { fom_band_body<NSF, NSP, NXM, QO>(FR_BAND_PASS); }
+// The half plan with the post as functionals: 5 x 8 more doubles of right-hand-side windows beside the (5, 8) window, two waves per SIMD
+#ifndef FINROM_HALF_FN_WPE
+#define FINROM_HALF_FN_WPE 2
+#endif
+template <int NSF, int NSP, int NXM>
+__global__ __launch_bounds__(64, FINROM_HALF_FN_WPE) void fom_band_half_fn_kernel(
+    BandDev p, const int* __restrict__ abmap, const double* __restrict__ Fg, const int* __restrict__ act, const int* __restrict__ ent_extra,
+    const int* __restrict__ ecp_ptr, const int* __restrict__ ecp_slot, const int* __restrict__ ecp_off, const int* __restrict__ schur_off,
+    const double* __restrict__ cw, const int* __restrict__ piv_row, const int* __restrict__ piv_off, double* __restrict__ Gw, int64_t S,
+    double* __restrict__ qoi, int* __restrict__ info) {
+  fom_band_fn_body<NSF, NSP, NXM, BAND_NF>(p, abmap, Fg, act, ent_extra, ecp_ptr, ecp_slot, ecp_off, schur_off, cw, piv_row, piv_off, Gw, S, qoi, info);
+}
 template <int NSF, int NSP, int NXM, int WV, bool QO>
 __global__ __launch_bounds__(64 * WV) void fom_band_ldsw_kernel(FR_BAND_ARGS) { fom_band_ldsw_body<NSF, NSP, NXM, WV, QO>(FR_BAND_PASS); }
 
@@ -831,6 +947,15 @@ int launch_t(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi,
   return 0;
 }
 
+template <int NSF, int NSP, int NXM = 2>
+int launch_fn(const BandDev& p, const BandFnDev& fn, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st) {
+  const size_t lds = (size_t)(XL<NSP, NXM>::SIZE + NXM * BAND_NF) * 64 * sizeof(double);      // the extras' state | their functional values
+  hipLaunchKernelGGL((fom_band_half_fn_kernel<NSF, NSP, NXM>), dim3((unsigned)nblk), dim3(64), lds, st, p, p.abmap, p.FgQ, p.act, p.ent_extra,
+                     p.ecp_ptr, p.ecp_slot, p.ecp_off, p.schur_off, fn.cw, fn.piv_row, fn.piv_off, Gw, S, qoi, info);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 #define FR_W4(A, B, X) if (p.NSF == A && p.NSP == B) return qo ? launch_ldsw<A, B, true, X>(p, Gw, nblk, S, qoi, info, st) : launch_ldsw<A, B, false, X>(p, Gw, nblk, S, qoi, info, st);
@@ -857,10 +982,21 @@ int band_path(const BandDev& p, bool qoi_only) {
 }
 
 // qoi_only: the caller wants no w; with the plan's QoI-only tables installed (BandDev::qo) the fins then ride as functionals
-int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qoi_only) {
+// fn: the plan is a half plan in the functional form of the post (its workspace layout holds nothing else: the caller passes the
+// tables with every launch of such a plan)
+int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qoi_only,
+                    const BandFnDev* fn) {
   if (nblk == 0) return 0;
   ScopedKernelTimer t(p.NSP <= 14 ? K_FOM_PATH_BAND_REG : K_FOM_PATH_BAND_LDSW, st);
   const bool qo = qoi_only && p.qo;
+  if (fn != nullptr) {
+    if (!qo || p.out_ptr == nullptr || p.n_obs > BAND_NF) { set_error("fom band sweep: the functional form serves QoI-only calls of a half plan"); return FINROM_ERR_ARG; }
+#define FR_T(A, B) if (p.NSF == A && p.NSP == B) return launch_fn<A, B>(p, *fn, Gw, nblk, S, qoi, info, st);
+    FR_T(3, 4) FR_T(4, 6) FR_T(5, 8)
+#undef FR_T
+    set_error("fom band sweep: unsupported window sizes");
+    return FINROM_ERR_UNSUPPORTED;
+  }
 #define FR_T(A, B) if (p.NSF == A && p.NSP == B) return qo ? launch_t<A, B, true>(p, Gw, nblk, S, qoi, info, st) : launch_t<A, B, false>(p, Gw, nblk, S, qoi, info, st);
   FR_T(3, 6) FR_T(4, 10) FR_T(5, 14)
 #undef FR_T

@@ -52,6 +52,11 @@ struct PostTables {
   const int* act; const int* lx_ptr; const int* ent_extra; const int* ecp_ptr; const int* ecp_slot; const int* ecp_off;
 };
 
+// The post as functionals (fom_band.hip, band_sweep<.., NF>): NF more right-hand-side windows ride the post's forward sweep, one per
+// distinct observation row, and the observables accumulate pivot by pivot -- nothing of the post's factor is stored.
+// (BandFnDev, finrom_core.h: the rows' weights and the pivots that are interface nodes of a row's fin)
+template <int NF, int NS> struct FnState { double zw[NF][NS]; double q[NF]; BandFnDev T; };
+
 constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
 
 // (offR: the region the right-hand side is read from and the solution written to -- p.offY for the forward solve, p.offV for the

@@ -354,6 +354,7 @@ class FomEngine:
         mirror-symmetric (mirror_rows), the half operator has QoI-only tables and the library has the half plan's window sizes.
         Otherwise nothing changes.  FINROM_NO_MIRROR=1 at engine creation switches the form off."""
         self.band_mirror = None
+        self.band_mirror_form = 0
         if _os.environ.get("FINROM_NO_MIRROR") is not None or not self.band_qoi_only:
             return
         form = self.mirror_form(ops, self.xdim, c0_csr, W_csr, rhs, B_obs)
@@ -367,6 +368,9 @@ class FomEngine:
         check(rc, "finrom_fom_set_band_mirror")
         self.band_mirror = bpm
         self.band_mirror_slots = nslots
+        # 2: the post's observation rows ride its forward sweep as functionals (no stored factor); 1: the stored-factor form --
+        # a descriptor that does not fit the functional form, or FINROM_FOM_POST_STORED=1 at engine creation
+        self.band_mirror_form = int(lib().finrom_fom_band_mirror_form(self._h))
 
     def solve(self, X, want_w=False):
         b = _Batch(X, self.xdim)

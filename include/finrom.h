@@ -268,6 +268,20 @@ int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* desc,
 /* Its checks, host only: finrom_fom_band_validate for (n_half, xdim, n_rows), plus the output map for n_obs columns. */
 int finrom_fom_band_mirror_validate(const finrom_fom_band_desc* desc, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
                                     const int32_t* out_ptr, const int32_t* out_col);
+/* The post as functionals: where the half descriptor fits -- n_rows <= 5, every row's fin weights on the one fin its qoi_row_fin
+ * names, no post node an interface node of two fins that rows own -- finrom_fom_set_band_mirror derives, per distinct row o, the
+ * weights c_o on the post and lets them ride the post's forward sweep as right-hand sides: q_o = (L^-1 c_o)^T (L^-1 f), no stored
+ * factor, no backward sweep; the plan's workspace is then nAB + nfins x nif doubles per sample.  A descriptor that does not fit
+ * keeps the stored-factor form, as every descriptor does with FINROM_FOM_POST_STORED=1 in the environment of the set call.
+ * finrom_fom_band_mirror_validate checks the derived tables too (every index in range, the operator rebuilt from them equal to
+ * obs_*).  finrom_fom_band_mirror_functionals (host only) returns them: *fits = 0 and nothing written, or *fits = 1 and
+ * cw [npost x 5] (pivot-major: row o's post-only weight on post pivot t at cw[5 t + o]), piv_row [npost] (the row whose fin has
+ * pivot t as an interface node, -1: none) and piv_off [npost] (f * nif + k: that node is interface node k of fin f). */
+int finrom_fom_band_mirror_functionals(const finrom_fom_band_desc* desc, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                       const int32_t* out_ptr, const int32_t* out_col, int32_t* fits, double* cw, int32_t* piv_row,
+                                       int32_t* piv_off);
+/* 0: the handle has no half plan; 1: half plan with the post's factor stored; 2: half plan with the post as functionals. */
+int finrom_fom_band_mirror_form(finrom_fom_t h);
 
 /* The adjoint gradient on the band sweep's layout (finrom_fom_gradient for batches beyond the small-batch schedule): after the
  * full sweep the workspace holds the factor and w; A v = -B_obs^T (B_obs w - d) is solved with the stored columns (one forward
