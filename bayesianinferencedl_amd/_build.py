@@ -11,8 +11,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libfinrom_hip.so")
-SOURCES = ["finrom_api.hip", "fom_kernels.hip", "fom_band.hip", "fom_band_wide.hip", "fom_band_adjoint.hip", "rom_kernels.hip", "rom_proj_wide.hip", "rom_proj_half.hip", "rom_proj_single.hip", "rom_onesample.hip", "rom_gram.hip", "util_kernels.hip", "mlp_kernels.hip", "mlp_train.hip", "hmc_kernels.hip", "hmc_metric.hip", "hmc_stats.hip", "hmc_model.hip", "lbfgs_kernels.hip", "field_prior.hip", "comm.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("finrom_core.h", "finrom_internal.h", "rom_proj_device.h", "fom_band_device.h", "mlp_device.h", "block_reduce.h")] + [os.path.join(ROOT, "include", "finrom.h")]
+# the host layer behind the C ABI: what build_asan() instruments
+API_SOURCES = ["finrom_api.hip", "fom_band_tables.hip", "rom_tables.hip"]
+SOURCES = API_SOURCES + ["fom_kernels.hip", "fom_band.hip", "fom_band_wide.hip", "fom_band_adjoint.hip", "rom_kernels.hip", "rom_proj_wide.hip", "rom_proj_half.hip", "rom_proj_single.hip", "rom_onesample.hip", "rom_gram.hip", "util_kernels.hip", "mlp_kernels.hip", "mlp_train.hip", "hmc_kernels.hip", "hmc_metric.hip", "hmc_stats.hip", "hmc_model.hip", "lbfgs_kernels.hip", "field_prior.hip", "comm.hip"]
+HEADERS = [os.path.join(CSRC, h) for h in ("finrom_core.h", "finrom_internal.h", "rom_proj_device.h", "fom_band_device.h", "mlp_device.h", "block_reduce.h", "api_private.h", "rom_tables.h")] + [os.path.join(ROOT, "include", "finrom.h")]
 
 
 def _deps(path, seen=None):
@@ -85,23 +87,26 @@ if __name__ == "__main__":
 
 
 def build_asan() -> str:
-    """Host-side AddressSanitizer + UBSan build of the C-ABI layer (csrc/finrom_api.hip: the create-time validators of every
-    descriptor) for the CPU box: only the HOST code of finrom_api.hip is instrumented (-Xarch_host), the kernels' objects are
+    """Host-side AddressSanitizer + UBSan build of the C-ABI layer (API_SOURCES: the create-time validators of every
+    descriptor) for the CPU box: only the HOST code of those units is instrumented (-Xarch_host), the kernels' objects are
     the product's.  GPU sanitizers are not available on this pool; tools/asan_validators.py drives the corrupt-descriptor
     cases through this library without a GPU (a corrupt descriptor is rejected before any device call)."""
     build()
     hipcc = _hipcc()
-    obj = os.path.join(LIBDIR, "finrom_api_asan.o")
     lib = os.path.join(LIBDIR, "libfinrom_hip_asan.so")
     san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer"]
-    src = os.path.join(CSRC, "finrom_api.hip")
-    if _stale(obj, sorted(_deps(src))):
-        r = subprocess.run([hipcc, *FLAGS, "-O1", "-g", *san, "-c", src, "-o", obj], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("hipcc (asan) failed:\n" + r.stdout + r.stderr)
-    others = [os.path.join(LIBDIR, s_.replace(".hip", ".o")) for s_ in SOURCES if s_ != "finrom_api.hip"]
-    if _stale(lib, [obj] + others):
-        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *san[:2], "-o", lib, obj, *others], capture_output=True, text=True)
+    objs = []
+    for s_ in API_SOURCES:
+        src = os.path.join(CSRC, s_)
+        obj = os.path.join(LIBDIR, s_.replace(".hip", "_asan.o"))
+        objs.append(obj)
+        if _stale(obj, sorted(_deps(src))):
+            r = subprocess.run([hipcc, *FLAGS, "-O1", "-g", *san, "-c", src, "-o", obj], capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("hipcc (asan) failed:\n" + r.stdout + r.stderr)
+    others = [os.path.join(LIBDIR, s_.replace(".hip", ".o")) for s_ in SOURCES if s_ not in API_SOURCES]
+    if _stale(lib, objs + others):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *san[:2], "-o", lib, *objs, *others], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc (asan link) failed:\n" + r.stdout + r.stderr)
     return lib

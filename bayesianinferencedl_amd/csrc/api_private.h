@@ -1,0 +1,119 @@
+// Private to the host layer (finrom_api.hip, fom_band_tables.hip, rom_tables.hip): the handle structs behind
+// include/finrom.h's opaque pointers, and the few helpers one of those units defines and another calls.  No kernel source
+// includes this header.
+#pragma once
+#include "finrom_internal.h"
+#include "rom_tables.h"
+
+using namespace finrom;      // (the handle structs are the C ABI's: global names, made of finrom:: parts)
+
+struct finrom_fom_s {
+  FomDev d{};
+  FomSmallDev small{};
+  BandDev band{};                      // frontal band sweep (finrom_fom_set_band); band.on = 0: interpreter
+  BandGradDev band_grad{};             // adjoint gradient on the band layout (finrom_fom_set_band_gradient)
+  FomDev band_asm{};                   // parameters of the band sweep's assembly pre-pass (fom_assemble_kernel)
+  // half-domain plan of a mirror-symmetric operator (finrom_fom_set_band_mirror): serves the calls that want no w
+  BandDev band_m{};
+  FomDev band_m_asm{};
+  BandFnDev band_m_fn{};               // cw != nullptr: band_m is in the functional form of the post (no stored factor; DESIGN 4c')
+  const BandDev& band_for(bool want_w) const { return !want_w && band_m.on ? band_m : band; }
+  std::vector<void*> owned;
+  Scratch xT, Gw, gradT, qtmp;
+  Scratch hgrad;                       // finrom_hmc_leapfrog_fom without grad_out: the gradient between the FOM's launches and the kick
+  int last_path = FINROM_FOM_PATH_NONE;   // finrom_fom_last_path
+};
+struct finrom_rom_s {
+  RomDev d{};
+  std::vector<void*> owned;
+  Scratch Ar, Br, theta, qtmp, vw, grad_ticket, part, ext;
+  int g_npairs = 0; const int* g_pair_p = nullptr; const int* g_pair_i = nullptr; const double* g_Gt = nullptr;
+  RomGramDev gram;                     // offline/online form (finrom_rom_set_gram); gram.h is filled at create
+  int projection = FINROM_PROJECTION_DIRECT;
+  std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
+  int mirror_n = 0;                    // rows of the installed half descriptor
+  int mirror_counts[2][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / the short list
+  int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
+  int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
+  bool short_grouped = env_rom_short_grouped();      // (A/B, read at creation: the short half list keeps a group per leading parameter, as before group_pays)
+  bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
+  hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's
+  // waves then share SIMDs with the projection on those CUs only, and run faster for being fewer.  cus < 0: per_se = -cus
+  // CUs in every shader engine (the mask's bit i is CU i / n_se of shader engine i % n_se -- measured: the first 32 c bits give the
+  // sweep the same speed as any 32 c' <= bits < 32 (c + 1), and bit patterns that fill whole engines starve the dispatcher)
+  hipStream_t fom_side = nullptr; hipEvent_t ev_join_fom = nullptr; int fom_side_cus = 0;
+  int ensure_fom_side(int cus) {
+    if (fom_side_cus == cus && (fom_side || cus != 0)) return 0;      // (made, or refused by the runtime once: do not ask again)
+    if (call_captures() || any_capture()) { set_error("the FOM side stream cannot be created while a stream capture is open"); return FINROM_ERR_UNSUPPORTED; }
+    if (fom_side) { (void)hipStreamDestroy(fom_side); fom_side = nullptr; }
+    int dev = 0; hipDeviceProp_t pr;
+    FR_HIP(hipGetDevice(&dev));
+    FR_HIP(hipGetDeviceProperties(&pr, dev));
+    const int ncu = pr.multiProcessorCount;
+    const int want = cus;
+    if (cus < 0) cus = -cus * (ncu / 8);                 // (eight CUs per shader engine on gfx950)
+    if (cus < 1 || cus > ncu) { set_error("FINROM_FOM_CUS out of range"); return FINROM_ERR_ARG; }
+    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
+    for (int b = 0; b < cus; ++b) mask[b >> 5] |= 1u << (b & 31);      // the first `cus` bits
+    // (a runtime that refuses the mask is not an error of the call: the FOM half then stays on the caller's stream, as before)
+    if (hipExtStreamCreateWithCUMask(&fom_side, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); fom_side = nullptr; fom_side_cus = want; return 0; }
+    if (!ev_join_fom) FR_HIP(hipEventCreateWithFlags(&ev_join_fom, hipEventDisableTiming));
+    fom_side_cus = want;
+    return 0;
+  }
+  int ensure_side() {
+    if (side) return 0;
+    if (call_captures() || any_capture()) { set_error("the library's side stream cannot be created while a stream capture is open: run the call once before the capture"); return FINROM_ERR_UNSUPPORTED; }
+    int lo = 0, hi = 0;
+    FR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));          // numerically lower = higher priority
+    FR_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, hi));
+    FR_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    FR_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    return 0;
+  }
+  // finrom_romml_grad -> finrom_rom_grad (one-sample form only): leave the gradient's partial sums to the consumer; where they are
+  bool defer_gsum = false; const double* last_gpart = nullptr;
+  const MlpFuse* fuse = nullptr;       // (same path) the error model's forward pass as a workgroup of the contraction kernel
+  const MlpBackFuse* back = nullptr;   // (same path) its walk back through the hidden layers as a workgroup of the gradient contraction
+  bool info_store = false;             // (same path) the solve kernel stores info instead of or-ing into it
+};
+struct finrom_sampler_s {
+  double* U = nullptr; int n = 0; Scratch xi;
+  Scratch fpart, ftick;                // finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field: partial sums, arrival counters
+};
+struct finrom_metric_s { MetricDev d{}; };
+struct finrom_mlp_s {
+  MlpDev d{}; std::vector<void*> owned; Scratch tape, theta, gth, shift, qtmp, etmp, g0, y0p, thp;
+  // finrom_hmc_leapfrog: the partial sums of theta the last step left in thp, and the field they belong to (position buffer,
+  // momentum buffer, step size, chains): the next step uses them only if it is that field's step
+  const double* carry_k = nullptr; const double* carry_mom = nullptr; double carry_eps = 0.0; int64_t carry_S = 0;
+};
+
+namespace finrom {
+template <class T>
+int up(std::vector<void*>& owned, const T** dst, const T* host, size_t count) {
+  T* dp = nullptr;
+  int rc = upload(&dp, host, count);
+  if (rc) return rc;
+  if (dp) owned.push_back(dp);
+  *dst = dp;
+  return 0;
+}
+
+// the runtime part of finrom_api.hip
+bool overlap_enabled();                    // finrom_set_overlap's flag (finrom_solve_pairs reads it)
+
+// fom_band_tables.hip (host only)
+int validate_band(const finrom_fom_band_desc* a, int n, int xdim, int n_obs, int64_t* gsize_out, int64_t* nL_out);
+int validate_band_mirror(const finrom_fom_band_desc* a, int n_half, int xdim, int n_rows, int n_obs, const int32_t* out_ptr,
+                         const int32_t* out_col, int64_t* gsize_out, int64_t* nL_out);
+int derive_post_functionals(const finrom_fom_band_desc* a, int n_half, int n_rows, std::vector<double>& cw, std::vector<int>& piv_row,
+                            std::vector<int>& piv_off);
+
+// the FOM half as finrom_solve_pairs runs it, in stages (finrom_api.hip)
+bool env_no_band();                        // FINROM_NO_BAND, read once per process
+int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr);
+int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages);
+}  // namespace finrom

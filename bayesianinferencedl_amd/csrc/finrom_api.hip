@@ -1,13 +1,13 @@
-// extern "C" surface of libfinrom_hip.so (see include/finrom.h for the contract).
-#include "finrom_internal.h"
+// extern "C" surface of libfinrom_hip.so (see include/finrom.h for the contract), in four parts: the runtime services, the FOM
+// handle, the ROM handle with finrom_solve_pairs, inference (sampler, mlp, hmc, metric, lbfgs).  The host-only table builders and
+// validators are rom_tables.hip's and fom_band_tables.hip's.  An extern "C" region is open only around entry
+// points; every helper stands outside one.
+#include "api_private.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <iterator>
-#include <map>
 #include <mutex>
-#include <numeric>
 
 namespace finrom {
 
@@ -147,119 +147,8 @@ static void drain_pending() {
   }
   g_pending.clear();
 }
+bool overlap_enabled() { return g_overlap; }
 
-int launch_subfin_avg(const double*, int, int, const double*, int64_t, double*, hipStream_t);
-int launch_sampler(const double*, int, const double*, int64_t, double*, hipStream_t);
-int launch_sub(const double*, const double*, int64_t, double*, hipStream_t);
-int launch_sub_flagged(const double*, double*, const int*, int, int64_t, double*, hipStream_t);
-int launch_philox_normal(unsigned long long, int64_t, int64_t, int, double*, hipStream_t);
-int launch_hmc_draw(const unsigned long long*, int64_t, int, int64_t, int64_t, double*, double*, hipStream_t);
-
-}  // namespace finrom
-
-using namespace finrom;
-
-struct finrom_fom_s {
-  FomDev d{};
-  FomSmallDev small{};
-  BandDev band{};                      // frontal band sweep (finrom_fom_set_band); band.on = 0: interpreter
-  BandGradDev band_grad{};             // adjoint gradient on the band layout (finrom_fom_set_band_gradient)
-  FomDev band_asm{};                   // parameters of the band sweep's assembly pre-pass (fom_assemble_kernel)
-  // half-domain plan of a mirror-symmetric operator (finrom_fom_set_band_mirror): serves the calls that want no w
-  BandDev band_m{};
-  FomDev band_m_asm{};
-  BandFnDev band_m_fn{};               // cw != nullptr: band_m is in the functional form of the post (no stored factor; DESIGN 4c')
-  const BandDev& band_for(bool want_w) const { return !want_w && band_m.on ? band_m : band; }
-  std::vector<void*> owned;
-  Scratch xT, Gw, gradT, qtmp;
-  Scratch hgrad;                       // finrom_hmc_leapfrog_fom without grad_out: the gradient between the FOM's launches and the kick
-  int last_path = FINROM_FOM_PATH_NONE;   // finrom_fom_last_path
-};
-struct finrom_rom_s {
-  RomDev d{};
-  std::vector<void*> owned;
-  Scratch Ar, Br, theta, qtmp, vw, grad_ticket, part, ext;
-  int g_npairs = 0; const int* g_pair_p = nullptr; const int* g_pair_i = nullptr; const double* g_Gt = nullptr;
-  RomGramDev gram;                     // offline/online form (finrom_rom_set_gram); gram.h is filled at create
-  int projection = FINROM_PROJECTION_DIRECT;
-  std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
-  int mirror_n = 0;                    // rows of the installed half descriptor
-  int mirror_counts[2][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / the short list
-  int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
-  int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
-  bool short_grouped = getenv("FINROM_ROM_SHORT_GROUPED") != nullptr;      // (A/B, read at creation: the short half list keeps a group per leading parameter, as before group_pays)
-  bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
-  hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's
-  // waves then share SIMDs with the projection on those CUs only, and run faster for being fewer.  cus < 0: per_se = -cus
-  // CUs in every shader engine (the mask's bit i is CU i / n_se of shader engine i % n_se -- measured: the first 32 c bits give the
-  // sweep the same speed as any 32 c' <= bits < 32 (c + 1), and bit patterns that fill whole engines starve the dispatcher)
-  hipStream_t fom_side = nullptr; hipEvent_t ev_join_fom = nullptr; int fom_side_cus = 0;
-  int ensure_fom_side(int cus) {
-    if (fom_side_cus == cus && (fom_side || cus != 0)) return 0;      // (made, or refused by the runtime once: do not ask again)
-    if (call_captures() || any_capture()) { set_error("the FOM side stream cannot be created while a stream capture is open"); return FINROM_ERR_UNSUPPORTED; }
-    if (fom_side) { (void)hipStreamDestroy(fom_side); fom_side = nullptr; }
-    int dev = 0; hipDeviceProp_t pr;
-    FR_HIP(hipGetDevice(&dev));
-    FR_HIP(hipGetDeviceProperties(&pr, dev));
-    const int ncu = pr.multiProcessorCount;
-    const int want = cus;
-    if (cus < 0) cus = -cus * (ncu / 8);                 // (eight CUs per shader engine on gfx950)
-    if (cus < 1 || cus > ncu) { set_error("FINROM_FOM_CUS out of range"); return FINROM_ERR_ARG; }
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    for (int b = 0; b < cus; ++b) mask[b >> 5] |= 1u << (b & 31);      // the first `cus` bits
-    // (a runtime that refuses the mask is not an error of the call: the FOM half then stays on the caller's stream, as before)
-    if (hipExtStreamCreateWithCUMask(&fom_side, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); fom_side = nullptr; fom_side_cus = want; return 0; }
-    if (!ev_join_fom) FR_HIP(hipEventCreateWithFlags(&ev_join_fom, hipEventDisableTiming));
-    fom_side_cus = want;
-    return 0;
-  }
-  int ensure_side() {
-    if (side) return 0;
-    if (call_captures() || any_capture()) { set_error("the library's side stream cannot be created while a stream capture is open: run the call once before the capture"); return FINROM_ERR_UNSUPPORTED; }
-    int lo = 0, hi = 0;
-    FR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));          // numerically lower = higher priority
-    FR_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, hi));
-    FR_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    FR_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    return 0;
-  }
-  // finrom_romml_grad -> finrom_rom_grad (one-sample form only): leave the gradient's partial sums to the consumer; where they are
-  bool defer_gsum = false; const double* last_gpart = nullptr;
-  const MlpFuse* fuse = nullptr;       // (same path) the error model's forward pass as a workgroup of the contraction kernel
-  const MlpBackFuse* back = nullptr;   // (same path) its walk back through the hidden layers as a workgroup of the gradient contraction
-  bool info_store = false;             // (same path) the solve kernel stores info instead of or-ing into it
-};
-struct finrom_sampler_s {
-  double* U = nullptr; int n = 0; Scratch xi;
-  Scratch fpart, ftick;                // finrom_sampler_field / _pullback / finrom_hmc_leapfrog_field: partial sums, arrival counters
-};
-struct finrom_metric_s { MetricDev d{}; };
-struct finrom_mlp_s {
-  MlpDev d{}; std::vector<void*> owned; Scratch tape, theta, gth, shift, qtmp, etmp, g0, y0p, thp;
-  // finrom_hmc_leapfrog: the partial sums of theta the last step left in thp, and the field they belong to (position buffer,
-  // momentum buffer, step size, chains): the next step uses them only if it is that field's step
-  const double* carry_k = nullptr; const double* carry_mom = nullptr; double carry_eps = 0.0; int64_t carry_S = 0;
-};
-
-template <class T>
-static int up(std::vector<void*>& owned, const T** dst, const T* host, size_t count) {
-  T* dp = nullptr;
-  int rc = upload(&dp, host, count);
-  if (rc) return rc;
-  if (dp) owned.push_back(dp);
-  *dst = dp;
-  return 0;
-}
-
-extern "C" {
-
-int finrom_version(void) { return FINROM_ABI_VERSION; }
-const char* finrom_last_error(void) { return g_err.c_str(); }
-
-int finrom_device_count(int* count) { if (!count) return FINROM_ERR_ARG; FR_HIP(hipGetDeviceCount(count)); return 0; }
-int finrom_set_device(int ordinal) { FR_HIP(hipSetDevice(ordinal)); return 0; }
 // finrom_malloc / finrom_free recycle small buffers (<= 16 MiB, size classes = powers of two, at most 256 MiB parked): the scalar
 // call surface allocates a handful of small buffers per call, and hipMalloc / hipFree cost more than its kernels.  A parked
 // buffer carries the event finrom_free_async recorded behind its last user; the next owner waits for it.
@@ -275,6 +164,17 @@ size_t size_class(size_t bytes) { size_t c = 256; while (c < bytes) c <<= 1; ret
 void event_destroy_cb(void* e) { (void)hipEventDestroy((hipEvent_t)e); }
 }  // namespace
 
+}  // namespace finrom
+
+using namespace finrom;
+
+extern "C" {
+
+int finrom_version(void) { return FINROM_ABI_VERSION; }
+const char* finrom_last_error(void) { return g_err.c_str(); }
+
+int finrom_device_count(int* count) { if (!count) return FINROM_ERR_ARG; FR_HIP(hipGetDeviceCount(count)); return 0; }
+int finrom_set_device(int ordinal) { FR_HIP(hipSetDevice(ordinal)); return 0; }
 int finrom_malloc(void** dptr, size_t bytes) {
   if (!dptr) return FINROM_ERR_ARG;
   *dptr = nullptr;
@@ -314,6 +214,7 @@ int finrom_malloc(void** dptr, size_t bytes) {
   if (bytes <= kPoolMaxEach) { std::lock_guard<std::mutex> lk(g_pool_mu); g_pool_live.emplace_back(*dptr, cap); }
   return 0;
 }
+}  // extern "C"
 // stream: the stream of the buffer's last user, or NULL when that user is known to have finished / ran on the default stream
 static int pool_free(void* dptr, hipStream_t stream, bool have_stream) {
   if (!dptr) return 0;
@@ -352,6 +253,7 @@ static int pool_free(void* dptr, hipStream_t stream, bool have_stream) {
   dev_free(dptr);
   return 0;
 }
+extern "C" {
 int finrom_free(void* dptr) { return pool_free(dptr, nullptr, false); }
 int finrom_free_async(void* dptr, void* stream) { return pool_free(dptr, (hipStream_t)stream, true); }
 int finrom_note_stream(void* stream) {
@@ -409,6 +311,10 @@ int finrom_profile_read(int slot, const char** name, int64_t* launches, double* 
   if (total_ms) *total_ms = g_ms[slot];
   return 0;
 }
+
+}  // extern "C"
+
+extern "C" {
 
 // ---------------------------------------------------------------------------------------
 // FOM
@@ -558,9 +464,19 @@ void finrom_fom_destroy(finrom_fom_t h) {
   delete h;
 }
 
+}  // extern "C"
+namespace finrom {
+// FINROM_NO_BAND (A/B: the interpreter although the mesh has a band plan): read once per process, by whichever of
+// fom_solve_stages, finrom_fom_gradient and finrom_solve_pairs is called first; all three see that value
+bool env_no_band() { static const bool v = getenv("FINROM_NO_BAND") != nullptr; return v; }
+// equal pieces when the batch exceeds the workspace bound `limit` (a short last piece would leave the GPU mostly idle)
+static int64_t fom_equal_chunk(int64_t S, int64_t limit) {
+  const int64_t npieces = (S + limit - 1) / limit;
+  return npieces <= 1 ? limit : ((S + npieces - 1) / npieces + 63) / 64 * 64;
+}
 // stages: 1 = pack + assembly, 2 = interpreter (+ unpack of w), 3 = both.  finrom_solve_pairs runs stage 1, then
 // launches the ROM half, then stage 2 (only possible when the batch fits one workspace chunk).
-static int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr) {
+int64_t fom_chunk_samples(const FomDev& d, const BandDev* band) {
   // bound the per-call workspace (L values dominate: nnzL * 8 B per sample)
   const size_t per_sample = ((size_t)(band && band->on ? band->gsize : d.gsize) + d.xdim) * sizeof(double);
   // (FINROM_FOM_WORKSPACE_BYTES=<n>, read per call: another bound, so that a test can make a small batch run in pieces)
@@ -569,29 +485,26 @@ static int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr)
   const int64_t chunk = bound / (int64_t)per_sample;
   return std::max<int64_t>(64, chunk / 64 * 64);
 }
-static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st,
-                            int stages) {
+int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages) {
   const FomDev& d = h->d;
-  static const bool env_no_band = getenv("FINROM_NO_BAND") != nullptr;
+  const bool no_band = env_no_band();
   // Small batches: where the mesh has a band plan the band sweep serves them too -- ONE wave walking its 1597 pivots takes 1.7 ms
   // (QoI only) / 2.3 ms (with w) at m = 12 and 4.2 / 4.4 ms at m = 20, the level-scheduled small-batch kernel 2.7 and 17.9 ms
   // (tools/fom_small_vs_band.py) -- so the latency-oriented schedule (one workgroup per sample) is the forward path only of
   // meshes without window sizes (m >= 32); finrom_fom_gradient keeps it for small batches (its adjoint stage beats a lone wave
   // of the band adjoint kernel: 3.1 against 10 ms).
-  if (h->small.small_max > 0 && S <= h->small.small_max && !(h->band.on && !env_no_band)) {
+  if (h->small.small_max > 0 && S <= h->small.small_max && !(h->band.on && !no_band)) {
     int rc;
     if (!h->small.in_lds && (rc = h->Gw.reserve((size_t)S * d.gsize * sizeof(double)))) return rc;
     if (!(stages & 2)) return 0;
     h->last_path = h->small.in_lds ? FINROM_FOM_PATH_SMALL_LDS : FINROM_FOM_PATH_SMALL_GLOBAL;
     return launch_fom_small(d, h->small, x, S, (double*)h->Gw.p, qoi, w, info, st);
   }
-  if (h->band.on && !env_no_band) {
+  if (h->band.on && !no_band) {
     const BandDev& b = h->band_for(w != nullptr);        // (the half plan of a mirror-symmetric operator when nobody wants w)
     const FomDev& basm = &b == &h->band_m ? h->band_m_asm : h->band_asm;
     h->last_path = band_path(b, w == nullptr);
-    const int64_t limit = fom_chunk_samples(d, &b);
-    const int64_t npieces = (S + limit - 1) / limit;
-    const int64_t chunk = npieces <= 1 ? limit : ((S + npieces - 1) / npieces + 63) / 64 * 64;
+    const int64_t chunk = fom_equal_chunk(S, fom_chunk_samples(d, &b));
     for (int64_t s0 = 0; s0 < S; s0 += chunk) {
       const int64_t Sc = std::min(chunk, S - s0), nblk = (Sc + 63) / 64;
       int rc;
@@ -612,9 +525,7 @@ static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* 
     return 0;
   }
   h->last_path = FINROM_FOM_PATH_INTERPRETER;
-  // equal pieces when the batch exceeds the workspace bound (a short last piece would leave the GPU mostly idle)
-  const int64_t limit = fom_chunk_samples(d), npieces = (S + limit - 1) / limit;
-  const int64_t chunk = npieces <= 1 ? limit : ((S + npieces - 1) / npieces + 63) / 64 * 64;
+  const int64_t chunk = fom_equal_chunk(S, fom_chunk_samples(d));
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int64_t Sc = std::min(chunk, S - s0);
     const int64_t nblk = (Sc + 63) / 64;
@@ -634,6 +545,8 @@ static int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* 
   }
   return 0;
 }
+}  // namespace finrom
+extern "C" {
 
 int finrom_fom_solve(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, void* stream) {
   CallGuard cg((hipStream_t)stream);
@@ -746,120 +659,7 @@ int finrom_fom_set_small(finrom_fom_t h, const finrom_fom_small_desc* a) {
   return 0;
 }
 
-// Host-only check of a band descriptor against the sizes of the FOM it belongs to (every index the kernels dereference, the
-// privacy of the slots the fins write to, the window / pipeline preconditions).  No device call: also exported as
-// finrom_fom_band_validate so that a descriptor can be checked on a box without a GPU (tools/asan_validators.py).
-static int validate_band(const finrom_fom_band_desc* a, int n, int xdim, int n_obs, int64_t* gsize_out, int64_t* nL_out) {
-  if (!a || n <= 0 || xdim <= 0 || n_obs < 0) { set_error("fom_set_band: null argument"); return FINROM_ERR_ARG; }
-  struct { int n, xdim, n_obs; } d{n, xdim, n_obs};
-  auto bad = [&](const char* what) { set_error(std::string("fom_set_band: invalid ") + what); return FINROM_ERR_ARG; };
-  if (!band_supported(a->NSF, a->NSP, a->NX)) { set_error("fom_set_band: window sizes not built into the library"); return FINROM_ERR_UNSUPPORTED; }
-  if (a->nfins < 0 || a->npf < 0 || a->nif != a->NSF - 1 || a->npost <= 0 || a->nAB <= 0 || a->nterms < 0 || a->nLx < 0) return bad("sizes");
-  // the sweeps' prologue fills a whole window of NS nodes and their software pipelines request the entering node NS positions
-  // ahead of the pivot: a segment with fewer pivots than window slots is not a shape the kernels were written for
-  if (a->nfins > 0 && a->npf < a->NSF) return bad("npf (a fin needs at least NSF pivots)");
-  if (a->npost < a->NSP) return bad("npost (the post needs at least NSP pivots)");
-  const int G = a->nfins * (a->npf + a->nif) + a->npost;
-  if ((int64_t)a->nfins * a->npf + a->npost != n) return bad("pivot count (must equal the number of dofs)");
-  // every table is dereferenced below and by the kernels: a missing pointer is a descriptor error, not a host fault
-  if (!a->abmap || !a->ab_c0 || !a->ab_ptr || !a->Fg || !a->act || !a->lx_ptr || !a->ent_extra || !a->ecp_ptr || !a->perm ||
-      (a->nterms > 0 && (!a->ab_idx || !a->ab_w)) || (a->nfins > 0 && (!a->schur_off || !a->iface_elim)) ||
-      (d.n_obs > 0 && !a->obs_ptr)) return bad("table pointer (null)");
-  for (int e = 0; e < 3 * G; ++e) if (a->abmap[e] < 0 || a->abmap[e] >= a->nAB) return bad("abmap");
-  const int64_t nL = (int64_t)a->nfins * a->npf * a->NSF + (int64_t)a->npost * a->NSP;
-  const int64_t gsize = (int64_t)a->nAB + nL + a->nLx + n + band_xsize(a->NSP) + n;      // ... | y -> w | extras (LDS variant) | adjoint
-  if (gsize * 512 >= (int64_t)1 << 31) { set_error("fom_set_band: workspace too long for 32-bit buffer offsets"); return FINROM_ERR_UNSUPPORTED; }
-  if (a->ab_ptr[0] != 0 || a->ab_ptr[a->nAB] != a->nterms) return bad("ab_ptr");
-  for (int e = 0; e < a->nAB; ++e) if (a->ab_ptr[e + 1] < a->ab_ptr[e]) return bad("ab_ptr");
-  for (int t = 0; t < a->nterms; ++t) if (a->ab_idx[t] < 0 || a->ab_idx[t] >= d.xdim) return bad("ab_idx");
-  if (a->lx_ptr[0] != 0 || a->lx_ptr[a->npost] != a->nLx || a->ecp_ptr[0] != 0) return bad("lx_ptr / ecp_ptr");
-  for (int p = 0; p < a->npost; ++p) {
-    if (a->act[p] < 0 || a->act[p] >= (1 << a->NX)) return bad("act");
-    if (a->lx_ptr[p + 1] - a->lx_ptr[p] != __builtin_popcount((unsigned)a->act[p])) return bad("lx_ptr (must count the bits of act)");
-    if (a->ent_extra[p] < 0 || a->ent_extra[p] > a->NX) return bad("ent_extra");
-    if (a->ecp_ptr[p + 1] < a->ecp_ptr[p]) return bad("ecp_ptr");
-  }
-  const int necp_ = a->ecp_ptr[a->npost];
-  if (necp_ > 0 && (!a->ecp_slot || !a->ecp_off)) return bad("table pointer (null)");
-  for (int c = 0; c < necp_; ++c)
-    if (a->ecp_slot[c] < 0 || a->ecp_slot[c] >= a->NX || a->ecp_off[c] < 0 || a->ecp_off[c] >= a->nAB) return bad("ecp_slot / ecp_off");
-  const int nift = a->nif * (a->nif + 1) / 2;
-  for (int t = 0; t < a->nfins * nift; ++t) if (a->schur_off[t] < 0 || a->schur_off[t] >= a->nAB) return bad("schur_off");
-  // (interface nodes are POST nodes: the fins' backward sweeps read their w after the post's has written it)
-  for (int t = 0; t < a->nfins * a->nif; ++t) if (a->iface_elim[t] < a->nfins * a->npf || a->iface_elim[t] >= n) return bad("iface_elim");
-  {
-    // The fins of a workgroup are swept by DIFFERENT waves (fom_band_ldsw_kernel), each adding its Schur complement to the post's
-    // value slots with a plain load-add-store: a slot written by two fins would race.  Slots are private per fin, distinct
-    // within a fin, and not shared with plain (read-only, de-duplicated) value slots of segment nodes other than the post's
-    // own interface entries -- i.e. a Schur / extra-coupling slot appears in abmap at most once.
-    std::vector<int> owner(a->nAB, -1);                 // fin that writes the slot
-    for (int f = 0; f < a->nfins; ++f)
-      for (int t = 0; t < nift; ++t) {
-        const int off = a->schur_off[f * nift + t];
-        if (owner[off] >= 0) return bad(owner[off] == f ? "schur_off (slot repeated within a fin)" : "schur_off (slot shared by two fins)");
-        owner[off] = f;
-      }
-    std::vector<int> uses(a->nAB, 0);
-    for (int e = 0; e < 3 * G; ++e) if (a->abmap[e] >= 0 && a->abmap[e] < a->nAB) ++uses[a->abmap[e]];
-    for (int c = 0; c < necp_; ++c) ++uses[a->ecp_off[c]];
-    for (int e = 0; e < a->nAB; ++e) if (owner[e] >= 0 && uses[e] > 1) return bad("schur_off (a slot the fins write to is read by more than one entry)");
-  }
-  {
-    std::vector<char> seen(n, 0);
-    for (int i = 0; i < n; ++i) { int v = a->perm[i]; if (v < 0 || v >= n || seen[v]) return bad("perm"); seen[v] = 1; }
-  }
-  if (d.n_obs > 0) {
-    if (a->obs_ptr[0] != 0) return bad("obs_ptr");
-    for (int o = 0; o < d.n_obs; ++o) if (a->obs_ptr[o + 1] < a->obs_ptr[o]) return bad("obs_ptr");
-    if (a->obs_ptr[d.n_obs] > 0 && (!a->obs_idx || !a->obs_w)) return bad("table pointer (null)");
-    for (int t = 0; t < a->obs_ptr[d.n_obs]; ++t) if (a->obs_idx[t] < 0 || a->obs_idx[t] >= n) return bad("obs_idx");
-  }
-  // the fins' sweeps do not carry a load on their own nodes over to the interface nodes' right-hand sides
-  for (int f = 0; f < a->nfins; ++f)
-    for (int t = 0; t < a->npf + a->nif; ++t)
-      if (a->Fg[f * (a->npf + a->nif) + t] != 0.0) { set_error("fom_set_band: load on a fin's segment nodes is not supported by the sweep"); return FINROM_ERR_UNSUPPORTED; }
-  // QoI-only tables: the same operator as obs_*, entry by entry
-  const int nq = (a->qoi_FgQ != nullptr) + (a->qoi_row_fin != nullptr) + (a->qoi_obs_ptr != nullptr);
-  if (nq != 0) {
-    if (nq != 3 || d.n_obs <= 0) return bad("QoI-only tables (all or none)");
-    const int post_e0 = a->nfins * a->npf, post_g0 = a->nfins * (a->npf + a->nif), ntot = a->npf + a->nif;
-    if (a->qoi_obs_ptr[0] != 0) return bad("qoi_obs_ptr");
-    for (int o = 0; o < d.n_obs; ++o) if (a->qoi_obs_ptr[o + 1] < a->qoi_obs_ptr[o]) return bad("qoi_obs_ptr");
-    const int nqz = a->qoi_obs_ptr[d.n_obs];
-    if (nqz > 0 && (!a->qoi_obs_idx || !a->qoi_obs_w)) return bad("table pointer (null)");
-    for (int t = 0; t < nqz; ++t) if (a->qoi_obs_idx[t] < post_e0 || a->qoi_obs_idx[t] >= n) return bad("qoi_obs_idx (post nodes only)");
-    std::vector<int> fin_row(std::max(a->nfins, 1), -1);
-    for (int o = 0; o < d.n_obs; ++o) {
-      const int f = a->qoi_row_fin[o];
-      if (f < -1 || f >= a->nfins) return bad("qoi_row_fin");
-      if (f >= 0) { if (fin_row[f] >= 0) return bad("qoi_row_fin (a fin belongs to at most one row)"); fin_row[f] = o; }
-    }
-    for (int g = 0; g < a->npost; ++g) if (a->qoi_FgQ[post_g0 + g] != a->Fg[post_g0 + g]) return bad("qoi_FgQ (must equal Fg on the post)");
-    for (int f = 0; f < a->nfins; ++f)
-      if (fin_row[f] < 0)
-        for (int t = 0; t < ntot; ++t) if (a->qoi_FgQ[f * ntot + t] != 0.0) return bad("qoi_FgQ (weights on a fin no row owns)");
-    std::vector<double> full(n), rec(n);
-    for (int o = 0; o < d.n_obs; ++o) {
-      std::fill(full.begin(), full.end(), 0.0); std::fill(rec.begin(), rec.end(), 0.0);
-      for (int t = a->obs_ptr[o]; t < a->obs_ptr[o + 1]; ++t) full[a->obs_idx[t]] += a->obs_w[t];
-      for (int t = a->qoi_obs_ptr[o]; t < a->qoi_obs_ptr[o + 1]; ++t) rec[a->qoi_obs_idx[t]] += a->qoi_obs_w[t];
-      const int f = a->qoi_row_fin[o];
-      if (f >= 0) {
-        for (int t = 0; t < a->npf; ++t) rec[f * a->npf + t] += a->qoi_FgQ[f * ntot + t];
-        for (int t = 0; t < a->nif; ++t) rec[a->iface_elim[f * a->nif + t]] += a->qoi_FgQ[f * ntot + a->npf + t];
-      }
-      for (int i = 0; i < n; ++i) if (full[i] != rec[i]) return bad("QoI-only tables (not the operator obs_* describes)");
-    }
-  }
-  if (gsize_out) *gsize_out = gsize;
-  if (nL_out) *nL_out = nL;
-  return 0;
-}
-
-int finrom_fom_band_validate(const finrom_fom_band_desc* a, int32_t n, int32_t xdim, int32_t n_obs) {
-  return validate_band(a, n, xdim, n_obs, nullptr, nullptr);
-}
-
+}  // extern "C"
 // Device tables of a validated band descriptor for a problem of n dofs and n_obs computed observation rows (the handle's own
 // sizes for finrom_fom_set_band, the half problem's for finrom_fom_set_band_mirror): the sweep's BandDev and the parameters of
 // its assembly pre-pass.  The handle owns the uploads.
@@ -918,6 +718,7 @@ static int build_band(finrom_fom_t h, const finrom_fom_band_desc* a, int n, int 
   *b_out = b;
   return 0;
 }
+extern "C" {
 
 int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   if (!h || !a) { set_error("fom_set_band: null argument"); return FINROM_ERR_ARG; }
@@ -928,107 +729,6 @@ int finrom_fom_set_band(finrom_fom_t h, const finrom_fom_band_desc* a) {
   if (int rc = build_band(h, a, d.n, d.n_obs, gsize, nL, &b, &h->band_asm)) return rc;
   h->band = b;
   h->band_m = BandDev{}; h->band_m_fn = BandFnDev{};      // (a half plan belongs to the plan it was installed beside)
-  return 0;
-}
-
-// Host-only check of the half problem of a mirror-symmetric operator: the half descriptor like any band descriptor (for n_half dofs
-// and n_rows computed observation rows), register windows only, QoI-only tables present (the half plan serves calls without w),
-// and the map from computed rows to output columns: in range, every one of the n_obs output columns written exactly once.
-static int validate_band_mirror(const finrom_fom_band_desc* a, int n_half, int xdim, int n_rows, int n_obs, const int32_t* out_ptr,
-                                const int32_t* out_col, int64_t* gsize_out, int64_t* nL_out) {
-  if (!a || !out_ptr || !out_col || n_rows <= 0 || n_obs <= 0) { set_error("fom_set_band_mirror: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_band(a, n_half, xdim, n_rows, gsize_out, nL_out)) return rc;
-  auto bad = [&](const char* what) { set_error(std::string("fom_set_band_mirror: invalid ") + what); return FINROM_ERR_ARG; };
-  if (a->NSP > 14) { set_error("fom_set_band_mirror: only the register sweep takes a half plan"); return FINROM_ERR_UNSUPPORTED; }
-  if (!a->qoi_FgQ) return bad("descriptor (the half plan needs the QoI-only tables)");
-  if (out_ptr[0] != 0) return bad("out_ptr");
-  for (int o = 0; o < n_rows; ++o) if (out_ptr[o + 1] < out_ptr[o]) return bad("out_ptr");
-  if (out_ptr[n_rows] != n_obs) return bad("out_ptr (must end at the number of output columns)");
-  std::vector<char> written(n_obs, 0);
-  for (int c = 0; c < n_obs; ++c) {
-    const int col = out_col[c];
-    if (col < 0 || col >= n_obs) return bad("out_col (out of range)");
-    if (written[col]) return bad("out_col (an output column is written twice, another one not at all)");
-    written[col] = 1;
-  }
-  return 0;
-}
-
-// The post as functionals (fom_band.hip, DESIGN 4c'): the tables of a VALIDATED half descriptor, host only.
-//   cw [npost][BAND_NF]   row o's post-only weights (qoi_obs_*), dense; rows beyond n_rows are zero
-//   piv_row, piv_off [npost]   post pivot -> the row that owns the fin this pivot is an interface node of (-1: none) and the slot
-//                              f * nif + t in which that fin's sweep leaves its g for the node
-// -> 1: the form fits; 0: it does not -- more than BAND_NF rows, other window sizes than the half plans', a row with weights on two
-// fins, a post node that is an interface node of two fins that rows own -- and the stored-factor form serves the plan;
-// < 0: the derived tables do not describe the operator obs_* describes (an error, like any other validator finding).
-static int derive_post_functionals(const finrom_fom_band_desc* a, int n_half, int n_rows, std::vector<double>& cw, std::vector<int>& piv_row,
-                                   std::vector<int>& piv_off) {
-  auto bad = [&](const char* what) { set_error(std::string("fom_set_band_mirror: invalid ") + what); return (int)FINROM_ERR_ARG; };
-  const bool windows = a->NX <= 2 && ((a->NSF == 3 && a->NSP == 4) || (a->NSF == 4 && a->NSP == 6) || (a->NSF == 5 && a->NSP == 8));
-  if (!windows || n_rows > BAND_NF || !a->qoi_FgQ) return 0;
-  const int post_e0 = a->nfins * a->npf, ntot = a->npf + a->nif;
-  for (int o = 0; o < n_rows; ++o)                        // a row's weights on fin nodes: one fin, the one row_fin names
-    for (int t = a->obs_ptr[o]; t < a->obs_ptr[o + 1]; ++t)
-      if (a->obs_idx[t] < post_e0 && a->obs_w[t] != 0.0 && a->obs_idx[t] / a->npf != a->qoi_row_fin[o]) return 0;
-  cw.assign((size_t)a->npost * BAND_NF, 0.0);
-  piv_row.assign(a->npost, -1); piv_off.assign(a->npost, 0);
-  for (int o = 0; o < n_rows; ++o)
-    for (int t = a->qoi_obs_ptr[o]; t < a->qoi_obs_ptr[o + 1]; ++t) {
-      const int pv = a->qoi_obs_idx[t] - post_e0;
-      if (pv < 0 || pv >= a->npost) return bad("qoi_obs_idx (a weight outside the post)");
-      cw[(size_t)pv * BAND_NF + o] += a->qoi_obs_w[t];
-    }
-  for (int o = 0; o < n_rows; ++o) {
-    const int f = a->qoi_row_fin[o];
-    if (f < 0) continue;
-    for (int t = 0; t < a->nif; ++t) {
-      const int pv = a->iface_elim[f * a->nif + t] - post_e0;
-      if (pv < 0 || pv >= a->npost) return bad("iface_elim (an interface node outside the post)");
-      if (piv_row[pv] >= 0) return 0;
-      piv_row[pv] = o; piv_off[pv] = f * a->nif + t;
-    }
-  }
-  // every index the kernel dereferences, and the operator rebuilt from the tables against obs_*, entry by entry
-  for (int pv = 0; pv < a->npost; ++pv)
-    if (piv_row[pv] < -1 || piv_row[pv] >= n_rows || piv_off[pv] < 0 || piv_off[pv] >= a->nfins * a->nif) return bad("derived pivot map");
-  std::vector<double> full(n_half), rec(n_half);
-  for (int o = 0; o < n_rows; ++o) {
-    std::fill(full.begin(), full.end(), 0.0); std::fill(rec.begin(), rec.end(), 0.0);
-    for (int t = a->obs_ptr[o]; t < a->obs_ptr[o + 1]; ++t) full[a->obs_idx[t]] += a->obs_w[t];
-    for (int pv = 0; pv < a->npost; ++pv) {
-      rec[post_e0 + pv] += cw[(size_t)pv * BAND_NF + o];
-      if (piv_row[pv] == o) {                             // the g slot holds, before the fin's elimination, the row's weight on the node
-        const int f = piv_off[pv] / a->nif, t = piv_off[pv] % a->nif;
-        rec[post_e0 + pv] += a->qoi_FgQ[f * ntot + a->npf + t];
-      }
-    }
-    const int f = a->qoi_row_fin[o];
-    if (f >= 0) for (int t = 0; t < a->npf; ++t) rec[f * a->npf + t] += a->qoi_FgQ[f * ntot + t];
-    for (int i = 0; i < n_half; ++i) if (full[i] != rec[i]) return bad("derived functional tables (not the operator obs_* describes)");
-  }
-  return 1;
-}
-
-int finrom_fom_band_mirror_validate(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
-                                    const int32_t* out_ptr, const int32_t* out_col) {
-  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
-  std::vector<double> cw; std::vector<int> piv_row, piv_off;
-  const int fits = derive_post_functionals(a, n_half, n_rows, cw, piv_row, piv_off);
-  return fits < 0 ? fits : 0;
-}
-
-// Host only: the tables finrom_fom_set_band_mirror derives for the functional form of the post, for a test to walk.  *fits = 0: the
-// descriptor keeps the stored-factor form and nothing is written; cw [npost * 5], piv_row and piv_off [npost] otherwise.
-int finrom_fom_band_mirror_functionals(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
-                                       const int32_t* out_ptr, const int32_t* out_col, int32_t* fits, double* cw, int32_t* piv_row,
-                                       int32_t* piv_off) {
-  if (!fits || !cw || !piv_row || !piv_off) { set_error("fom_band_mirror_functionals: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
-  std::vector<double> c; std::vector<int> pr, po;
-  const int f = derive_post_functionals(a, n_half, n_rows, c, pr, po);
-  if (f < 0) return f;
-  *fits = f;
-  if (f) { std::copy(c.begin(), c.end(), cw); std::copy(pr.begin(), pr.end(), piv_row); std::copy(po.begin(), po.end(), piv_off); }
   return 0;
 }
 
@@ -1190,16 +890,15 @@ int finrom_fom_gradient(finrom_fom_t h, const double* x, const double* data, int
   if (!h->d.has_grad && !h->band_grad.on) { set_error("fom_gradient: finrom_fom_set_gradient has not been called"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const FomDev& d = h->d;
-  static const bool env_no_band_grad = getenv("FINROM_NO_BAND") != nullptr;
+  const bool no_band = env_no_band();
   const bool small = h->small.small_max > 0 && S <= h->small.small_max && d.n_obs <= 64 && d.has_grad;
-  if (!small && h->band.on && h->band_grad.on && !env_no_band_grad) {
+  if (!small && h->band.on && h->band_grad.on && !no_band) {
     // the full band sweep (the factor and w stay in the workspace), then the adjoint solve and the contraction on the same layout
     const BandDev& b = h->band;
     h->last_path = band_path(b, false);
     const size_t per_sample = ((size_t)b.gsize + 2 * d.xdim) * sizeof(double);
     const int64_t limit = std::max<int64_t>(64, (int64_t)((size_t)48 << 30) / (int64_t)per_sample / 64 * 64);
-    const int64_t npieces = (S + limit - 1) / limit;
-    const int64_t chunk = npieces <= 1 ? limit : ((S + npieces - 1) / npieces + 63) / 64 * 64;
+    const int64_t chunk = fom_equal_chunk(S, limit);
     for (int64_t s0 = 0; s0 < S; s0 += chunk) {
       const int64_t Sc = std::min(chunk, S - s0), nblk = (Sc + 63) / 64;
       int rc;
@@ -1251,377 +950,13 @@ int finrom_fom_gradient(finrom_fom_t h, const double* x, const double* data, int
   return 0;
 }
 
+}  // extern "C"
+
+extern "C" {
+
 // ---------------------------------------------------------------------------------------
 // ROM
 // ---------------------------------------------------------------------------------------
-namespace {
-int validate_rom_desc(const finrom_rom_desc* a) {
-  if (a->n <= 0 || a->r <= 0 || a->P < 0 || a->P > 31 || a->n_obs < 0 || a->nterms < 0) { set_error("rom_create: inconsistent sizes"); return FINROM_ERR_ARG; }
-  if (!a->row_ptr || (a->nterms > 0 && (!a->term_p || !a->term_val))) { set_error("rom_create: null table"); return FINROM_ERR_ARG; }
-  if (a->row_ptr[0] != 0 || a->row_ptr[a->n] != a->nterms) { set_error("rom_create: invalid row_ptr"); return FINROM_ERR_ARG; }
-  for (int i = 0; i < a->n; ++i) if (a->row_ptr[i + 1] < a->row_ptr[i]) { set_error("rom_create: invalid row_ptr"); return FINROM_ERR_ARG; }
-  for (int t = 0; t < a->nterms; ++t) if (a->term_p[t] < 0 || a->term_p[t] > a->P) { set_error("rom_create: invalid term_p"); return FINROM_ERR_ARG; }
-  // a row lists each theta index at most once: the pattern-uniform k-step tables below fill a slot with the SUM of the row's
-  // terms that carry the slot's index, so a repeated index would be counted once per repetition
-  for (int i = 0; i < a->n; ++i) {
-    unsigned seen = 0;
-    for (int t = a->row_ptr[i]; t < a->row_ptr[i + 1]; ++t) {
-      if (seen & (1u << a->term_p[t])) { set_error("rom_create: a row of psi lists the same theta index twice (merge the terms)"); return FINROM_ERR_ARG; }
-      seen |= 1u << a->term_p[t];
-    }
-  }
-  return 0;
-}
-
-// rows with a term, sorted by term count (descending)
-std::vector<int> rows_by_term_count(const finrom_rom_desc* a) {
-  auto cnt = [&](int row) { return a->row_ptr[row + 1] - a->row_ptr[row]; };
-  std::vector<int> order;
-  for (int i = 0; i < a->n; ++i) if (cnt(i) > 0) order.push_back(i);
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cnt(x) > cnt(y); });
-  return order;
-}
-
-// pattern-uniform k-steps (RomDev::tvu): four rows that share ONE list of theta indices; sorted by term count, descending
-struct KStep { std::vector<int> pat; int rows[4]; };
-// How the rows that do not fill a k-step of their own pattern are packed.  PACK_CONSECUTIVE: rows that follow each other in pattern
-// order share a k-step while the union of their patterns has at most kMaxTerms entries -- every list but the short half list.
-// PACK_FEWEST (the half list with dropped rows, finrom_rom_set_mirror, DESIGN 4b''): the leftovers are a tenth to a third of such a
-// list, so of three packings -- consecutive, nested (below), padded (every remainder alone in a k-step of its own pattern) -- the
-// one with the fewest k-steps wins, among equals the one with the fewest k-steps that need vector arithmetic in the grouped loop,
-// then the one with the fewest multiply-adds, then the earlier in this order.
-enum { PACK_CONSECUTIVE = 0, PACK_FEWEST = 1 };
-constexpr int kMaxTerms = 4;      // terms per row of a k-step (rom_proj_device.h: the loops' slot count)
-// multiplies / multiply-adds per block that proj_main_grouped's `finish` spends on a k-step of this pattern (build_grouped_tables)
-// (group0: the k-step sits in segment 0 with its usual coefficients -- a lone theta_d then multiplies its rows)
-int kstep_vector_ops(const std::vector<int>& pat, bool group0 = false) {
-  const int nt = (int)pat.size();
-  if (nt == 1) return group0 && pat[0] != 0 ? 1 : 0;                             // T_d or T_0 as loaded
-  if (nt == 2 && (pat[0] == 0) != (pat[1] == 0)) return 1;                       // group d: T_d + (1 / theta_d) T_0
-  return nt - (std::find(pat.begin(), pat.end(), 0) == pat.begin() ? 1 : 0);     // group 0: the first coefficient is 1 only for T_0
-}
-// When a leading parameter is worth a group (build_grouped_tables, scale_free).  The grouped form pays for itself on the k-steps
-// whose pattern is {theta_d} ALONE: divided by theta_d their rows are the slab as loaded, NB multiplies saved each.  A k-step
-// {1, theta_d} costs NB multiply-adds either way, T_d + (1 / theta_d) T_0 in the group or theta_d T_d + T_0 at scale 1.  Every group
-// costs a rescale of the accumulators, 4 multiplies on each of the NB (NB + 1) / 2 tiles behind a drain of the matrix pipe (five
-// s_nop 15 and a fence: about as long as kRescaleDrainOps multiplies).  So d becomes a group only if
-//   NB x (its {theta_d}-alone k-steps)  >  2 NB (NB + 1) + kRescaleDrainOps;
-// otherwise its k-steps go to segment 0 with their usual coefficients.  The rule is applied per weight class (a group is a run
-// of one class) and only to a descriptor with term-less rows, the short half list (the trigger of PACK_FEWEST): that list has lost
-// the interior rows that carry {theta_d} alone.  Every other list is built as it always was.
-constexpr int kRescaleDrainOps = 20;
-bool group_pays(int alone_ksteps, int NB) { return alone_ksteps * NB > 2 * NB * (NB + 1) + kRescaleDrainOps; }
-struct PackCost {
-  int ksteps = 0, fma_ksteps = 0, fma = 0;
-  bool operator<(const PackCost& o) const { return ksteps != o.ksteps ? ksteps < o.ksteps : fma_ksteps != o.fma_ksteps ? fma_ksteps < o.fma_ksteps : fma < o.fma; }
-};
-PackCost pack_cost(const std::vector<KStep>& ks) {
-  PackCost c;
-  for (const KStep& k : ks) { const int ops = kstep_vector_ops(k.pat); ++c.ksteps; c.fma_ksteps += ops > 0; c.fma += ops; }
-  return c;
-}
-typedef std::vector<std::pair<std::vector<int>, std::vector<int>>> LeftClasses;      // (pattern, its 1..3 left-over rows)
-std::vector<KStep> pack_consecutive(const LeftClasses& cls) {
-  std::vector<KStep> out;
-  KStep cur{{}, {-1, -1, -1, -1}};
-  int fill = 0;
-  auto flush = [&]() { if (fill) out.push_back(cur); cur = KStep{{}, {-1, -1, -1, -1}}; fill = 0; };
-  for (const auto& c : cls)
-    for (int row : c.second) {
-      std::vector<int> u = cur.pat;
-      for (int pp : c.first) if (std::find(u.begin(), u.end(), pp) == u.end()) u.push_back(pp);
-      if (fill == 4 || (int)u.size() > kMaxTerms) { flush(); u = c.first; }
-      cur.pat = u; cur.rows[fill++] = row;
-    }
-  flush();
-  return out;
-}
-std::vector<KStep> pack_padded(const LeftClasses& cls) {
-  std::vector<KStep> out;
-  for (const auto& c : cls) {
-    KStep k{c.first, {-1, -1, -1, -1}};
-    for (size_t i = 0; i < c.second.size() && i < 4; ++i) k.rows[i] = c.second[i];
-    out.push_back(k);
-  }
-  return out;
-}
-// nested: the classes with the longest patterns open k-steps; a class joins the k-step with room whose pattern CONTAINS its own
-// (the shortest such pattern, then the tightest room) -- the k-step then costs what it cost before, the guest's missing terms are
-// zero rows -- and is split over several if need be; what stays partly filled is then merged pairwise, smallest union first,
-// while the union has at most kMaxTerms entries and the rows fit.
-std::vector<KStep> pack_nested(const LeftClasses& cls_in) {
-  struct Bin { std::vector<int> pat, rows; };
-  LeftClasses cls(cls_in);
-  for (auto& c : cls) std::sort(c.first.begin(), c.first.end());
-  std::stable_sort(cls.begin(), cls.end(), [](const auto& x, const auto& y) { return x.first.size() > y.first.size(); });
-  std::vector<Bin> bins;
-  for (const auto& c : cls) {
-    size_t next = 0;
-    while (next < c.second.size()) {
-      const int pending = (int)(c.second.size() - next);
-      int best = -1;
-      for (int b = 0; b < (int)bins.size(); ++b) {
-        const int room = 4 - (int)bins[b].rows.size();
-        if (room <= 0 || !std::includes(bins[b].pat.begin(), bins[b].pat.end(), c.first.begin(), c.first.end())) continue;
-        if (best < 0) { best = b; continue; }
-        const int broom = 4 - (int)bins[best].rows.size();
-        if (bins[b].pat.size() != bins[best].pat.size()) { if (bins[b].pat.size() < bins[best].pat.size()) best = b; continue; }
-        const bool fits = room >= pending, bfits = broom >= pending;
-        if (fits != bfits ? fits : (fits ? room < broom : room > broom)) best = b;
-      }
-      if (best < 0) { bins.push_back({c.first, {}}); best = (int)bins.size() - 1; }
-      while (next < c.second.size() && bins[best].rows.size() < 4) bins[best].rows.push_back(c.second[next++]);
-    }
-  }
-  for (;;) {
-    int bi = -1, bj = -1; size_t bu = 0;
-    for (int i = 0; i < (int)bins.size(); ++i)
-      for (int j = i + 1; j < (int)bins.size(); ++j) {
-        if (bins[i].rows.size() + bins[j].rows.size() > 4) continue;
-        std::vector<int> u;
-        std::set_union(bins[i].pat.begin(), bins[i].pat.end(), bins[j].pat.begin(), bins[j].pat.end(), std::back_inserter(u));
-        if ((int)u.size() > kMaxTerms) continue;
-        if (bi < 0 || u.size() < bu) { bi = i; bj = j; bu = u.size(); }
-      }
-    if (bi < 0) break;
-    std::vector<int> u;
-    std::set_union(bins[bi].pat.begin(), bins[bi].pat.end(), bins[bj].pat.begin(), bins[bj].pat.end(), std::back_inserter(u));
-    bins[bi].pat = u;
-    bins[bi].rows.insert(bins[bi].rows.end(), bins[bj].rows.begin(), bins[bj].rows.end());
-    bins.erase(bins.begin() + bj);
-  }
-  std::vector<KStep> out;
-  for (const Bin& b : bins) {
-    KStep k{b.pat, {-1, -1, -1, -1}};
-    for (size_t i = 0; i < b.rows.size(); ++i) k.rows[i] = b.rows[i];
-    out.push_back(k);
-  }
-  return out;
-}
-std::vector<KStep> uniform_ksteps(const finrom_rom_desc* a, const std::vector<int>& order, int rule = PACK_CONSECUTIVE) {
-  std::vector<KStep> ksteps;
-  auto pattern = [&](int row) { return std::vector<int>(a->term_p + a->row_ptr[row], a->term_p + a->row_ptr[row + 1]); };
-  std::vector<int> byp(order);
-  std::stable_sort(byp.begin(), byp.end(), [&](int x, int y) { return pattern(x) < pattern(y); });
-  LeftClasses left;
-  for (size_t i0 = 0; i0 < byp.size();) {
-    size_t i1 = i0;
-    while (i1 < byp.size() && pattern(byp[i1]) == pattern(byp[i0])) ++i1;
-    size_t i = i0;
-    for (; i + 4 <= i1; i += 4) ksteps.push_back({pattern(byp[i]), {byp[i], byp[i + 1], byp[i + 2], byp[i + 3]}});
-    if (i < i1) left.push_back({pattern(byp[i]), std::vector<int>(byp.begin() + i, byp.begin() + i1)});
-    i0 = i1;
-  }
-  std::vector<KStep> packed = pack_consecutive(left);
-  if (rule == PACK_FEWEST) {
-    for (const std::vector<KStep>& cand : {pack_nested(left), pack_padded(left)})
-      if (pack_cost(cand) < pack_cost(packed)) packed = cand;
-  }
-  ksteps.insert(ksteps.end(), packed.begin(), packed.end());
-  std::stable_sort(ksteps.begin(), ksteps.end(), [](const KStep& x, const KStep& y) { return x.pat.size() > y.pat.size(); });
-  return ksteps;
-}
-
-// ---- the same k-steps GROUPED by their leading parameter (proj_main_grouped, NB <= 5) ----------------------------------
-// A k-step whose rows carry {theta_d} or {1, theta_d} belongs to group d and is accumulated DIVIDED by theta_d: its slab is
-// T_d (no arithmetic at all) or T_d + (1/theta_d) T_0 (one multiply-add per block); the accumulators are rescaled where the
-// group changes -- by (theta_d / theta_e)^2 between groups d and e, by theta_d^2 after the last -- so that the sum is the
-// one the ungrouped loop forms, up to rounding.  Everything else (rows that touch two parameters, merged leftovers) comes
-// first, at scale 1, with the usual coefficients.  The per-sample scalars (1, theta, 1 / theta, the rescale factors) are
-// one row of RomDev::ext, filled by rom_ext_kernel ahead of the projection kernel; the records name them by index.
-struct GroupedTables { std::vector<double> tvg; std::vector<int> kmg, def; int nkg = 0, n_ext = 0, ext_final = 0, live = 0, fma_ksteps = 0; };
-// kclass (the half list of a mirror-symmetric ROM, DESIGN 4b'): per k-step 0 = rows that count twice (left of the symmetry line),
-// 1 = rows that count once (on it).  The k-steps that count twice all come first; the factor of the record that opens the first
-// k-step that counts once -- or the final factor if there is none -- carries an exact 2 (bit 1 of its ext_def flags), so the
-// weights act on the accumulators and no row is scaled by sqrt(2).  slot0 / ext0: the list's rows and factors sit behind
-// another list's (slot0 table slots, ext0 scalars, of which the first 1 + 2 P are shared); `def` then holds the factors only.
-// scale_free (the short half list, group_pays above): a leading parameter whose group would not pay for its rescale stays at scale 1;
-// what is left of the factors is the exact 2 where the weight class changes and the final one.
-bool build_grouped_tables(const finrom_rom_desc* a, const std::vector<KStep>& ksteps, int rp, GroupedTables& out,
-                          const std::vector<int>* kclass = nullptr, int slot0 = 0, int ext0 = 0, bool scale_free = false) {
-  const int r = a->r;
-  struct GStep { int cls, group; std::vector<int> pat; const int* rows; };
-  std::vector<GStep> gs;
-  for (size_t k = 0; k < ksteps.size(); ++k) {
-    const KStep& ks = ksteps[k];
-    if (ks.rows[0] < 0 && ks.rows[1] < 0 && ks.rows[2] < 0 && ks.rows[3] < 0) continue;      // (padding k-steps of the ungrouped list)
-    int group = 0;
-    std::vector<int> pat = ks.pat;
-    if (pat.size() == 1 && pat[0] != 0) group = pat[0];
-    else if (pat.size() == 2 && (pat[0] == 0) != (pat[1] == 0)) { group = pat[0] ? pat[0] : pat[1]; pat = {group, 0}; }
-    gs.push_back({kclass ? (*kclass)[k] : 0, group, pat, ks.rows});
-  }
-  if (scale_free) {
-    std::map<std::pair<int, int>, int> alone;      // (class, group) -> k-steps with the pattern {theta_group} alone
-    for (const GStep& g : gs) if (g.group != 0 && g.pat.size() == 1) ++alone[{g.cls, g.group}];
-    for (GStep& g : gs) {
-      if (g.group == 0) continue;
-      const auto it = alone.find({g.cls, g.group});
-      if (group_pays(it == alone.end() ? 0 : it->second, rp / 16)) continue;
-      if (g.pat.size() == 2) g.pat = {0, g.group};      // (T_0 first: `finish` then does fma(theta_d, T_d, T_0), NB operations)
-      g.group = 0;
-    }
-  }
-  std::stable_sort(gs.begin(), gs.end(), [](const GStep& x, const GStep& y) { return x.cls != y.cls ? x.cls < y.cls : x.group < y.group; });
-  // segments: runs of one (class, group); segment 0 is the scale-1 start (group 0 of the first class, possibly empty)
-  struct Seg { int cls, group; };
-  std::vector<Seg> segs;
-  bool any_group = false;
-  if (!gs.empty()) segs.push_back({gs[0].cls, 0});
-  for (const GStep& g : gs) {
-    if (g.cls != segs.back().cls || g.group != segs.back().group) segs.push_back({g.cls, g.group});
-    any_group = any_group || g.group != 0;
-  }
-  const int P = a->P, nfac = (int)segs.size(), base = ext0 ? ext0 : 1 + 2 * P, n_ext = base + nfac;
-  if ((!any_group && !scale_free) || n_ext > 64) return false;      // (a scale-free list may have no group at all)
-  // ext[0] = 1, ext[p] = theta_p, ext[P + p] = 1 / theta_p, then one factor per change of segment and the final one; as
-  // (numerator, denominator, flags: 1 squared, 2 times two)
-  std::vector<int> def(ext0 ? 0 : 3 * (size_t)base, 0);
-  if (!ext0) for (int pp = 1; pp <= P; ++pp) { def[3 * pp] = pp; def[3 * (P + pp) + 1] = pp; }
-  for (int g = 0; g < nfac; ++g) {      // factor g: from segment g to segment g + 1, the last one back to scale 1
-    const bool last = g + 1 == nfac;
-    const bool twice = kclass != nullptr && segs[g].cls == 0 && (last || segs[g + 1].cls == 1);
-    def.push_back(segs[g].group); def.push_back(last ? 0 : segs[g + 1].group); def.push_back(1 | (twice ? 2 : 0));
-  }
-  std::vector<double>& tvg = out.tvg; std::vector<int>& kmg = out.kmg;
-  tvg.clear(); kmg.clear();
-  int slot = slot0, seg = 0;
-  bool first = true;
-  for (const GStep& g : gs) {
-    const int nt = (int)g.pat.size();
-    int rec[8] = {slot, nt, 0, 0, 0, 0, 0, 0};
-    for (int t = 0; t < nt; ++t) rec[4 + t] = g.group ? (t == 0 ? 0 : P + g.group) : g.pat[t];
-    if (rec[4] == 0) rec[2] |= 1;                       // the first coefficient is 1: its rows are the slab as they are
-    if (g.cls != segs[seg].cls || g.group != segs[seg].group) {
-      ++seg;
-      if (!first) { rec[2] |= 2; rec[3] = base + seg - 1; }      // (nothing to rescale in front of the very first k-step)
-    }
-    first = false;
-    kmg.insert(kmg.end(), rec, rec + 8);
-    for (int t = 0; t < nt; ++t)
-      for (int q = 0; q < 4; ++q) {
-        const size_t base_ = tvg.size();
-        tvg.resize(base_ + rp, 0.0);
-        const int row = g.rows[q];
-        if (row < 0) continue;
-        for (int tt = a->row_ptr[row]; tt < a->row_ptr[row + 1]; ++tt)
-          if (a->term_p[tt] == g.pat[t]) for (int col = 0; col < r; ++col) tvg[base_ + col] += a->term_val[(size_t)tt * r + col];
-      }
-    slot += nt;
-  }
-  // zero k-steps fill the list up to a multiple of three (the loop rotates three slab buffers) and serve the pipeline's reads
-  // of the records / rows of the k-steps behind the last one
-  int nkg = (int)gs.size();
-  const int zslot = slot;
-  tvg.resize(tvg.size() + (size_t)4 * 4 * rp, 0.0);
-  while (nkg % 3) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); ++nkg; }
-  for (int k = 0; k < 8; ++k) { int rec[8] = {zslot, 1, 1, 0, 0, 0, 0, 0}; kmg.insert(kmg.end(), rec, rec + 8); }
-  out.def = def; out.nkg = nkg; out.n_ext = n_ext; out.ext_final = base + nfac - 1;
-  out.live = (int)gs.size(); out.fma_ksteps = 0;
-  for (const GStep& g : gs) out.fma_ksteps += kstep_vector_ops(g.pat, g.group == 0) > 0;
-  return true;
-}
-
-// ---- the half descriptor of a mirror-symmetric ROM (finrom_rom_set_mirror) -------------------------------------------------
-int validate_rom_mirror(const finrom_rom_desc* a, int n_full, const int32_t* row_node, const double* row_weight, const int32_t* theta_twin) {
-  if (!a || !row_node || !row_weight || !theta_twin) { set_error("rom_mirror: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_rom_desc(a)) return rc;
-  if (a->n > n_full) { set_error("rom_mirror: more half rows than rows"); return FINROM_ERR_ARG; }
-  for (int p = 0; p < a->P; ++p)
-    if (theta_twin[p] < 0 || theta_twin[p] >= a->P || theta_twin[theta_twin[p]] != p) { set_error("rom_mirror: theta_twin is not an involution"); return FINROM_ERR_ARG; }
-  std::vector<char> seen((size_t)n_full, 0);
-  int64_t covered = 0;
-  for (int i = 0; i < a->n; ++i) {
-    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
-    if (row_node[i] < 0 || row_node[i] >= n_full) { set_error("rom_mirror: row_node out of range"); return FINROM_ERR_ARG; }
-    if (seen[row_node[i]]) { set_error("rom_mirror: a row is listed twice"); return FINROM_ERR_ARG; }
-    seen[row_node[i]] = 1;
-    covered += row_weight[i] == 2.0 ? 2 : 1;
-  }
-  if (covered != n_full) { set_error("rom_mirror: the weights do not add up to the number of rows"); return FINROM_ERR_ARG; }
-  // only one parameter of a mirror pair may appear (the samples that walk this list carry the same value in both)
-  unsigned used = 0;
-  for (int t = 0; t < a->nterms; ++t) if (a->term_p[t] > 0) used |= 1u << (a->term_p[t] - 1);
-  for (int p = 0; p < a->P; ++p)
-    if (theta_twin[p] != p && (used & (1u << p)) && (used & (1u << theta_twin[p]))) { set_error("rom_mirror: both parameters of a mirror pair appear"); return FINROM_ERR_ARG; }
-  return 0;
-}
-
-// the half list's k-steps: rows that count twice and rows that count once never share a k-step.  A descriptor with rows that have no
-// terms is the SHORT list (engine.py: mirror_skip_rows dropped them): its leftovers are packed for the fewest k-steps (PACK_FEWEST);
-// a descriptor without such rows keeps the list it always had.
-std::vector<KStep> mirror_ksteps(const finrom_rom_desc* a, const double* row_weight, std::vector<int>& kclass) {
-  std::vector<KStep> ksteps;
-  kclass.clear();
-  const std::vector<int> order = rows_by_term_count(a);
-  const int rule = (int)order.size() < a->n ? PACK_FEWEST : PACK_CONSECUTIVE;
-  for (int cls = 0; cls < 2; ++cls) {
-    std::vector<int> part;
-    for (int row : order) if ((row_weight[row] == 2.0) == (cls == 0)) part.push_back(row);
-    for (const KStep& ks : uniform_ksteps(a, part, rule)) { ksteps.push_back(ks); kclass.push_back(cls); }
-  }
-  return ksteps;
-}
-// the short half list (a descriptor with term-less rows) is built scale-free unless the A/B switch asks for the groups it had
-bool short_scale_free(const finrom_rom_desc* a, bool short_grouped) { return !short_grouped && (int)rows_by_term_count(a).size() < a->n; }
-}  // namespace
-
-// Host only (no device needed): the grouped tables finrom_rom_create builds for r <= 80, for tests of the host logic.
-int finrom_rom_grouped_tables(const finrom_rom_desc* a, int32_t* nkg, int32_t* n_ext, int32_t* ext_final, int64_t* n_slots,
-                              int32_t* kmg, double* tvg, int32_t* ext_def) {
-  if (!a || !nkg || !n_ext || !ext_final || !n_slots) { set_error("rom_grouped_tables: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_rom_desc(a)) return rc;
-  const int NB = (a->r + 15) / 16, rp = 16 * NB;
-  GroupedTables g;
-  if (NB > 5 || !build_grouped_tables(a, uniform_ksteps(a, rows_by_term_count(a)), rp, g)) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
-  *nkg = g.nkg; *n_ext = g.n_ext; *ext_final = g.ext_final; *n_slots = (int64_t)(g.tvg.size() / ((size_t)4 * rp));
-  if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
-  if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
-  if (ext_def) std::memcpy(ext_def, g.def.data(), g.def.size() * sizeof(int));
-  return 0;
-}
-
-int finrom_rom_mirror_validate(const finrom_rom_desc* a, int32_t n_full, const int32_t* row_node, const double* row_weight,
-                               const int32_t* theta_twin) {
-  return validate_rom_mirror(a, n_full, row_node, row_weight, theta_twin);
-}
-
-// Host only: the half list finrom_rom_set_mirror builds from the half descriptor, as a list of its own (slots and scalars from 0).
-int finrom_rom_mirror_tables(const finrom_rom_desc* a, const double* row_weight, int32_t* nkg, int32_t* n_ext, int32_t* ext_final,
-                             int64_t* n_slots, int32_t* kmg, double* tvg, int32_t* ext_def) {
-  if (!a || !row_weight || !nkg || !n_ext || !ext_final || !n_slots) { set_error("rom_mirror_tables: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_rom_desc(a)) return rc;
-  for (int i = 0; i < a->n; ++i)
-    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
-  const int NB = (a->r + 15) / 16, rp = 16 * NB;
-  GroupedTables g;
-  std::vector<int> kclass;
-  const std::vector<KStep> ksteps = mirror_ksteps(a, row_weight, kclass);
-  if (NB > 5 || !build_grouped_tables(a, ksteps, rp, g, &kclass, 0, 0, short_scale_free(a, getenv("FINROM_ROM_SHORT_GROUPED") != nullptr))) { *nkg = 0; *n_ext = 0; *ext_final = 0; *n_slots = 0; return 0; }
-  *nkg = g.nkg; *n_ext = g.n_ext; *ext_final = g.ext_final; *n_slots = (int64_t)(g.tvg.size() / ((size_t)4 * rp));
-  if (kmg) std::memcpy(kmg, g.kmg.data(), g.kmg.size() * sizeof(int));
-  if (tvg) std::memcpy(tvg, g.tvg.data(), g.tvg.size() * sizeof(double));
-  if (ext_def) std::memcpy(ext_def, g.def.data(), g.def.size() * sizeof(int));
-  return 0;
-}
-
-// Host only: what the half list of this descriptor multiplies -- rows with terms, k-steps before the padding to a multiple of three,
-// and how many of those need vector arithmetic (0, 0, 0 where finrom_rom_mirror_tables reports no grouped form).
-int finrom_rom_mirror_counts(const finrom_rom_desc* a, const double* row_weight, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps) {
-  if (!a || !row_weight || !live_rows || !ksteps || !fma_ksteps) { set_error("rom_mirror_counts: null argument"); return FINROM_ERR_ARG; }
-  if (int rc = validate_rom_desc(a)) return rc;
-  for (int i = 0; i < a->n; ++i)
-    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
-  const int NB = (a->r + 15) / 16, rp = 16 * NB;
-  GroupedTables g;
-  std::vector<int> kclass;
-  const std::vector<KStep> ks = mirror_ksteps(a, row_weight, kclass);
-  *live_rows = 0; *ksteps = 0; *fma_ksteps = 0;
-  if (NB > 5 || !build_grouped_tables(a, ks, rp, g, &kclass, 0, 0, short_scale_free(a, getenv("FINROM_ROM_SHORT_GROUPED") != nullptr))) return 0;
-  *live_rows = (int32_t)rows_by_term_count(a).size(); *ksteps = g.live; *fma_ksteps = g.fma_ksteps;
-  return 0;
-}
-
 int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
   if (!a || !out) { set_error("rom_create: null argument"); return FINROM_ERR_ARG; }
   *out = nullptr;
@@ -1754,6 +1089,7 @@ int finrom_rom_create(const finrom_rom_desc* a, finrom_rom_t* out) {
   return 0;
 }
 
+}  // extern "C"
 // a half list (finrom_rom_set_mirror / _short) appended behind the handle's grouped tables: records, rows and factors go behind
 // what is there, everything is uploaded again; nd gets the new arrays and n_ext, kmg0 = where the list's records start
 struct HostTables { std::vector<double> tvg; std::vector<int> kmg, def; };
@@ -1776,6 +1112,7 @@ static int append_half_list(finrom_rom_t h, const finrom_rom_desc* a, const doub
   next.tvg.swap(tvg); next.kmg.swap(kmg); next.def.swap(def);      // (the caller commits them with nd once nothing can fail any more)
   return 0;
 }
+extern "C" {
 
 int finrom_rom_set_mirror(finrom_rom_t h, const finrom_rom_desc* a, const int32_t* row_node, const double* row_weight,
                           const int32_t* theta_twin) {
@@ -1808,8 +1145,7 @@ int finrom_rom_set_mirror_short(finrom_rom_t h, const finrom_rom_desc* a, const 
   if (int rc = validate_rom_desc(a)) return rc;
   if (a->r != d.r || a->P != d.P || a->n != h->mirror_n) { set_error("rom_set_mirror_short: sizes differ from the half descriptor's"); return FINROM_ERR_ARG; }
   if (!(theta_lo > 0.0 && theta_lo <= theta_hi)) { set_error("rom_set_mirror_short: need 0 < theta_lo <= theta_hi"); return FINROM_ERR_ARG; }
-  for (int i = 0; i < a->n; ++i)
-    if (row_weight[i] != 1.0 && row_weight[i] != 2.0) { set_error("rom_mirror: a row weight is neither 1 nor 2"); return FINROM_ERR_ARG; }
+  if (int rc = validate_row_weights(a, row_weight)) return rc;
   GroupedTables g;
   int kmg0 = 0;
   RomDev nd = d;
@@ -1905,6 +1241,7 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
   return 0;
 }
 
+}  // extern "C"
 // A_r, B_r (or, with factor > 0, the factor / the solution) by the form of the reduced operator the handle is set to
 // (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
@@ -1978,6 +1315,7 @@ static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double
   }
   return 0;
 }
+extern "C" {
 
 int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
                      double* B_r, int32_t* info, void* stream) {
@@ -2086,6 +1424,7 @@ int finrom_subfin_avg(const double* Sop, int32_t P, int32_t n, const double* k, 
   return launch_subfin_avg(Sop, P, n, k, S, theta, (hipStream_t)stream);
 }
 
+}  // extern "C"
 // FINROM_TRACE=<prefix>: every finrom_solve_pairs call records, per workgroup of the FOM interpreter and of the
 // projection kernel, {start, end, HW_ID, XCC_ID} and rewrites <prefix>.fom.bin / <prefix>.proj.bin (int64 x 6 per
 // workgroup) after a device synchronisation.  Diagnostic for the co-residency of the two halves.
@@ -2100,6 +1439,7 @@ static int trace_dump(const char* kind, long long* dbuf, size_t nwg) {
   if (FILE* f = fopen(path.c_str(), "wb")) { fwrite(h.data(), sizeof(long long), h.size(), f); fclose(f); }
   return 0;
 }
+extern "C" {
 
 int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, const double* x, int64_t S,
                        double* qoi, double* qoi_r, double* err, double* w, double* w_r, double* theta,
@@ -2124,7 +1464,7 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // per workgroup: the two kernels cannot share a CU, side by side they take turns CU by CU at the dispatcher's discretion.  That
   // still beats running them in turn by 1-5 % (r = 200: 68.6 against 72.0 ms per 20k samples, 420 against 425 ms per 125k), so
   // those sizes fork too; their event-timed kernel durations then include waiting for CUs -- FINROM_NO_OVERLAP=1 gives clean ones.)
-  const bool overlap = g_overlap && !env_no_overlap;
+  const bool overlap = overlap_enabled() && !env_no_overlap;
   hipStream_t side = overlap ? rom->side : st;
   const bool tracing = trace_prefix() != nullptr;
   if (tracing) {
@@ -2155,7 +1495,7 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // multi-wave projection kernels (r = 120: 49.7 -> 56.7 ms, their workgroups leave the confined sweep too few slots), the four-wave
   // sweep (LDS-exclusive: no change) or the offline/online form (FOM-bound: 9.1 -> 14.3).  FINROM_FOM_CUS=<n> forces n CUs (0: off).
   static const int env_fom_cus = getenv("FINROM_FOM_CUS") != nullptr ? atoi(getenv("FINROM_FOM_CUS")) : -1;
-  static const bool env_no_band2 = getenv("FINROM_NO_BAND") != nullptr;
+  const bool no_band = env_no_band();
   int fom_cus = env_fom_cus;
   // The half plan of a mirror-symmetric operator (finrom_fom_set_band_mirror: a 154-register wave, 60 KB per sample, 1.3 ms alone)
   // is confined to ONE CU of every shader engine: it then lives 6.1 ms on 32 CUs instead of 3.1 ms on 96, still a third of the
@@ -2163,7 +1503,7 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // three 19.32 (the full plan with three: 20.11-20.15).
   const bool half_plan = &fband == &fom->band_m;
   if (fom_cus < 0)
-    fom_cus = (rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !env_no_band2 &&
+    fom_cus = (rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !no_band &&
                w == nullptr && S >= 16384) ? (half_plan ? -1 : -3) : 0;
   hipStream_t fst = st;
   if (overlap && fom_cus != 0) {
@@ -2226,6 +1566,10 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   return 0;
 }
 
+}  // extern "C"
+
+extern "C" {
+
 int finrom_sampler_create(const double* U, int32_t n, finrom_sampler_t* out) {
   if (!U || n <= 0 || !out) { set_error("sampler_create: bad argument"); return FINROM_ERR_ARG; }
   // the kernel only visits the K-range of an UPPER factor (scipy.linalg.cholesky's default, gaussian_field.py:30): a lower
@@ -2265,6 +1609,7 @@ int finrom_sampler_draw_seeded(finrom_sampler_t h, uint64_t seed, int64_t first_
   return 0;
 }
 
+}  // extern "C"
 // the two triangular products' workspace on the handle (field_prior.hip): grown outside a capture only (Scratch::reserve refuses
 // it inside one, with a message); the arrival counters are zeroed once, the kernels leave them zero
 static int field_prior_ws(finrom_sampler_t h, int64_t S) {
@@ -2273,6 +1618,7 @@ static int field_prior_ws(finrom_sampler_t h, int64_t S) {
   if (fresh) FR_HIP(hipMemset(h->ftick.p, 0, field_prior_tick_bytes(h->n)));
   return h->fpart.reserve(field_prior_part_bytes(h->n, S));
 }
+extern "C" {
 int finrom_sampler_field(finrom_sampler_t h, const double* mean, const double* v, int64_t S, double* k, void* stream) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!v || !k))) { set_error("sampler_field: bad argument (null handle, v or k, or S < 0)"); return FINROM_ERR_ARG; }
@@ -2335,6 +1681,7 @@ int32_t finrom_mlp_stage_reach(int32_t n_layers, int32_t n_w, int32_t n_out, int
   return mlp_stage_reach(n_layers, n_w, n_out);
 }
 int32_t finrom_mlp_forward_max_in(void) { return MLP_FORWARD_MAX_IN; }
+}  // extern "C"
 // clears the caller's info for the forms of romml_grad_impl whose kernels only ever flag in (a kernel node, not a memset node: below)
 __global__ __launch_bounds__(256) static void clear_info_kernel(int32_t* __restrict__ info, int64_t S) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2413,6 +1760,7 @@ static int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop
                              gparts, gparts ? ROM_GRAD_SMALL_NG : 0, bf.on && gparts ? (const float*)mlp->g0.p : nullptr,
                              hs != nullptr ? &hs->tail : nullptr);
 }
+extern "C" {
 
 int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,
                       int32_t data_per_sample, int64_t S, double* grad, double* loss, double* qoi_r, double* e_nn,
@@ -2421,6 +1769,7 @@ int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, con
   return romml_grad_impl(rom, mlp, Sop, k, data, data_per_sample, S, grad, loss, qoi_r, e_nn, info, stream, nullptr);
 }
 
+}  // extern "C"
 static int hmc_dev(const finrom_hmc_state* a, HmcDev* h, const char* who) {
   if (!a || a->C < 0 || a->n <= 0 || !a->mean || !a->K || !a->U || !a->dU || !a->Kq[0] || !a->Kq[1] || !a->P || !a->dUq || !a->H0 ||
       !a->P_block || !a->lu_block || !a->jt || !a->pt || !a->accept || !a->loss || !a->info) {
@@ -2432,6 +1781,7 @@ static int hmc_dev(const finrom_hmc_state* a, HmcDev* h, const char* who) {
   h->accept = (long long*)a->accept; h->trace = a->trace; h->loss = a->loss; h->info = a->info;
   return 0;
 }
+extern "C" {
 int finrom_hmc_begin(const finrom_hmc_state* a, void* stream) {
   CallGuard cg((hipStream_t)stream);
   HmcDev h;
@@ -2480,7 +1830,7 @@ int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, c
   CallGuard cg((hipStream_t)stream);
   HmcDev h;
   if (int rc = hmc_dev(a, &h, "hmc_leapfrog")) return rc;
-  if (!mlp || a->n != mlp->d.n_in || step < 0) { set_error("hmc_leapfrog: bad argument"); return FINROM_ERR_ARG; }
+  if (!rom || !mlp || a->n != mlp->d.n_in || step < 0) { set_error("hmc_leapfrog: bad argument"); return FINROM_ERR_ARG; }
   if (a->c_pri == 0.0) { set_error("hmc_leapfrog: c_pri = 0"); return FINROM_ERR_ARG; }
   HmcStep hs;
   hs.mom = a->P; hs.eps = a->eps; hs.k_out = a->Kq[(step + 1) & 1];
@@ -2499,6 +1849,7 @@ int finrom_hmc_leapfrog(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, c
   return rc;
 }
 
+}  // extern "C"
 // the leapfrog step in whitened coordinates: field kernel (position update in front), the plain romml value and gradient at the
 // field, pullback kernel (momentum update behind); no theta carry (the field is not the position)
 // (metric: the position moves along vel = M^-1 p, formed first -- finrom_hmc_leapfrog_field_metric; nullptr: along p itself)
@@ -2532,6 +1883,7 @@ static int hmc_leapfrog_field_impl(finrom_rom_t rom, finrom_mlp_t mlp, const dou
   return launch_field_prior(prior->U, prior->n, 1, grad_field, nullptr, 0.0, nullptr, nullptr, nullptr, &tl, a->C,
                             (double*)prior->fpart.p, (int*)prior->ftick.p, st);
 }
+extern "C" {
 int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior, const double* field_mean,
                               double* field, double* grad_field, const finrom_hmc_state* a, int32_t step, const double* data,
                               int32_t data_per_sample, double* qoi_r, double* e_nn, void* stream) {
@@ -2540,6 +1892,7 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
                                  nullptr, nullptr, stream);
 }
 
+}  // extern "C"
 // ---- the chains under the full-order and the plain reduced model (hmc_model.hip; hmc.py model="fom" | "rom") ----------------------
 static int hmc_model_map_check(const char* who, const double* A, int32_t P) {
   if (A != nullptr && (P < 1 || P > HMC_MODEL_MAXP)) {
@@ -2572,6 +1925,7 @@ static int hmc_kick_impl(const finrom_hmc_state* a, int32_t step, const double* 
   if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_ARG; }
   return launch_hmc_kick(h, a->Kq[(step + 1) & 1], grad, g_theta, A, P, grad_out, (hipStream_t)stream);
 }
+extern "C" {
 int finrom_hmc_drift(const finrom_hmc_state* a, int32_t step, const double* A, const double* theta0, int32_t P, double* theta_out,
                      void* stream) {
   CallGuard cg((hipStream_t)stream);
@@ -2582,6 +1936,7 @@ int finrom_hmc_kick(const finrom_hmc_state* a, int32_t step, const double* grad,
   CallGuard cg((hipStream_t)stream);
   return hmc_kick_impl(a, step, grad, g_theta, A, P, grad_out, stream, "hmc_kick");
 }
+}  // extern "C"
 // info is this step's alone: finrom_fom_gradient's and finrom_rom_grad's kernels flag into it (a kernel node: see romml_grad_impl)
 static int hmc_clear_info(int32_t* info, int64_t S, hipStream_t st) {
   hipLaunchKernelGGL(clear_info_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, info, S);
@@ -2598,6 +1953,7 @@ static int hmc_fom_check(finrom_fom_t fom, const finrom_hmc_state* a, const doub
   if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_UNSUPPORTED; }
   return 0;
 }
+extern "C" {
 int finrom_hmc_leapfrog_fom(finrom_fom_t fom, const finrom_hmc_state* a, int32_t step, const double* data, int32_t data_per_sample,
                             double* grad_out, double* qoi, void* stream) {
   CallGuard cg((hipStream_t)stream);
@@ -2721,6 +2077,7 @@ int finrom_metric_apply(finrom_metric_t h, int32_t op, const double* x, int64_t 
   if (S == 0) return 0;
   return launch_metric_apply(h->d, op, x, S, y, quad, (hipStream_t)stream);
 }
+}  // extern "C"
 static int hmc_metric_check(const finrom_hmc_state* a, finrom_metric_t m, const char* who) {
   if (!m) { set_error(std::string(who) + ": null metric handle"); return FINROM_ERR_ARG; }
   if (a->n != m->d.n) {
@@ -2728,6 +2085,7 @@ static int hmc_metric_check(const finrom_hmc_state* a, finrom_metric_t m, const 
   }
   return 0;
 }
+extern "C" {
 int finrom_hmc_begin_metric(const finrom_hmc_state* a, finrom_metric_t metric, void* stream) {
   CallGuard cg((hipStream_t)stream);
   HmcDev h;
@@ -2757,6 +2115,7 @@ int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const d
                                  &metric->d, vel, stream);
 }
 
+}  // extern "C"
 // multi-start L-BFGS (lbfgs_kernels.hip): every check on the host, before the stream is looked at
 static int lbfgs_dev(const finrom_lbfgs_state* a, LbfgsDev* L, const char* who) {
   auto bad = [&](const std::string& what) { set_error(std::string(who) + ": " + what); return FINROM_ERR_ARG; };
@@ -2785,6 +2144,7 @@ static int lbfgs_dev(const finrom_lbfgs_state* a, LbfgsDev* L, const char* who) 
   L->k1_ptr = a->k1_ptr; L->k1_idx = a->k1_idx; L->k1_val = a->k1_val;
   return 0;
 }
+extern "C" {
 int finrom_lbfgs_begin(const finrom_lbfgs_state* a, void* stream) {
   LbfgsDev L;
   if (int rc = lbfgs_dev(a, &L, "lbfgs_begin")) return rc;

@@ -176,6 +176,14 @@ int launch_pack(const double* x, int64_t S, int d, double* xT, hipStream_t st);
 int launch_fom_assemble(const FomDev& p, const double* xT, int64_t nblk, double* Gw, hipStream_t st);
 int launch_fom(const FomDev& p, const double* xT, int64_t nblk, int64_t S, double* Gw, double* qoi, int* info, hipStream_t st);
 int launch_unpack_w(const FomDev& p, const double* Gw, int64_t S, double* w, hipStream_t st);
+// util_kernels.hip: sub-fin averages, the sampler's triangular product, differences, the counter-based draws
+int launch_subfin_avg(const double* Sop, int P, int n, const double* k, int64_t S, double* theta, hipStream_t st);
+int launch_sampler(const double* U, int n, const double* xi, int64_t S, double* k, hipStream_t st);
+int launch_sub(const double* a, const double* b, int64_t count, double* out, hipStream_t st);
+int launch_sub_flagged(const double* a, double* b, const int* info, int n_obs, int64_t count, double* out, hipStream_t st);
+int launch_philox_normal(unsigned long long seed, int64_t first, int64_t S, int n, double* xi, hipStream_t st);
+int launch_hmc_draw(const unsigned long long* seeds, int64_t C, int n, int64_t first, int64_t B, double* P_block, double* lu_block,
+                    hipStream_t st);
 
 // frontal band sweep (fom_band.hip, finrom_fom_set_band): per-sample workspace [AB | L | Lx | y -> w], sample-blocked
 struct BandDev {

@@ -412,3 +412,22 @@ def test_the_leapfrog_form_refuses_a_batched_model(spaces):
     lf.reset()
     with pytest.raises(_ffi.FinromError, match=r"status -4\).*one-sample form"):
         lf.step(0)
+
+
+def test_the_leapfrog_form_refuses_a_null_reduced_model(spaces):
+    """finrom_hmc_leapfrog with a valid state, a valid error-model handle and rom = NULL: FINROM_ERR_ARG (-1) and an error text, from
+    the argument check in front of every launch (the call used to read rom->d.P first) -- the state keeps its bits."""
+    import torch
+    c = K.FUSED_BY_NAME["one-staged-w16"]
+    lf = _Leap(spaces, c)
+    lf.reset()
+    torch.cuda.synchronize()
+    before = lf.snapshot()
+    rc = lf.L.finrom_hmc_leapfrog(None, lf.mlp._h, lf.sop.ptr, C.byref(lf.st), 0, lf.data.data_ptr(), 1 if c.per_sample else 0,
+                                  lf.grad[0].data_ptr(), lf.q[0].data_ptr(), lf.e[0].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == -1
+    assert b"hmc_leapfrog: bad argument" in lf.L.finrom_last_error()
+    torch.cuda.synchronize()
+    after = lf.snapshot()
+    for k in ("Kq0", "Kq1", "P", "dUq", "loss", "info"):
+        assert np.array_equal(before[k], after[k]), k

@@ -29,6 +29,33 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert lib.finrom_version() == _ffi.ABI_VERSION == 12
 
 
+def test_library_defines_no_unmangled_symbol_but_the_declared_entry_points():
+    """The library shares a process with torch, the HIP runtime and RCCL: beside the finrom_* entry points of include/finrom.h it
+    defines only C++-mangled names (_Z...) and the toolchain's own (_init, _fini, __hip_cuid_*), so that no helper or global of the
+    host layer (size_class, g_pool_mu, pack_cost, ... once had C linkage) can bind to, or be bound by, another library's."""
+    from bayesianinferencedl_amd import _build
+    path = _build.build()
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    defined = {}
+    for line in out.splitlines():
+        parts = line.split()
+        if len(parts) >= 3:
+            defined[parts[-1].split("@")[0]] = parts[-2]
+    assert defined, "nm listed nothing"
+    header = open(os.path.join(ROOT, "include", "finrom.h")).read()
+    declared = set(re.findall(r"\b(finrom_[a-z0-9_]+)\s*\(", header))
+    assert declared, "no declarations parsed"
+    exported = {s_ for s_ in defined if re.match(r"^finrom_", s_)}
+    assert exported == declared, sorted(exported ^ declared)
+    stray = sorted(s_ for s_, kind in defined.items() if s_ not in exported and kind in "TDB" and not s_.startswith("_"))
+    assert stray == [], stray
+    once_global = {"build_grouped_tables", "event_destroy_cb", "g_pool_events", "g_pool_free", "g_pool_free_bytes", "g_pool_live",
+                   "g_pool_mu", "group_pays", "kstep_vector_ops", "mirror_ksteps", "pack_consecutive", "pack_cost", "pack_nested",
+                   "pack_padded", "rows_by_term_count", "short_scale_free", "size_class", "uniform_ksteps", "validate_rom_desc",
+                   "validate_rom_mirror"}
+    assert not once_global & set(defined), sorted(once_global & set(defined))
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from bayesianinferencedl_amd import _ffi
     monkeypatch.setenv("FINROM_LIB", "/nonexistent/libfinrom_hip.so")
@@ -392,7 +419,7 @@ def test_sampler_rejects_a_lower_triangular_factor():
 
 def test_validators_under_address_sanitizer():
     """SURVEY 5 (race / memory checking of the host layer): the C-ABI's create-time validators run under an AddressSanitizer +
-    UBSan build of csrc/finrom_api.hip (host code only) on the CPU box, fed corrupt descriptors by tools/asan_validators.py."""
+    UBSan build of the host layer (_build.API_SOURCES: host code only) on the CPU box, fed corrupt descriptors by tools/asan_validators.py."""
     from bayesianinferencedl_amd import _build
     lib = _build.build_asan()
     rt = _build.asan_runtime()
