@@ -62,6 +62,12 @@ class FomBandDesc(C.Structure):
                 ("qoi_FgQ", c_f64p), ("qoi_row_fin", c_i32p), ("qoi_obs_ptr", c_i32p), ("qoi_obs_idx", c_i32p), ("qoi_obs_w", c_f64p)]
 
 
+# finrom_fom_band_fin_rec / finrom_fom_band_post_rec (include/finrom.h) as NumPy record types: 32 and 96 bytes
+BAND_FIN_REC = np.dtype([("off", np.int32, 3), ("pad0", np.int32), ("fg", np.float64), ("pad1", np.float64)])
+BAND_POST_REC = np.dtype([("off", np.int32, 3), ("gv", np.int32), ("ex", np.int32), ("act", np.int32), ("c0", np.int32),
+                          ("c1", np.int32), ("row", np.int32), ("pad0", np.int32), ("fg", np.float64), ("cw", np.float64, 5),
+                          ("pad1", np.float64)])
+
 c_f32p = C.POINTER(C.c_float)
 
 
@@ -146,6 +152,11 @@ SIGNATURES = {
     "finrom_fom_band_mirror_functionals": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p,
                                                      c_i32p, c_f64p, c_i32p, c_i32p]),
     "finrom_fom_band_mirror_form": (C.c_int, [C.c_void_p]),
+    "finrom_fom_band_mirror_records": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p,
+                                                 c_i32p, C.c_void_p, C.c_void_p]),
+    "finrom_fom_band_records_check": (C.c_int, [C.POINTER(FomBandDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p,
+                                                C.c_void_p, C.c_void_p]),
+    "finrom_fom_band_mirror_records_on": (C.c_int, [C.c_void_p]),
     "finrom_fom_solve_rhs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_fom_last_path": (C.c_int, [C.c_void_p]),
     "finrom_fom_set_small_max": (C.c_int, [C.c_void_p, C.c_int32]),

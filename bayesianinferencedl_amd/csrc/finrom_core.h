@@ -222,7 +222,18 @@ bool band_supported(int NSF, int NSP, int NX);
 // node, as an offset into the region at BandDev::offY.  A BandDev that goes with these tables has offY = nAB and
 // gsize = nAB + nfins * nif: value slots and the fins' g are all its workspace holds.
 constexpr int BAND_NF = 5;
-struct BandFnDev { const double* cw = nullptr; const int* piv_row = nullptr; const int* piv_off = nullptr; };
+// Pivot records (finrom.h, finrom_fom_band_mirror_records): everything the store-free sweeps read per pivot, in one aligned record
+// per entering node, so that the kernel fetches it with wide scalar loads steps ahead of its use.  fin_rec: nfins x (npf + nif)
+// records; post_rec: npost + NSP (record k: node k enters, act belongs to pivot k - NSP).  Both arrays end in band_rec_pad(NS) zero
+// records: the sweep's pipeline requests records beyond its last pivot and never uses them.  nullptr: the tables above are read.
+typedef finrom_fom_band_fin_rec BandFinRec;
+typedef finrom_fom_band_post_rec BandPostRec;
+static_assert(sizeof(BandFinRec) == 32 && sizeof(BandPostRec) == 96, "records are two and six 16-byte scalar loads");
+constexpr int band_rec_pad(int NS) { return 4 * NS; }
+struct BandFnDev {
+  const double* cw = nullptr; const int* piv_row = nullptr; const int* piv_off = nullptr;
+  const BandFinRec* fin_rec = nullptr; const BandPostRec* post_rec = nullptr;
+};
 int launch_fom_band(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qoi_only,
                     const BandFnDev* fn = nullptr);
 int launch_fom_band_wide(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st, bool qo);   // fom_band_wide.hip

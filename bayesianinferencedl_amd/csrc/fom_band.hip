@@ -676,6 +676,263 @@ __device__ __forceinline__ void fom_band_fn_body(BandDev p, const int* __restric
     });
 }
 
+// ---- the same form on pivot records (DESIGN 4c'; BandFinRec / BandPostRec, finrom.h) -----------------------------------------------
+// band_sweep reads, per pivot, nine wave-uniform tables where it needs them -- every read a scalar round trip on the critical path,
+// with the address arithmetic of its table -- and loads the fin's g for an interface node behind a branch, whose join makes the
+// wave wait for ALL its vector loads in every step: the entries requested for two steps ahead included.  Here a pivot's table
+// values are one record, requested into SGPRs RF steps before they are used: at step s the node that enters behind pivot s has
+//   its address part (three value slots and the slot of g, as byte offsets)   in ra[s mod RF] -- requested at step s - RF,
+//   from which its values are requested into ab / gvr[s mod RF]               -- used at step s + RF,
+//   and its enter part (ent_extra, act, ecp range, row, FgQ, cw) requested     -- into re[s mod RF], used at step s + RF.
+// The load of g is unconditional (a node that is no interface node has a harmless slot in its record; the select on row == o
+// discards it) and travels with the three entries.  Records are read through the constant address space (scalar loads, their
+// waits at the uses) and requested at the END of a step, behind its last LDS access: scalar loads share lgkmcnt with LDS and return
+// out of order, so any wait for an LDS value also waits for them.  The arithmetic is band_sweep<.., NOSTORE>'s, operation by
+// operation: the results are the same bits.
+typedef int rec_i4 __attribute__((ext_vector_type(4)));
+typedef const rec_i4 __attribute__((address_space(4)))* rec_p;
+__device__ __forceinline__ double rec_f64(int lo, int hi) { return __hiloint2double(hi, lo); }
+__device__ __forceinline__ void rec_settle(rec_i4& v) {      // the wait for a requested part of a record happens where this stands
+  int x = v.x, y = v.y, z = v.z, w = v.w;
+  asm volatile("" : "+s"(x), "+s"(y), "+s"(z), "+s"(w));
+  v = rec_i4{x, y, z, w};
+}
+
+template <int NS, bool POST, int NXM, int NF>
+__device__ __forceinline__ void band_sweep_rec(const Io& io, double* __restrict__ xs, rec_p rec, const int* __restrict__ ecp_slot,
+                                               const int* __restrict__ ecp_off, int npiv, int ntot, double (&win)[NS * (NS + 1) / 2],
+                                               double (&yw)[NS], int& bad, FnState<(NF > 0 ? NF : 1), NS>* __restrict__ fs = nullptr) {
+  using L = XL<NS, NXM>;
+  constexpr int XZ = L::SIZE;
+  constexpr int Q = POST ? sizeof(BandPostRec) / 16 : sizeof(BandFinRec) / 16;      // 16-byte loads per record; the first is the address part
+  static_assert(POST == (NF > 0), "the post carries the functionals, the fins carry none");
+  static_for<0, NS*(NS + 1) / 2>([&](auto i) { win[decltype(i)::value] = 0.0; });
+  static_for<0, NS>([&](auto i) { yw[decltype(i)::value] = 0.0; });
+  if constexpr (POST) static_for<0, L::SIZE + NXM * NF>([&](auto i) { xs[decltype(i)::value * 64] = 0.0; });
+  if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+    constexpr int o = decltype(oc)::value;
+    fs->q[o] = 0.0;
+    static_for<0, NS>([&](auto i) { fs->zw[o][decltype(i)::value] = 0.0; });
+  });
+
+  // the enter part e of a post record: (ex, act, c0, c1) (row, -, fg) (cw0, cw1) (cw2, cw3) (cw4, -); of a fin record: (fg, -)
+  auto enter = [&](auto uc, double ab0, double ab1, double ab2, double gv, const rec_i4 (&e)[Q - 1]) {
+    constexpr int u = decltype(uc)::value;
+    static_for<0, NS>([&](auto vc) { constexpr int v = decltype(vc)::value; if constexpr (v != u) win[tri(u, v)] = 0.0; });
+    double diag = 0.0, yv = 0.0;
+    double zv[NF > 0 ? NF : 1];
+    if constexpr (NF > 0) {
+      const int row = e[1].x;
+      static_for<0, NF>([&](auto oc) {
+        constexpr int o = decltype(oc)::value;
+        const double cwo = o % 2 == 0 ? rec_f64(e[2 + o / 2].x, e[2 + o / 2].y) : rec_f64(e[2 + o / 2].z, e[2 + o / 2].w);
+        zv[o] = cwo + (row == o ? gv : 0.0);
+      });
+    }
+    if constexpr (POST) {
+      static_for<0, NXM>([&](auto sc) { xs[(L::X + decltype(sc)::value * NS + u) * 64] = 0.0; });
+      const int ex = e[0].x;
+      if (ex != 0) {                                     // the node was an extra: its state moves from LDS into the window
+        const int sl = ex - 1;
+        if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+          constexpr int o = decltype(oc)::value;
+          zv[o] = xs[(XZ + sl * NF + o) * 64] + zv[o];
+          xs[(XZ + sl * NF + o) * 64] = 0.0;
+        });
+        static_for<0, NS>([&](auto vc) {
+          constexpr int v = decltype(vc)::value;
+          if constexpr (v != u) win[tri(u, v)] = xs[(L::X + sl * NS + v) * 64];
+        });
+        diag = xs[(L::XD + sl) * 64]; yv = xs[(L::XY + sl) * 64];
+        static_for<0, NXM>([&](auto oc) {
+          constexpr int o = decltype(oc)::value;
+          if (o != sl) {
+            const int a = o > sl ? o : sl, b = o > sl ? sl : o;
+            const int idx = L::XX + a * (a - 1) / 2 + b;
+            xs[(L::X + o * NS + u) * 64] = xs[idx * 64];
+            xs[idx * 64] = 0.0;
+          }
+        });
+        static_for<0, NS>([&](auto vc) { xs[(L::X + sl * NS + decltype(vc)::value) * 64] = 0.0; });
+        xs[(L::XD + sl) * 64] = 0.0; xs[(L::XY + sl) * 64] = 0.0;
+      }
+    }
+    win[tri(u, u)] = diag + ab0;
+    win[tri(u, (u + NS - 1) % NS)] += ab1;
+    win[tri(u, (u + 1) % NS)] += ab2;
+    yw[u] = yv + (POST ? rec_f64(e[POST ? 1 : 0].z, e[POST ? 1 : 0].w) : rec_f64(e[0].x, e[0].y));
+    if constexpr (NF > 0) static_for<0, NF>([&](auto oc) { fs->zw[decltype(oc)::value][u] = zv[decltype(oc)::value]; });
+    if constexpr (POST) {
+      for (int c = e[0].z, c1 = e[0].w; c < c1; ++c)     // long-range couplings of this node: to extras (rare; its loads wait in place)
+        xs[(L::X + ecp_slot[c] * NS + u) * 64] += io.ld(ecp_off[c]);
+    }
+  };
+
+  static_for<0, NS>([&](auto uc) {                       // prologue: the first NS nodes enter an empty window
+    constexpr int u = decltype(uc)::value;
+    if (u < ntot) {
+      const rec_i4 a = rec[u * Q];
+      rec_i4 e[Q - 1];
+      static_for<1, Q>([&](auto i) { e[decltype(i)::value - 1] = rec[u * Q + decltype(i)::value]; });
+      enter(uc, io.ldb(a.x), io.ldb(a.y), io.ldb(a.z), NF > 0 ? io.ldb(a.w) : 0.0, e);
+    }
+  });
+
+  constexpr int RF = (NS % 2 == 0) ? 2 : NS;
+  double ab[RF][3], gvr[RF];
+  rec_i4 ra[RF], re[RF][Q - 1];
+  static_for<0, RF>([&](auto i) {
+    constexpr int s = decltype(i)::value;
+    ab[s][0] = ab[s][1] = ab[s][2] = 0.0; gvr[s] = 0.0;
+    ra[s] = rec[(NS + s) * Q];                           // (beyond the last node: pad records, band_rec_pad)
+    static_for<1, Q>([&](auto j) { re[s][decltype(j)::value - 1] = rec_i4{0, 0, 0, 0}; });
+  });
+  static_for<0, RF>([&](auto i) { rec_settle(ra[decltype(i)::value]); });
+  for (int s0 = 0; s0 < npiv + RF; s0 += NS) {
+    static_for<0, NS>([&](auto usc) {
+      constexpr int us = decltype(usc)::value;
+      constexpr int u = (us + NS - RF % NS) % NS;        // window slot of pivot s - RF
+      constexpr int rs = us % RF;                        // ring slot (of pivot s - RF and, afterwards, of pivot s)
+      const int sidx = s0 + us;
+      const int pp = sidx - RF;
+      if (pp >= 0 && pp < npiv) {
+        const bool more = pp + NS < ntot;
+        const double ab0 = ab[rs][0], ab1 = ab[rs][1], ab2 = ab[rs][2];
+        const double d = win[tri(u, u)];
+        if (!(d > 0.0)) bad = 1;
+        double inv = __builtin_amdgcn_rsq(d);
+        inv = inv * fma(-0.5 * d * inv, inv, 1.5);
+        inv = inv * fma(-0.5 * d * inv, inv, 1.5);
+        double l[NS];
+        static_for<1, NS>([&](auto sc) { constexpr int s_ = decltype(sc)::value; l[s_] = win[tri((u + s_) % NS, u)] * inv; });
+        const double yp = yw[u] * inv;
+        double zp[NF > 0 ? NF : 1];
+        if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+          constexpr int o = decltype(oc)::value;
+          zp[o] = fs->zw[o][u] * inv;
+          fs->q[o] = fma(zp[o], yp, fs->q[o]);
+          static_for<1, NS>([&](auto sc) {
+            constexpr int s_ = decltype(sc)::value;
+            fs->zw[o][(u + s_) % NS] = fma(-l[s_], zp[o], fs->zw[o][(u + s_) % NS]);
+          });
+        });
+        static_for<1, NS>([&](auto sc) {
+          constexpr int s_ = decltype(sc)::value;
+          yw[(u + s_) % NS] = fma(-l[s_], yp, yw[(u + s_) % NS]);
+          static_for<1, s_ + 1>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            win[tri((u + s_) % NS, (u + t) % NS)] = fma(-l[s_], l[t], win[tri((u + s_) % NS, (u + t) % NS)]);
+          });
+        });
+        if constexpr (POST) {
+          const int am = re[rs][0].y;
+          if (am != 0) {
+            double le[NXM];
+            static_for<0, NXM>([&](auto sc) {
+              constexpr int sl = decltype(sc)::value;
+              le[sl] = 0.0;
+              if (am & (1 << sl)) {
+                const double v = xs[(L::X + sl * NS + u) * 64] * inv;
+                le[sl] = v;
+                xs[(L::XY + sl) * 64] = fma(-v, yp, xs[(L::XY + sl) * 64]);
+                if constexpr (NF > 0) static_for<0, NF>([&](auto oc) {
+                  constexpr int a = (XZ + sl * NF + decltype(oc)::value) * 64;
+                  xs[a] = fma(-v, zp[decltype(oc)::value], xs[a]);
+                });
+                xs[(L::XD + sl) * 64] = fma(-v, v, xs[(L::XD + sl) * 64]);
+                static_for<1, NS>([&](auto tc) {
+                  constexpr int t = decltype(tc)::value;
+                  constexpr int a = (L::X + sl * NS + (u + t) % NS) * 64;
+                  xs[a] = fma(-v, l[t], xs[a]);
+                });
+              }
+            });
+            static_for<1, NXM>([&](auto ac) {
+              constexpr int a = decltype(ac)::value;
+              static_for<0, a>([&](auto bc) {
+                constexpr int b = decltype(bc)::value;
+                xs[L::xx(a, b) * 64] = fma(-le[a], le[b], xs[L::xx(a, b) * 64]);
+              });
+            });
+          }
+        }
+        if (more) enter(std::integral_constant<int, u>{}, ab0, ab1, ab2, gvr[rs], re[rs]);
+        else {
+          static_for<0, NS>([&](auto vc) { win[tri(u, decltype(vc)::value)] = 0.0; });      // nobody enters: the slot is empty
+          if constexpr (NF > 0) static_for<0, NF>([&](auto oc) { fs->zw[decltype(oc)::value][u] = 0.0; });
+        }
+      }
+      // The node that enters behind pivot s: its values in flight for RF steps.  Requested on EVERY path -- beyond the last node
+      // the address part is a neighbour's or a pad record's (offset 0) and nobody uses what comes back -- so that the number of
+      // loads in flight is the same whichever way the step went, and the wait at their use is for the older ones only.
+      ab[rs][0] = io.ldb(ra[rs].x); ab[rs][1] = io.ldb(ra[rs].y); ab[rs][2] = io.ldb(ra[rs].z);
+      if constexpr (NF > 0) gvr[rs] = io.ldb(ra[rs].w);
+      // The records.  A wait for one scalar value waits for every scalar load in flight, and the compiler puts it at the value's
+      // first use -- the test of `act` at the top of a step, right behind the requests of the step before.  So the wait is taken
+      // HERE, once per step, for the records the NEXT step uses (requested a step ago: they have landed), and only then are this
+      // step's requests issued: nothing a step reads is still in flight while it runs.
+      constexpr int nrs = (us + 1) % RF;
+      rec_settle(ra[nrs]);
+      static_for<1, Q>([&](auto j) { rec_settle(re[nrs][decltype(j)::value - 1]); });
+      int nx = sidx + NS;
+      asm volatile("" : "+s"(nx));                       // (the requests stay behind the settled values)
+      static_for<1, Q>([&](auto j) { re[rs][decltype(j)::value - 1] = rec[nx * Q + decltype(j)::value]; });      // its enter part
+      ra[rs] = rec[(nx + RF) * Q];                       // the address part of the node RF steps behind it
+    });
+  }
+}
+
+template <int NSF, int NSP, int NXM, int NF>
+__device__ __forceinline__ void fom_band_fnrec_body(BandDev p, const BandFinRec* __restrict__ fin_rec, const BandPostRec* __restrict__ post_rec,
+                                                    const int* __restrict__ ecp_slot, const int* __restrict__ ecp_off,
+                                                    const int* __restrict__ schur_off, double* __restrict__ Gw, int64_t S,
+                                                    double* __restrict__ qoi, int* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) double xlds[];
+  const int lane = threadIdx.x;
+  const int64_t blk = blockIdx.x;
+  double* __restrict__ Gs = Gw + blk * (int64_t)p.gsize * 64;
+  Io io{__builtin_amdgcn_make_buffer_rsrc(Gs, 0, p.gsize * 512, 0x00020000), lane * 8};
+  double* xs = xlds + lane;
+  int bad = 0;
+  constexpr int NIFT = (NSF - 1) * NSF / 2;
+  {
+    double win[NSF * (NSF + 1) / 2], yw[NSF];
+    for (int f = 0; f < p.nfins; ++f) {
+      const int npiv = p.npf, ntot = p.npf + p.nif;
+      band_sweep_rec<NSF, false, NXM, 0>(io, xs, (rec_p)(unsigned long long)(fin_rec + f * ntot), ecp_slot, ecp_off, npiv, ntot, win, yw, bad);
+      fin_functional_out<NSF>(p, io, yw, f, npiv, p.nif);
+      int k = 0;
+      for (int t = 0; t < p.nif; ++t)
+        for (int s = 0; s <= t; ++s, ++k) {
+          const int a = (npiv + t) % NSF, b = (npiv + s) % NSF;
+          double v = 0.0;
+          static_for<0, NSF>([&](auto ac) {
+            static_for<0, decltype(ac)::value + 1>([&](auto bc) {
+              constexpr int ua = decltype(ac)::value, ub = decltype(bc)::value;
+              v = ((a == ua && b == ub) || (a == ub && b == ua)) ? win[tri(ua, ub)] : v;
+            });
+          });
+          const int off = schur_off[f * NIFT + k];
+          io.st(io.ld(off) + v, off);
+        }
+    }
+  }
+  FnState<NF, NSP> fs;
+  {
+    double win[NSP * (NSP + 1) / 2], yw[NSP];
+    band_sweep_rec<NSP, true, NXM, NF>(io, xs, (rec_p)(unsigned long long)post_rec, ecp_slot, ecp_off, p.npost, p.npost, win, yw, bad, &fs);
+  }
+  const int64_t s = blk * 64 + lane;
+  const double nanv = __builtin_nan("");
+  if (bad && info != nullptr && s < S) atomicOr(&info[s], 1);
+  if (s < S)
+    static_for<0, NF>([&](auto oc) {                     // each distinct row once, stored to all its output columns
+      constexpr int o = decltype(oc)::value;
+      if (o < p.n_obs)
+        for (int c = p.out_ptr[o], c1 = p.out_ptr[o + 1]; c < c1; ++c) qoi[s * p.n_out + p.out_col[c]] = bad ? nanv : fs.q[o];
+    });
+}
+
 // ---- the post's backward sweep with the other waves as loaders ----------------------------------------------------------------
 // L^T w = y is a recurrence over the pivots: one wave computes, and what it waits for is the next column of L from HBM (written
 // non-temporally by the forward sweep; a register ring of four columns left 0.9 us per pivot at one wave per CU).  The window is
@@ -914,6 +1171,14 @@ __global__ __launch_bounds__(64, FINROM_HALF_FN_WPE) void fom_band_half_fn_kerne
     double* __restrict__ qoi, int* __restrict__ info) {
   fom_band_fn_body<NSF, NSP, NXM, BAND_NF>(p, abmap, Fg, act, ent_extra, ecp_ptr, ecp_slot, ecp_off, schur_off, cw, piv_row, piv_off, Gw, S, qoi, info);
 }
+// ... and on pivot records (BandFnDev::fin_rec / post_rec; FINROM_FOM_NO_PIVOT_RECORDS=1 keeps the kernel above)
+template <int NSF, int NSP, int NXM>
+__global__ __launch_bounds__(64, FINROM_HALF_FN_WPE) void fom_band_half_fnrec_kernel(
+    BandDev p, const BandFinRec* __restrict__ fin_rec, const BandPostRec* __restrict__ post_rec, const int* __restrict__ ecp_slot,
+    const int* __restrict__ ecp_off, const int* __restrict__ schur_off, double* __restrict__ Gw, int64_t S, double* __restrict__ qoi,
+    int* __restrict__ info) {
+  fom_band_fnrec_body<NSF, NSP, NXM, BAND_NF>(p, fin_rec, post_rec, ecp_slot, ecp_off, schur_off, Gw, S, qoi, info);
+}
 template <int NSF, int NSP, int NXM, int WV, bool QO>
 __global__ __launch_bounds__(64 * WV) void fom_band_ldsw_kernel(FR_BAND_ARGS) { fom_band_ldsw_body<NSF, NSP, NXM, WV, QO>(FR_BAND_PASS); }
 
@@ -950,6 +1215,10 @@ int launch_t(const BandDev& p, double* Gw, int64_t nblk, int64_t S, double* qoi,
 template <int NSF, int NSP, int NXM = 2>
 int launch_fn(const BandDev& p, const BandFnDev& fn, double* Gw, int64_t nblk, int64_t S, double* qoi, int* info, hipStream_t st) {
   const size_t lds = (size_t)(XL<NSP, NXM>::SIZE + NXM * BAND_NF) * 64 * sizeof(double);      // the extras' state | their functional values
+  if (fn.post_rec != nullptr && fn.fin_rec != nullptr)
+    hipLaunchKernelGGL((fom_band_half_fnrec_kernel<NSF, NSP, NXM>), dim3((unsigned)nblk), dim3(64), lds, st, p, fn.fin_rec, fn.post_rec,
+                       p.ecp_slot, p.ecp_off, p.schur_off, Gw, S, qoi, info);
+  else
   hipLaunchKernelGGL((fom_band_half_fn_kernel<NSF, NSP, NXM>), dim3((unsigned)nblk), dim3(64), lds, st, p, p.abmap, p.FgQ, p.act, p.ent_extra,
                      p.ecp_ptr, p.ecp_slot, p.ecp_off, p.schur_off, fn.cw, fn.piv_row, fn.piv_off, Gw, S, qoi, info);
   FR_HIP(hipGetLastError());

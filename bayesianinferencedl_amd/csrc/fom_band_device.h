@@ -34,6 +34,9 @@ struct Io {                       // the wave's slice of the workspace as a buff
   template <int K> __device__ __forceinline__ double ldk(int elem) const {      // element elem + K, K folded into the offset field
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, lane8 + (K % 8) * 512, (elem + K / 8 * 8) * 512, BAND_STREAM_AUX));
   }
+  __device__ __forceinline__ double ldb(int byte_off) const {                   // the offset in bytes, as a pivot record holds it
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, lane8, byte_off, 0));
+  }
   __device__ __forceinline__ void st(double v, int elem) const {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, lane8, elem * 512, 0);
   }

@@ -195,6 +195,59 @@ int derive_post_functionals(const finrom_fom_band_desc* a, int n_half, int n_row
   return 1;
 }
 
+// The pivot records of the functional form (finrom.h; fom_band.hip, band_sweep_rec) from a VALIDATED half descriptor and the
+// tables derive_post_functionals made of it.  Without the pad records (band_rec_pad) the kernel's arrays end in.
+void derive_pivot_records(const finrom_fom_band_desc* a, const std::vector<double>& cw, const std::vector<int>& piv_row,
+                          const std::vector<int>& piv_off, std::vector<BandFinRec>& fin_rec, std::vector<BandPostRec>& post_rec) {
+  const int ntot = a->npf + a->nif, gfin = a->nfins * ntot;
+  fin_rec.assign(gfin, BandFinRec{});
+  for (int g = 0; g < gfin; ++g) {
+    for (int e = 0; e < 3; ++e) fin_rec[g].off[e] = a->abmap[3 * g + e] << 9;
+    fin_rec[g].fg = a->qoi_FgQ[g];
+  }
+  post_rec.assign(a->npost + a->NSP, BandPostRec{});
+  for (int t = 0; t < a->npost + a->NSP; ++t) {
+    BandPostRec& r = post_rec[t];
+    if (t >= a->NSP) r.act = a->act[t - a->NSP];
+    if (t >= a->npost) continue;
+    for (int e = 0; e < 3; ++e) r.off[e] = a->abmap[3 * (gfin + t) + e] << 9;
+    r.row = piv_row[t];
+    r.gv = r.row >= 0 ? (a->nAB + piv_off[t]) << 9 : r.off[0];      // (no interface node: any slot will do, the sweep discards it)
+    r.ex = a->ent_extra[t]; r.c0 = a->ecp_ptr[t]; r.c1 = a->ecp_ptr[t + 1];
+    r.fg = a->qoi_FgQ[gfin + t];
+    for (int o = 0; o < BAND_NF; ++o) r.cw[o] = cw[(size_t)t * BAND_NF + o];
+  }
+}
+
+// The nine source tables rebuilt from the records, entry by entry; every offset the kernel loads from inside the workspace of
+// the functional form (nAB value slots + nfins x nif slots of the fins' g).
+int check_pivot_records(const finrom_fom_band_desc* a, const std::vector<double>& cw, const std::vector<int>& piv_row,
+                        const std::vector<int>& piv_off, const BandFinRec* fin_rec, const BandPostRec* post_rec) {
+  auto bad = [&](const char* what) { set_error(std::string("fom_set_band_mirror: invalid pivot record (") + what + ")"); return (int)FINROM_ERR_ARG; };
+  const int ntot = a->npf + a->nif, gfin = a->nfins * ntot;
+  const int64_t wbytes = ((int64_t)a->nAB + a->nfins * a->nif) << 9;
+  for (int g = 0; g < gfin; ++g) {
+    for (int e = 0; e < 3; ++e) if (fin_rec[g].off[e] != a->abmap[3 * g + e] << 9) return bad("abmap of a fin node");
+    if (fin_rec[g].fg != a->qoi_FgQ[g]) return bad("FgQ of a fin node");
+  }
+  for (int t = 0; t < a->npost + a->NSP; ++t) {
+    const BandPostRec& r = post_rec[t];
+    if (r.act != (t >= a->NSP ? a->act[t - a->NSP] : 0)) return bad("act");
+    if (t >= a->npost) {
+      if (r.off[0] | r.off[1] | r.off[2] | r.gv | r.ex | r.c0 | r.c1 | r.row) return bad("tail record");
+      continue;
+    }
+    for (int e = 0; e < 3; ++e) if (r.off[e] != a->abmap[3 * (gfin + t) + e] << 9) return bad("abmap");
+    if (r.fg != a->qoi_FgQ[gfin + t]) return bad("FgQ");
+    if (r.ex != a->ent_extra[t]) return bad("ent_extra");
+    if (r.c0 != a->ecp_ptr[t] || r.c1 != a->ecp_ptr[t + 1]) return bad("ecp_ptr");
+    if (r.row != piv_row[t]) return bad("piv_row");
+    if (r.row >= 0 ? r.gv != (a->nAB + piv_off[t]) << 9 : (r.gv < 0 || (r.gv & 511) != 0 || r.gv >= wbytes)) return bad("piv_off");
+    for (int o = 0; o < BAND_NF; ++o) if (r.cw[o] != cw[(size_t)t * BAND_NF + o]) return bad("cw");
+  }
+  return 0;
+}
+
 }  // namespace finrom
 
 using namespace finrom;
@@ -226,6 +279,36 @@ int finrom_fom_band_mirror_functionals(const finrom_fom_band_desc* a, int32_t n_
   *fits = f;
   if (f) { std::copy(c.begin(), c.end(), cw); std::copy(pr.begin(), pr.end(), piv_row); std::copy(po.begin(), po.end(), piv_off); }
   return 0;
+}
+
+// Host only: the pivot records finrom_fom_set_band_mirror installs with the functional form, for a test to walk.
+int finrom_fom_band_mirror_records(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                   const int32_t* out_ptr, const int32_t* out_col, int32_t* fits, finrom_fom_band_fin_rec* fin_rec,
+                                   finrom_fom_band_post_rec* post_rec) {
+  if (!fits || !fin_rec || !post_rec) { set_error("fom_band_mirror_records: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
+  std::vector<double> c; std::vector<int> pr, po;
+  const int f = derive_post_functionals(a, n_half, n_rows, c, pr, po);
+  if (f < 0) return f;
+  *fits = f;
+  if (!f) return 0;
+  std::vector<BandFinRec> fr; std::vector<BandPostRec> qr;
+  derive_pivot_records(a, c, pr, po, fr, qr);
+  if (int rc = check_pivot_records(a, c, pr, po, fr.data(), qr.data())) return rc;
+  std::copy(fr.begin(), fr.end(), fin_rec); std::copy(qr.begin(), qr.end(), post_rec);
+  return 0;
+}
+
+int finrom_fom_band_records_check(const finrom_fom_band_desc* a, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                  const int32_t* out_ptr, const int32_t* out_col, const finrom_fom_band_fin_rec* fin_rec,
+                                  const finrom_fom_band_post_rec* post_rec) {
+  if (!fin_rec || !post_rec) { set_error("fom_band_records_check: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_band_mirror(a, n_half, xdim, n_rows, n_obs, out_ptr, out_col, nullptr, nullptr)) return rc;
+  std::vector<double> c; std::vector<int> pr, po;
+  const int f = derive_post_functionals(a, n_half, n_rows, c, pr, po);
+  if (f < 0) return f;
+  if (!f) { set_error("fom_band_records_check: the descriptor does not fit the functional form"); return FINROM_ERR_ARG; }
+  return check_pivot_records(a, c, pr, po, fin_rec, post_rec);
 }
 
 }  // extern "C"

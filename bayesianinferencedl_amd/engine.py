@@ -355,6 +355,7 @@ class FomEngine:
         Otherwise nothing changes.  FINROM_NO_MIRROR=1 at engine creation switches the form off."""
         self.band_mirror = None
         self.band_mirror_form = 0
+        self.band_mirror_records = False
         if _os.environ.get("FINROM_NO_MIRROR") is not None or not self.band_qoi_only:
             return
         form = self.mirror_form(ops, self.xdim, c0_csr, W_csr, rhs, B_obs)
@@ -371,6 +372,9 @@ class FomEngine:
         # 2: the post's observation rows ride its forward sweep as functionals (no stored factor); 1: the stored-factor form --
         # a descriptor that does not fit the functional form, or FINROM_FOM_POST_STORED=1 at engine creation
         self.band_mirror_form = int(lib().finrom_fom_band_mirror_form(self._h))
+        # the functional form's sweeps read one prefetched record per pivot (FINROM_FOM_NO_PIVOT_RECORDS=1 at engine creation: the
+        # tables themselves, same bits)
+        self.band_mirror_records = bool(lib().finrom_fom_band_mirror_records_on(self._h))
 
     def solve(self, X, want_w=False):
         b = _Batch(X, self.xdim)

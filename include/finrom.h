@@ -282,6 +282,34 @@ int finrom_fom_band_mirror_functionals(const finrom_fom_band_desc* desc, int32_t
                                        int32_t* piv_off);
 /* 0: the handle has no half plan; 1: half plan with the post's factor stored; 2: half plan with the post as functionals. */
 int finrom_fom_band_mirror_form(finrom_fom_t h);
+/* Pivot records of the functional form: what its sweeps read per pivot -- nine tables of the descriptor and the derived ones above --
+ * gathered into one fixed-size record per ENTERING node, which the kernel requests with wide scalar loads two steps before it
+ * needs them.  Offsets are in BYTES into a sample block's workspace slice (slot << 9: 64 lanes of 8 bytes).
+ *   fin record k = f (npf + nif) + t: the three value slots of node t of fin f and qoi_FgQ of that node;
+ *   post record t < npost: node t's three value slots; gv = the slot its row's fin left g in (nAB + piv_off[t]) where t is an
+ *     interface node of a row's fin (row = piv_row[t] >= 0), else a slot the sweep may load and discard (the node's own first
+ *     entry); ent_extra[t], ecp_ptr[t] and [t + 1], qoi_FgQ, cw[5 t ..]; act = act[t - NSP] for t >= NSP, the pivot that
+ *     leaves the window as t enters it, 0 before;
+ *   post records npost .. npost + NSP - 1: act of the last NSP pivots, behind which nobody enters; everything else zero.
+ * finrom_fom_set_band_mirror installs them with the functional form unless FINROM_FOM_NO_PIVOT_RECORDS=1 is in the environment of
+ * the set call (the sweep then reads the tables themselves; same results bit for bit).  finrom_fom_solve sweeps on them at every
+ * batch size; finrom_solve_pairs where its FOM half runs on the CU-masked stream (batches of 16 384 samples and more beside the
+ * one-wave projection), and on the tables otherwise.  The records are checked like every derived
+ * table: the source tables rebuilt from them, entry by entry (finrom_fom_band_records_check does the same for records a caller
+ * hands in).  finrom_fom_band_mirror_records (host only): *fits as for finrom_fom_band_mirror_functionals; fin_rec takes
+ * nfins (npf + nif) records, post_rec npost + NSP. */
+typedef struct { int32_t off[3]; int32_t pad0; double fg; double pad1; } finrom_fom_band_fin_rec;                    /* 32 bytes */
+typedef struct { int32_t off[3]; int32_t gv; int32_t ex, act, c0, c1; int32_t row, pad0; double fg; double cw[5]; double pad1; } finrom_fom_band_post_rec;   /* 96 bytes */
+int finrom_fom_band_mirror_records(const finrom_fom_band_desc* desc, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                   const int32_t* out_ptr, const int32_t* out_col, int32_t* fits, finrom_fom_band_fin_rec* fin_rec,
+                                   finrom_fom_band_post_rec* post_rec);
+/* Host only: 0 if the records are the ones the (validated) descriptor's tables give, FINROM_ERR_ARG and a message naming the
+ * field otherwise. */
+int finrom_fom_band_records_check(const finrom_fom_band_desc* desc, int32_t n_half, int32_t xdim, int32_t n_rows, int32_t n_obs,
+                                  const int32_t* out_ptr, const int32_t* out_col, const finrom_fom_band_fin_rec* fin_rec,
+                                  const finrom_fom_band_post_rec* post_rec);
+/* 1: the handle's half plan sweeps on pivot records; 0: it reads the tables (or there is no functional form). */
+int finrom_fom_band_mirror_records_on(finrom_fom_t h);
 
 /* The adjoint gradient on the band sweep's layout (finrom_fom_gradient for batches beyond the small-batch schedule): after the
  * full sweep the workspace holds the factor and w; A v = -B_obs^T (B_obs w - d) is solved with the stored columns (one forward
