@@ -15,11 +15,15 @@ def _factor(n, seed):
     return U
 
 
-@pytest.mark.parametrize("n,S", [(130, 4096), (148, 4100), (300, 4357), (517, 5000), (1597, 4200)])
+@pytest.mark.parametrize("n,S", [(130, 4096), (148, 4100), (300, 4357), (517, 5000), (1597, 4200), (2050, 4100)])
 def test_throughput_sampler_kernel_matches_numpy_and_the_small_kernel_bit_for_bit(n, S, monkeypatch):
-    """n = 130 / 148 / 300 / 517 / 1597: the last column tile holds 2 / 20 / 44 / 5 / 61 live columns (one, two, three, one, four
-    live 16-column MFMA tiles on the first wave column, none on the second); S not a multiple of 256 nor of 1024: partial sample
-    tiles and a partial sample group; several column groups at n = 1597 (13 column tiles: groups of 8 and 5)."""
+    """n = 130 / 148 / 300 / 517 / 1597 / 2050: the last column tile holds 2 / 20 / 44 / 5 / 61 / 2 live columns (one, two, three,
+    one, four, one live 16-column MFMA tiles on the first wave column, none on the second); S not a multiple of 256 nor of 1024:
+    partial sample tiles and a partial sample group; several column groups at n = 1597 (13 column tiles: groups of 8 and 5).
+    FINROM_SAMPLER_NO_PAD differs from the default launch only from n >= 1921: a column group runs to its top tile's K end only when
+    that end, (top + 1) * 128, reaches 2048.  Below, the two launches are the same and their comparison says nothing; n = 2050 (17
+    column tiles: the top group of 8 padded, the next not, the lone tile 0) is the size at which it compares the padded lockstep with
+    tiles that each stop at their own K end.  tests/test_gpu_util_kernels.py checks that path at every element with exact sums."""
     import torch
     from bayesianinferencedl_amd.engine import FieldSampler
     dev = torch.device("cuda", torch.cuda.current_device())
