@@ -97,6 +97,13 @@ class HmcStats(C.Structure):
                 ("misfit", C.c_void_p), ("accepted", C.c_void_p)]
 
 
+class HmcDa(C.Structure):
+    _fields_ = [("n_obs", C.c_int32), ("data_per_sample", C.c_int32), ("ok1", C.c_void_p), ("Uq", C.c_void_p),
+                ("qoi_f", C.c_void_p), ("info_f", C.c_void_p), ("data", C.c_void_p), ("lu2_block", C.c_void_p),
+                ("D", C.c_void_p), ("loss_f", C.c_void_p), ("accept1", C.c_void_p), ("cand_loss_f", C.c_void_p),
+                ("correction", C.c_void_p)]
+
+
 class LbfgsState(C.Structure):
     _fields_ = [("S", C.c_int64), ("d", C.c_int32), ("m", C.c_int32), ("ftol", C.c_double), ("gtol", C.c_double),
                 ("maxiter", C.c_int64), ("maxfun", C.c_int64), ("maxls", C.c_int32), ("lo", C.c_void_p), ("hi", C.c_void_p),
@@ -215,6 +222,9 @@ SIGNATURES = {
     "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
     "finrom_hmc_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_stats_update": (C.c_int, [C.POINTER(HmcStats), C.c_void_p]),
+    "finrom_hmc_end_stage1": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_end_stage2": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.POINTER(HmcDa), C.c_void_p]),
+    "finrom_hmc_draw_stage2": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_lbfgs_begin": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_propose": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p]),
     "finrom_lbfgs_accept": (C.c_int, [C.POINTER(LbfgsState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -52,7 +52,21 @@ through one adapter per model (the calls of estimate_MAP.objective(kind).device)
 _field_fom / _rom, built from two model-agnostic kernels (finrom_hmc_drift, finrom_hmc_kick).  The plain reduced model sees the
 field only through its sub-fin averages, so under a prior its fused step stays in whitened coordinates: theta = Sop m + (Sop U^T) v,
 grad_v = (Sop U^T)^T g_theta, no triangular product and no field during a trajectory.  `fom_value_and_grad` / `rom_value_and_grad`
-are the host callables for run_chains.  model="romml" (the default): every path, launch and bit as before."""
+are the host callables for run_chains.  model="romml" (the default): every path, launch and bit as before.
+
+`correct=` on the three chain functions: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under
+a surrogate -- model="romml" or "rom" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway,
+under the surrogate's Hamiltonian; the end point then gets ONE full-order forward solve (QoI only: no adjoint, no gradient), and
+stage 2 accepts a candidate that passed stage 1 with probability min(1, w(k') / w(k)), w = exp(-D), D = c_lik (loss_FOM -
+loss_surrogate).  The priors cancel in w; stage 1 is reversible for the surrogate's posterior, so the two stages together are
+reversible for the full-order posterior (the one the reference samples, pymc_func_bayes_inverse.py:174) at one forward solve per
+proposal instead of n_leapfrog value-and-gradient calls.  run_chains takes a callable (fom_value(Fin, data)) and is the NumPy
+statement; the device functions take the Fin.  Lockstep solves all C end points, also those stage 1 stopped.  The second uniform is
+one more draw of the chain's generator per proposal (rng="numpy") or Philox counter word 2 (philox.draw_block_stage2,
+finrom_hmc_draw_stage2).  The result gains accept1 [C] (proposals past stage 1; accept is the final count), correction
+[proposals + 1, C] (row 0 the start's D, row q the candidate's: the surrogate's log-likelihood error along the chain) and n_fom;
+stats= records the full-order misfit.  Not with model="fom", not with ChainStats(resume=...); the fused form has no metric form.
+correct=None: every path, launch and bit as before."""
 from __future__ import annotations
 
 import numpy as np
@@ -291,6 +305,63 @@ class _DeviceStats:
         return h
 
 
+class _DeviceDA:
+    """The buffers of delayed acceptance (finrom_hmc_end_stage1 / _stage2, finrom_hmc_draw_stage2) as torch tensors on `dev`, and the
+    full-order solve between the two stages: `fin`'s "field" engine, QoI only."""
+
+    def __init__(self, fin, Cn, n, data_t, per_sample, B, n_prop, dev):
+        import torch
+        from .. import _ffi
+        self._ffi, self._L, self.C, self.n_prop, self.data_t = _ffi, _ffi.lib(), Cn, n_prop, data_t
+        self.fom = fin._engine("field")
+        if self.fom.xdim != n:
+            raise ValueError(f"correct=: the full-order model takes fields of {self.fom.xdim} nodes, the chains have {n}")
+        if data_t.shape[-1] != self.fom.n_obs:
+            raise ValueError(f"correct=: the full-order model observes {self.fom.n_obs} values, data has {data_t.shape[-1]}")
+        f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+        self.ok1, self.Uq = torch.zeros(Cn, **i32), torch.zeros(Cn, **f64)
+        self.qoi, self.info = torch.zeros(Cn, self.fom.n_obs, **f64), torch.zeros(Cn, **i32)
+        self.lu2 = torch.zeros(B, Cn, **f64)
+        self.D, self.loss_f, self.cand = torch.zeros(Cn, **f64), torch.zeros(Cn, **f64), torch.zeros(Cn, **f64)
+        self.accept1 = torch.zeros(Cn, dtype=torch.int64, device=dev)
+        self.correction = torch.full((n_prop + 1, Cn), float("nan"), **f64)
+        self.desc = _ffi.HmcDa(n_obs=self.fom.n_obs, data_per_sample=per_sample, ok1=self.ok1.data_ptr(), Uq=self.Uq.data_ptr(),
+                               qoi_f=self.qoi.data_ptr(), info_f=self.info.data_ptr(), data=data_t.data_ptr(),
+                               lu2_block=self.lu2.data_ptr(), D=self.D.data_ptr(), loss_f=self.loss_f.data_ptr(),
+                               accept1=self.accept1.data_ptr(), cand_loss_f=self.cand.data_ptr(), correction=self.correction.data_ptr())
+
+    def buffers(self):
+        """Everything stage 2 writes: saved before a warm-up proposal and restored after the capture, with the chain state."""
+        return [self.D, self.loss_f, self.accept1, self.correction, self.cand]
+
+    def solve(self, field):
+        """qoi, info <- the full-order model at field [C, n] (a contiguous float64 device tensor), on torch's current stream: the
+        flags cleared (the solve flags into them), then ONE finrom_fom_solve without w."""
+        import torch
+        assert field.is_contiguous() and field.dtype == torch.float64 and field.shape[0] == self.C
+        self.info.zero_()
+        self._ffi.check(self._L.finrom_fom_solve(self.fom._h, field.data_ptr(), self.C, self.qoi.data_ptr(), None, self.info.data_ptr(),
+                                                 torch.cuda.current_stream().cuda_stream), "finrom_fom_solve")
+
+    def misfit(self):
+        r = self.qoi - self.data_t
+        return (r * r).sum(dim=1).mul_(0.5)
+
+    def start(self, field, loss_s, c_lik):
+        """Evaluation 0 of the correcting model: loss_f, D = c_lik (loss_f - loss_s) and row 0 of `correction` (also warms the
+        full-order workspace up before a capture).  ValueError for a flagged or non-finite start."""
+        import torch
+        self.solve(field)
+        lossF = self.misfit()
+        D = (lossF - loss_s).mul_(c_lik)
+        if bool(self.info.ne(0).any()) or not bool(torch.isfinite(lossF).all()) or not bool(torch.isfinite(D).all()):
+            raise ValueError("HMC start point: the correcting model is flagged or not finite there")
+        self.loss_f.copy_(lossF); self.D.copy_(D); self.correction[0].copy_(D)
+
+    def result(self):
+        return dict(accept1=self.accept1.cpu().numpy(), correction=self.correction.cpu().numpy(), n_fom=self.n_prop + 1)
+
+
 def potential(loss, grad, K, mean, sigma, tau):
     """U(k) = loss(k) / sigma^2 + |k - mean|^2 / (2 tau^2) and its gradient, row-wise for a batch K [C, n]."""
     d = K - mean
@@ -330,18 +401,34 @@ def _check_rng(rng, seeds, proposal0, who):
     return philox.check_seeds(seeds)
 
 
-def _device_draw(seeds64, dev):
+def _device_draw(seeds64, dev, stage2=False):
     """draw(first, nb, P_dev, lu_dev): one finrom_hmc_draw launch on the current stream -- the draws of proposals first .. first + nb - 1
-    of every chain into the head of the block buffers.  The seeds sit in an int64 tensor that holds the uint64 bit patterns."""
+    of every chain into the head of the block buffers.  The seeds sit in an int64 tensor that holds the uint64 bit patterns.
+    stage2: draw2(first, nb, lu2_dev) instead -- one finrom_hmc_draw_stage2 launch, the second log-uniforms (correct=)."""
     import torch
     from .. import _ffi
     L = _ffi.lib()
     seeds_t = torch.as_tensor(seeds64.view(np.int64), dtype=torch.int64, device=dev)
+    if stage2:
+        def draw2(first, nb, lu2_dev):
+            _ffi.check(L.finrom_hmc_draw_stage2(seeds_t.data_ptr(), seeds_t.numel(), first, nb, lu2_dev.data_ptr(),
+                                                torch.cuda.current_stream().cuda_stream), "finrom_hmc_draw_stage2")
+        return draw2
 
     def draw(first, nb, P_dev, lu_dev):
         _ffi.check(L.finrom_hmc_draw(seeds_t.data_ptr(), seeds_t.numel(), P_dev.shape[2], first, nb, P_dev.data_ptr(), lu_dev.data_ptr(),
                                      torch.cuda.current_stream().cuda_stream), "finrom_hmc_draw")
     return draw
+
+
+def _check_correct(correct, stats, who, model=None):
+    """Delayed acceptance corrects a surrogate, and this version does not continue its sums."""
+    if correct is None:
+        return
+    if model == "fom":
+        raise ValueError(f"{who}: correct= with model='fom': the chains already run under the full-order model, there is nothing to correct")
+    if stats is not None and stats.resume is not None:
+        raise ValueError(f"{who}: correct= with ChainStats(resume=...) is not supported (start the sums anew, with a burn >= proposal0)")
 
 
 def _check_metric(metric, n):
@@ -354,7 +441,7 @@ def _check_metric(metric, n):
 
 
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None):
+               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None, correct=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
@@ -371,10 +458,16 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     proposal0=p1 and the first run's mean passed explicitly, is the uninterrupted run.  proposal0 != 0 needs rng="philox".
     stats: None or a ChainStats (module docstring): `stats` of the result is then the started ChainStats of this run -- the moments
     of the chains' FIELDS after every proposal with global index >= burn, misfit and accept flag per proposal.
+    correct: None, or f(K [C, n] fields) -> (loss [C], bad [C]) of the model the chain is to be exact for (fom_value): delayed
+    acceptance, the NumPy statement of finrom_hmc_end_stage2 (module docstring).  The start and every trajectory's end point are
+    evaluated by it; the second uniform is one more uniform() of the chain's generator behind the first (rng="numpy"; drawn for
+    every proposal, whatever stage 1 said) or philox.draw_block_stage2's.  The result gains accept1, correction, n_fom and stage
+    [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted); stats' misfit is `correct`'s.
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
     trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
     with a prior also V [C, n], the whitened final states)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains")
+    _check_correct(correct, stats, "run_chains")
     _check_prior(prior, mean, "run_chains")
     metric = _check_metric(metric, np.shape(K0)[-1])
     K = np.array(K0, dtype=np.float64, copy=True)
@@ -416,7 +509,17 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     trace = [K.copy()] if keep_trace else None
     accept = np.zeros(C, np.int64)
     proposals = 0
-    cs = None if stats is None else stats.begin(last["field"], last["loss"], proposal0, max(0, (n_evals - 1) // n_leapfrog))
+    if correct is not None:                                          # delayed acceptance: D = c_lik (loss_FOM - loss_surrogate) at the start
+        c_lik = 1.0 / sigma ** 2
+        loss_f, bad_f = correct(last["field"])
+        loss_f = np.array(loss_f, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            D = c_lik * (loss_f - np.asarray(last["loss"], dtype=np.float64))
+        if np.any(bad_f) or not np.all(np.isfinite(loss_f)) or not np.all(np.isfinite(D)):
+            raise ValueError("HMC start point: the correcting model is flagged or not finite there")
+        accept1, correction, stage = np.zeros(C, np.int64), [D.copy()], []
+    cs = None if stats is None else stats.begin(last["field"], last["loss"] if correct is None else loss_f, proposal0,
+                                                max(0, (n_evals - 1) // n_leapfrog))
     while evals + n_leapfrog <= n_evals:
         if seeds64 is None:
             P = np.stack([r.standard_normal(n) for r in rngs])
@@ -436,18 +539,34 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         with np.errstate(over="ignore", invalid="ignore"):
             lu = np.log(np.array([r.uniform() for r in rngs])) if seeds64 is None else lub[0]
             ok = np.isfinite(H1) & (lu < H0 - H1)
+            if correct is not None:                                  # stage 2 (finrom_hmc_end_stage2's rule)
+                lu2 = (np.log(np.array([r.uniform() for r in rngs])) if seeds64 is None
+                       else philox.draw_block_stage2(seeds64, proposal0 + proposals, 1)[0])
+                ok1 = ok
+                cand_f, bad_f = correct(last["field"])
+                cand_f = np.asarray(cand_f, dtype=np.float64)
+                Dq = c_lik * (cand_f - np.asarray(last["loss"], dtype=np.float64))
+                good = ~np.asarray(bad_f, dtype=bool) & (np.abs(cand_f) <= 1.7e308) & np.isfinite(Dq)
+                ok = ok1 & good & (lu2 < D - Dq)
+                D, loss_f = np.where(ok, Dq, D), np.where(ok, cand_f, loss_f)
+                accept1 += ok1
+                correction.append(np.where(good, Dq, np.nan))
+                stage.append(ok1.astype(np.int8) + ok)
         K = np.where(ok[:, None], Kq, K); U = np.where(ok, Uq, U); dU = np.where(ok[:, None], dUq, dU)
         accept += ok
         if cs is not None:                                           # (the last evaluation was the end point's)
-            cs.update(last["field"], np.asarray(last["loss"], dtype=np.float64), ok, proposal0 + proposals)
+            cs.update(last["field"], np.asarray(last["loss"], dtype=np.float64) if correct is None else np.where(good, cand_f, np.nan),
+                      ok, proposal0 + proposals)
         proposals += 1
         if keep_trace:
             trace.append(K.copy())
+    da = {} if correct is None else dict(accept1=accept1, correction=np.stack(correction), n_fom=proposals + 1,
+                                         stage=np.array(stage, dtype=np.int8).reshape(proposals, C))
     if prior is not None:                                            # the states are v: report fields, and v beside them
         return HmcResult(K=prior.field(K), V=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
-                         trace=prior.field(np.stack(trace)) if keep_trace else None, stats=cs)
+                         trace=prior.field(np.stack(trace)) if keep_trace else None, stats=cs, **da)
     return HmcResult(K=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
-                     trace=np.stack(trace) if keep_trace else None, stats=cs)
+                     trace=np.stack(trace) if keep_trace else None, stats=cs, **da)
 
 
 def romml_value_and_grad(solver_r):
@@ -466,6 +585,18 @@ def fom_value_and_grad(solver, data):
     def f(K):
         res = solver.gradient_batch(np.ascontiguousarray(K, dtype=np.float64), data)
         return np.asarray(res["J"]), np.asarray(res["grad"]), np.asarray(res["info"]) != 0
+    return f
+
+
+def fom_value(solver, data):
+    """The full-order misfit alone, batched over chains: f(K [C, n] fields) -> (loss [C], bad [C]) from Fin.forward_batch without w
+    (one forward solve, no adjoint).  The callable run_chains(..., correct=) takes."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+
+    def f(K):
+        res = solver.forward_batch(np.ascontiguousarray(K, dtype=np.float64), want_w=False)
+        r = np.asarray(res["qoi"]) - data
+        return 0.5 * np.einsum("co,co->c", r, r), np.asarray(res["info"]) != 0
     return f
 
 
@@ -522,7 +653,7 @@ def _device_model(model, solver_r, solver, data_t):
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None, model="romml", solver=None):
+                     stats=None, model="romml", solver=None, correct=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -544,9 +675,16 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     launches, kick kernel), under a prior finrom_hmc_leapfrog_field_fom; "rom" -- finrom_hmc_leapfrog_rom for both priors: A = Sop
     under the i.i.d. prior, A = Sop U^T and theta0 = Sop mean in whitened coordinates, where no field exists during a trajectory
     (stats= adds one finrom_sampler_field launch on the end point per proposal; recorded evaluations form field and field-space
-    gradient step by step).  No metric forms (FINROM_ERR_UNSUPPORTED: fused=None falls back)."""
+    gradient step by step).  No metric forms (FINROM_ERR_UNSUPPORTED: fused=None falls back).
+    correct: a Fin (model "romml" or "rom") -- delayed acceptance: finrom_hmc_end_stage1 in the place of finrom_hmc_end, then one
+    finrom_sampler_field launch on the end point for the whitened plain ROM alone (shared with stats=), finrom_fom_solve without w
+    on the "field" engine at the candidate's field (Kq[n_leapfrog & 1], or the step's field buffer under a prior; its flags cleared
+    in front), finrom_hmc_end_stage2, and the stats launch with the full-order misfit: still one linear chain, captured once.  The
+    start point's solve warms the full-order workspace before the capture; under "philox" one finrom_hmc_draw_stage2 launch per
+    block sits beside finrom_hmc_draw, under "numpy" a third uploaded block carries the second uniforms.  No metric form."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
     _check_model(model, solver_r, solver, data, "run_chains_fused")
+    _check_correct(correct, stats, "run_chains_fused", model)
     import ctypes as C
     import torch
     from .. import _ffi
@@ -571,6 +709,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if metric is not None and model != "romml":
         raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog steps of model={model!r} "
                                "have no metric form (pass fused=False)")
+    if metric is not None and correct is not None:
+        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): delayed acceptance (correct=) has no metric "
+                               "form of the fused step (pass fused=False)")
     K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
     Cn, n = K.shape
     if prior is not None:                                            # whitened: N(0, I), c_pri = 1
@@ -618,6 +759,11 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                        info=info.data_ptr())
     st0 = _ffi.HmcState.from_buffer_copy(st)                         # evaluation 0: a "step" of length zero from K itself
     st0.eps = 0.0
+    da = None
+    if correct is not None:                                          # delayed acceptance: the buffers of finrom_hmc_end_stage1 / _stage2
+        da = _DeviceDA(correct, Cn, n, data_t, per_sample, B, n_prop, dev)
+        if seeds64 is not None:
+            draw2 = _device_draw(seeds64, dev, stage2=True)
 
     def stream():
         return torch.cuda.current_stream().cuda_stream
@@ -683,12 +829,19 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                 note(i)
         if metric is not None:
             _ffi.check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
+        elif da is not None:                                         # the surrogate's test, the full-order model at the end point, its test
+            _ffi.check(L.finrom_hmc_end_stage1(C.byref(st), n_leapfrog, da.ok1.data_ptr(), da.Uq.data_ptr(), stream()),
+                       "finrom_hmc_end_stage1")
+            if whitened_rom:                                         # (no step formed the field; the sums below share it)
+                field_of(Kq[n_leapfrog & 1])
+            da.solve(F if prior is not None else Kq[n_leapfrog & 1])
+            _ffi.check(L.finrom_hmc_end_stage2(C.byref(st), n_leapfrog, C.byref(da.desc), stream()), "finrom_hmc_end_stage2")
         else:
             _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
         if ds is not None:                                           # (F holds the field of the trajectory's last step: the end point's)
-            if whitened_rom:                                         # (no step formed it: the end point's field, for the sums alone)
+            if whitened_rom and da is None:                          # (no step formed it: the end point's field, for the sums alone)
                 field_of(Kq[n_leapfrog & 1])
-            ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss)
+            ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss if da is None else da.cand)
 
     # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
     Kq[0].copy_(K)
@@ -703,12 +856,15 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if trace is not None:
         trace[0].copy_(K)
     _restore_chain(stats, K, U, dU)
-    if whitened_rom and stats is not None:                           # the start point's field (also the field kernel's workspace, before a capture)
+    if whitened_rom and (stats is not None or da is not None):      # the start point's field (also the field kernel's workspace, before a capture)
         field_of(K)
-    ds = None if stats is None else _DeviceStats(stats, F if prior is not None else K, loss, proposal0, n_prop, pt, acc)
+    if da is not None:                                               # evaluation 0 of the full-order model (warms its workspace up)
+        da.start(F if prior is not None else K, loss, c_lik)
+    ds = None if stats is None else _DeviceStats(stats, F if prior is not None else K, loss if da is None else da.loss_f, proposal0,
+                                                 n_prop, pt, acc)
     g = None
     if graph and n_prop > 0:
-        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else [])
+        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else []) + (da.buffers() if da is not None else [])
         state = [t.clone() for t in moved]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -727,14 +883,20 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         nb = min(B, n_prop - done)
         if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
             draw(proposal0 + done, nb, P_dev, lu_dev)
+            if da is not None:
+                draw2(proposal0 + done, nb, da.lu2)
         else:
-            P_host, lu_host = np.zeros((B, Cn, n)), np.zeros((B, Cn))
+            P_host, lu_host, lu2_host = np.zeros((B, Cn, n)), np.zeros((B, Cn)), np.zeros((B, Cn))
             for j in range(nb):                                     # the host chain's draws, in its order
                 for c_, r in enumerate(rngs):
                     P_host[j, c_] = r.standard_normal(n)
                 with np.errstate(divide="ignore"):
                     lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
+                    if da is not None:                              # (the second uniform, behind the first, for every proposal)
+                        lu2_host[j] = np.log(np.array([r.uniform() for r in rngs]))
             P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
+            if da is not None:
+                da.lu2.copy_(torch.from_numpy(lu2_host))
         jt.zero_()
         for j in range(nb):
             first = 1 + (done + j) * n_leapfrog
@@ -746,10 +908,13 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                 evals += n_leapfrog
         done += nb
     cs = ds.result(K, U, dU) if ds is not None else None
+    more = da.result() if da is not None else {}
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs, model=model)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs, model=model,
+                             **more)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs, model=model)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs, model=model,
+                     **more)
 
 
 def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
@@ -764,7 +929,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0, stats=None, model="romml", solver=None):
+                      proposal0=0, stats=None, model="romml", solver=None, correct=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -797,9 +962,16 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     with another model.  `model` of the result names it.
     Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates (model=
     "fom": fom_value_and_grad(solver, data); "rom": rom_value_and_grad(solver_r, data)).
+    correct: a Fin, with model "romml" or "rom" (ValueError with "fom", and with ChainStats(resume=...)) -- delayed acceptance
+    (module docstring): the trajectory under the surrogate, one full-order forward solve at its end point, the second test.
+    Fused: run_chains_fused's launches (no metric form: fused=None then takes this one); here the rule of finrom_hmc_end_stage2 in
+    torch ops around correct.forward_batch(field, want_w=False) on device tensors, which serves metric= too.  Same chains as
+    run_chains(..., correct=fom_value(correct, data)).  The result gains accept1 [C], correction [proposals + 1, C] (row 0: the
+    start's D, row q: the candidate's) and n_fom = proposals + 1; stats' misfit is the full-order one.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
     _check_model(model, solver_r, solver, data, "run_chains_device")
+    _check_correct(correct, stats, "run_chains_device", model)
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
@@ -809,7 +981,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver)
+                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver,
+                                    correct=correct)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -846,6 +1019,19 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     acc = torch.zeros(C, dtype=torch.int64, device=dev)
     trace = torch.zeros(n_prop + 1, C, n, **f64) if keep_trace else None
     out = {}
+    da = None
+    if correct is not None:                                          # delayed acceptance: finrom_hmc_end_stage2's state and rule in torch ops
+        da = _DeviceDA(correct, C, n, data_t, 1 if data_t.ndim == 2 else 0, B, n_prop, dev)
+        lu2 = torch.zeros(1, C, **f64)
+        nan_c = torch.full((C,), float("nan"), **f64)
+        if seeds64 is not None:
+            draw2 = _device_draw(seeds64, dev, stage2=True)
+
+    def fom_misfit(Fq):
+        """(loss_f [C], flagged [C]) of the correcting model at the fields Fq: one forward solve, no adjoint."""
+        res = correct.forward_batch(Fq, want_w=False)
+        r = res["qoi"] - data_t
+        return (r * r).sum(dim=1).mul_(0.5), res["info"].ne(0)
 
     def evaluate():
         """dUq (= grad U / c_pri), out <- value and gradient at Kq (all static tensors: the same buffers at every call once captured)."""
@@ -892,13 +1078,24 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         Uq = potential_now()
         H1 = torch.add(Uq, torch.linalg.vecdot(Pq, Pq) if mh is None else mh.apply(Pq, "inv", want_quad=True)[1], alpha=0.5)
         ok = lu[0] < H0 - H1                                        # (H1 = inf or nan compares false, as on the host: rejected)
+        if da is not None:                                          # stage 2: the full-order misfit at the end point decides
+            torch.index_select(da.lu2, 0, jt, out=lu2)
+            lossF, flagged = fom_misfit(out["field"])
+            Dq = (lossF - out["loss"]).mul_(c_lik)
+            good = ~flagged & (lossF.abs() <= 1.7e308) & torch.isfinite(Dq)
+            da.accept1.add_(ok)
+            ok = ok & good & (lu2[0] < da.D - Dq)
+            torch.where(ok, Dq, da.D, out=da.D); torch.where(ok, lossF, da.loss_f, out=da.loss_f)
+            torch.where(good, lossF, nan_c, out=da.cand)
         torch.where(ok[:, None], Kq, K, out=K); torch.where(ok, Uq, U, out=U); torch.where(ok[:, None], dUq, dU, out=dU)
         acc.add_(ok)
         jt.add_(1); pt.add_(1)
         if trace is not None:
             trace.index_copy_(0, pt, K[None])
+        if da is not None:
+            da.correction.index_copy_(0, pt, torch.where(good, Dq, nan_c)[None])
         if ds is not None:                                          # (out holds the last evaluation: the end point's)
-            ds.update(out["field"], out["loss"])
+            ds.update(out["field"], out["loss"] if da is None else da.cand)
 
     Kq.copy_(K); Pq.zero_()
     evaluate()                                                      # evaluation 0: the starting point (also warms the library up)
@@ -910,10 +1107,16 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     if trace is not None:
         trace[0].copy_(K)
     _restore_chain(stats, K, U, dU)
-    ds = None if stats is None else _DeviceStats(stats, out["field"], out["loss"], proposal0, n_prop, pt, acc)
+    if da is not None:                                               # evaluation 0 of the correcting model
+        lossF, flagged = fom_misfit(out["field"])
+        D0 = (lossF - out["loss"]).mul_(c_lik)
+        if bool(flagged.any()) or not bool(torch.isfinite(lossF).all()) or not bool(torch.isfinite(D0).all()):
+            raise ValueError("HMC start point: the correcting model is flagged or not finite there")
+        da.loss_f.copy_(lossF); da.D.copy_(D0); da.correction[0].copy_(D0)
+    ds = None if stats is None else _DeviceStats(stats, out["field"], out["loss"] if da is None else da.loss_f, proposal0, n_prop, pt, acc)
     g = None
     if graph and n_prop > 0:
-        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else [])
+        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else []) + (da.buffers() if da is not None else [])
         state = [t.clone() for t in moved]
         try:
             side = torch.cuda.Stream()
@@ -937,14 +1140,20 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         nb = min(B, n_prop - done)
         if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
             draw(proposal0 + done, nb, P_dev, lu_dev)
+            if da is not None:
+                draw2(proposal0 + done, nb, da.lu2)
         else:
-            P_host, lu_host = np.zeros((B, C, n)), np.zeros((B, C))
+            P_host, lu_host, lu2_host = np.zeros((B, C, n)), np.zeros((B, C)), np.zeros((B, C))
             for j in range(nb):                                     # the host chain's draws, in its order (overlaps the device's
                 for c_, r in enumerate(rngs):                       #  work on the previous block: nothing here waits for it)
                     P_host[j, c_] = r.standard_normal(n)
                 with np.errstate(divide="ignore"):
                     lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
+                    if da is not None:                              # (the second uniform, behind the first, for every proposal)
+                        lu2_host[j] = np.log(np.array([r.uniform() for r in rngs]))
             P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
+            if da is not None:
+                da.lu2.copy_(torch.from_numpy(lu2_host))
         jt.zero_()
         for j in range(nb):
             first = 1 + (done + j) * n_leapfrog                     # evaluation indices of this proposal: first .. first + L - 1
@@ -956,7 +1165,10 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
                 evals += n_leapfrog
         done += nb
     cs = ds.result(K, U, dU) if ds is not None else None
+    more = da.result() if da is not None else {}
     if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs, model=model)
+        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs, model=model,
+                             **more)
     return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs, model=model)
+                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs, model=model,
+                     **more)

@@ -4,7 +4,8 @@ hmc_draw_kernel) draws on the device, restated for the host recursion `hmc.run_c
 For the chain with seed s (0 <= s < 2^64) and GLOBAL proposal index p, Philox4x32-10 (Salmon et al., SC'11) with key (s lo, s hi):
   * momentum: counter (p lo, p hi, pair index jb, 0); the output words (o1 o0) and (o3 o2) give two 53-bit uniforms u1 in (0, 1] and
     u2 in [0, 1), and Box-Muller turns them into the standard normals xi[2 jb], xi[2 jb + 1] (for odd n the last pair gives one);
-  * Metropolis uniform: counter (p lo, p hi, 0, 1); a = (o1 << 32) | o0, u = ((a >> 11) + 1) 2^-53 in (0, 1], lu = log u <= 0, finite.
+  * Metropolis uniform: counter (p lo, p hi, 0, 1); a = (o1 << 32) | o0, u = ((a >> 11) + 1) 2^-53 in (0, 1], lu = log u <= 0, finite;
+  * second-stage uniform (hmc.py correct=, finrom_hmc_draw_stage2): counter (p lo, p hi, 0, 2), the same conversion.
 A draw depends on (s, p) and on nothing else: a chain is the same for any block size, any deal of the chains over ranks, and for a
 run continued from its end state at the proposal index it stopped at."""
 from __future__ import annotations
@@ -79,6 +80,21 @@ def draw_block(seeds, first, B, n):
     a = ((o[1] << _S32) | o[0])[..., 0]
     lu = np.log(((a >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53)
     return np.ascontiguousarray(P[..., :n]), lu
+
+
+def draw_block_stage2(seeds, first, B):
+    """The SECOND log-uniforms of proposals first .. first + B - 1 for the chains with `seeds` [C]: lu2 [B, C], what
+    finrom_hmc_draw_stage2 writes (hmc.py correct=: the second stage's test).  Counter (p lo, p hi, 0, 2), the conversion of
+    draw_block's log-uniform: finite and <= 0, a function of (seed, p) alone."""
+    B = int(B)
+    if B < 0:
+        raise ValueError("draw_block_stage2: B < 0")
+    k0, k1, p_lo, p_hi = _words(seeds, first, B)
+    shape = (B, k0.shape[1], 1)
+    o = philox4x32_10([np.broadcast_to(p_lo, shape), np.broadcast_to(p_hi, shape), np.zeros(shape, np.uint64),
+                       np.full(shape, 2, np.uint64)], k0, k1)
+    a = ((o[1] << _S32) | o[0])[..., 0]
+    return np.log(((a >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53)
 
 
 def momentum(seed, p, n):

@@ -1829,6 +1829,41 @@ int finrom_hmc_draw(const uint64_t* seeds, int64_t C, int32_t n, int64_t first_p
   }
   return launch_hmc_draw((const unsigned long long*)seeds, C, n, first_proposal, B, P_block, lu_block, (hipStream_t)stream);
 }
+int finrom_hmc_end_stage1(const finrom_hmc_state* a, int32_t n_steps, int32_t* ok1, double* Uq, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_end_stage1")) return rc;
+  if (n_steps < 0) { set_error("hmc_end_stage1: n_steps < 0"); return FINROM_ERR_ARG; }
+  if (h.C == 0) return 0;
+  if (!ok1 || !Uq) { set_error("hmc_end_stage1: null ok1 or Uq"); return FINROM_ERR_ARG; }
+  return launch_hmc_end_stage1(h, a->Kq[n_steps & 1], ok1, Uq, (hipStream_t)stream);
+}
+int finrom_hmc_end_stage2(const finrom_hmc_state* a, int32_t n_steps, const finrom_hmc_da* da, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_end_stage2")) return rc;
+  if (n_steps < 0) { set_error("hmc_end_stage2: n_steps < 0"); return FINROM_ERR_ARG; }
+  if (!da) { set_error("hmc_end_stage2: null descriptor"); return FINROM_ERR_ARG; }
+  if (da->n_obs < 1) { set_error("hmc_end_stage2: n_obs < 1"); return FINROM_ERR_ARG; }
+  if (h.C == 0) return 0;
+  if (!da->ok1 || !da->Uq || !da->qoi_f || !da->info_f || !da->data || !da->lu2_block || !da->D || !da->loss_f || !da->accept1 ||
+      !da->cand_loss_f) {
+    set_error("hmc_end_stage2: null pointer in finrom_hmc_da (only correction may be NULL)"); return FINROM_ERR_ARG;
+  }
+  return launch_hmc_end_stage2(h, a->Kq[n_steps & 1], *da, (hipStream_t)stream);
+}
+int finrom_hmc_draw_stage2(const uint64_t* seeds, int64_t C, int64_t first_proposal, int64_t B, double* lu2_block, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  if (C < 0) { set_error("hmc_draw_stage2: C < 0"); return FINROM_ERR_ARG; }
+  if (B < 0) { set_error("hmc_draw_stage2: B < 0"); return FINROM_ERR_ARG; }
+  if (first_proposal < 0) { set_error("hmc_draw_stage2: first_proposal < 0"); return FINROM_ERR_ARG; }
+  if (B == 0 || C == 0) return 0;
+  if (!seeds || !lu2_block) { set_error("hmc_draw_stage2: null seeds or lu2_block"); return FINROM_ERR_ARG; }
+  if (B > INT64_MAX / 8 / C || first_proposal > INT64_MAX - B) {
+    set_error("hmc_draw_stage2: B x C or first_proposal + B does not fit 64 bits"); return FINROM_ERR_ARG;
+  }
+  return launch_hmc_draw_stage2((const unsigned long long*)seeds, C, first_proposal, B, lu2_block, (hipStream_t)stream);
+}
 int finrom_hmc_stats_update(const finrom_hmc_stats* s, void* stream) {
   CallGuard cg((hipStream_t)stream);
   if (!s) { set_error("hmc_stats_update: null descriptor"); return FINROM_ERR_ARG; }

@@ -184,6 +184,7 @@ int launch_sub_flagged(const double* a, double* b, const int* info, int n_obs, i
 int launch_philox_normal(unsigned long long seed, int64_t first, int64_t S, int n, double* xi, hipStream_t st);
 int launch_hmc_draw(const unsigned long long* seeds, int64_t C, int n, int64_t first, int64_t B, double* P_block, double* lu_block,
                     hipStream_t st);
+int launch_hmc_draw_stage2(const unsigned long long* seeds, int64_t C, int64_t first, int64_t B, double* lu2_block, hipStream_t st);
 
 // frontal band sweep (fom_band.hip, finrom_fom_set_band): per-sample workspace [AB | L | Lx | y -> w], sample-blocked
 struct BandDev {

@@ -95,6 +95,10 @@ struct HmcDev {                  // finrom_hmc_state with the host-side fields r
 int launch_hmc_begin(const HmcDev& h, hipStream_t st);
 int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st);
 int launch_hmc_stats(const finrom_hmc_stats& s, hipStream_t st);      // hmc_stats.hip (the descriptor holds device pointers only)
+// delayed acceptance: finrom_hmc_end cut into its decision (hmc_kernels.hip) and, behind a full-order solve, the second test and
+// the commit (hmc_da.hip; the descriptor holds device pointers only)
+int launch_hmc_end_stage1(const HmcDev& h, const double* Kq, int* ok1, double* Uq, hipStream_t st);
+int launch_hmc_end_stage2(const HmcDev& h, const double* Kq, const finrom_hmc_da& da, hipStream_t st);
 // hmc_model.hip (finrom_hmc_drift / _kick): the model-agnostic halves of a leapfrog step.  A [P x n] (optional, P <= HMC_MODEL_MAXP):
 // drift: k_out = k + eps h.P and theta_out [C x P] = theta0 + A k_out;  kick: the gradient at kq is grad [C x n] or A^T g_theta,
 // then h.dUq and h.P as HmcTail states them (flagged chains: dUq 0, momentum untouched); grad_out (optional): the gradient itself

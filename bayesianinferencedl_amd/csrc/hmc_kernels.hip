@@ -29,12 +29,11 @@ __global__ __launch_bounds__(256) void hmc_begin_kernel(HmcDev h) {
   if (threadIdx.x == 0) h.H0[c] = h.U[c] + 0.5 * pp;
 }
 
-// end of the trajectory: the last momentum update was a whole step (back to a half), potential and Hamiltonian at the end point,
-// Metropolis test against the uploaded log-uniform, state update, trace row
-__global__ __launch_bounds__(256) void hmc_end_kernel(HmcDev h, const double* __restrict__ Kq) {
-  __shared__ double red[4];
-  __shared__ int ok_s;
-  const int64_t c = blockIdx.x, j = *h.jt, row = *h.pt + 1;
+// the decision at the end of a trajectory, for every caller the same arithmetic: the last momentum update was a whole step (back to
+// a half), potential and Hamiltonian at the end point, Metropolis test against the uploaded log-uniform.  All 256 threads call it
+// (two block sums); thread 0 gets the decision and the end point's potential Uq, the others false and Uq untouched.
+__device__ __forceinline__ bool hmc_end_decide(const HmcDev& h, const double* __restrict__ Kq, int64_t c, int64_t j, double* red,
+                                               double& Uq_out) {
   const int64_t o = c * h.n;
   double sp = 0.0, sd = 0.0;
   for (int i = threadIdx.x; i < h.n; i += 256) {
@@ -43,11 +42,24 @@ __global__ __launch_bounds__(256) void hmc_end_kernel(HmcDev h, const double* __
     sp = fma(p, p, sp); sd = fma(d, d, sd);
   }
   const double pp = block_sum_256(sp, red), dd = block_sum_256(sd, red);
+  if (threadIdx.x != 0) return false;
+  double Uq = fma(h.c_lik, h.loss[c], 0.5 * h.c_pri * dd);
+  if (h.info[c] != 0 || !(Uq == Uq) || Uq > 1.7e308 || Uq < -1.7e308) Uq = __builtin_inf();
+  const double H1 = Uq + 0.5 * pp;
+  Uq_out = Uq;
+  return h.lu_block[j * h.C + c] < h.H0[c] - H1;                  // (H1 = inf or nan compares false: rejected)
+}
+
+// end of the trajectory: the decision, state update, trace row
+__global__ __launch_bounds__(256) void hmc_end_kernel(HmcDev h, const double* __restrict__ Kq) {
+  __shared__ double red[4];
+  __shared__ int ok_s;
+  const int64_t c = blockIdx.x, j = *h.jt, row = *h.pt + 1;
+  const int64_t o = c * h.n;
+  double Uq = 0.0;
+  const bool ok0 = hmc_end_decide(h, Kq, c, j, red, Uq);
   if (threadIdx.x == 0) {
-    double Uq = fma(h.c_lik, h.loss[c], 0.5 * h.c_pri * dd);
-    if (h.info[c] != 0 || !(Uq == Uq) || Uq > 1.7e308 || Uq < -1.7e308) Uq = __builtin_inf();
-    const double H1 = Uq + 0.5 * pp;
-    const int ok = h.lu_block[j * h.C + c] < h.H0[c] - H1;      // (H1 = inf or nan compares false: rejected)
+    const int ok = ok0;
     if (ok) h.U[c] = Uq;
     h.accept[c] += ok;
     ok_s = ok;
@@ -58,6 +70,16 @@ __global__ __launch_bounds__(256) void hmc_end_kernel(HmcDev h, const double* __
     if (ok) { h.K[o + i] = Kq[o + i]; h.dU[o + i] = h.dUq[o + i]; }
     if (h.trace != nullptr) h.trace[(row * h.C + c) * h.n + i] = ok ? Kq[o + i] : h.K[o + i];
   }
+}
+
+// delayed acceptance, stage 1 (finrom_hmc_end_stage1): the decision alone -- ok1 and the end point's potential, nothing else
+__global__ __launch_bounds__(256) void hmc_end_stage1_kernel(HmcDev h, const double* __restrict__ Kq, int* __restrict__ ok1,
+                                                             double* __restrict__ Uq_out) {
+  __shared__ double red[4];
+  const int64_t c = blockIdx.x;
+  double Uq = 0.0;
+  const bool ok = hmc_end_decide(h, Kq, c, *h.jt, red, Uq);
+  if (threadIdx.x == 0) { ok1[c] = ok ? 1 : 0; Uq_out[c] = Uq; }
 }
 
 __global__ void hmc_advance_kernel(long long* jt, long long* pt) { *jt += 1; *pt += 1; }
@@ -78,6 +100,14 @@ int launch_hmc_end(const HmcDev& h, const double* Kq, hipStream_t st) {
   hipLaunchKernelGGL(hmc_end_kernel, dim3((unsigned)h.C), dim3(256), 0, st, h, Kq);
   FR_HIP(hipGetLastError());
   hipLaunchKernelGGL(hmc_advance_kernel, dim3(1), dim3(1), 0, st, h.jt, h.pt);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_hmc_end_stage1(const HmcDev& h, const double* Kq, int* ok1, double* Uq, hipStream_t st) {
+  if (h.C == 0) return 0;
+  ScopedKernelTimer t(K_MISC, st);
+  hipLaunchKernelGGL(hmc_end_stage1_kernel, dim3((unsigned)h.C), dim3(256), 0, st, h, Kq, ok1, Uq);
   FR_HIP(hipGetLastError());
   return 0;
 }

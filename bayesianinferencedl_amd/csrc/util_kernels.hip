@@ -492,6 +492,30 @@ int launch_hmc_draw(const unsigned long long* seeds, int64_t C, int n, int64_t f
   return 0;
 }
 
+// The second log-uniform of each proposal of the block (hmc.py correct=: the second stage's test): counter (proposal lo, hi, 0, 2),
+// the conversion of lu_block above.  One thread per (proposal, chain).
+__global__ __launch_bounds__(256) void hmc_draw_stage2_kernel(const unsigned long long* __restrict__ seeds, int64_t C, int64_t first,
+                                                              int64_t B, double* __restrict__ lu2_block) {
+  const int64_t total = B * C;
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < total; row += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j = row / C;
+    const unsigned long long seed = seeds[row - j * C], g = (unsigned long long)(first + j);
+    unsigned o[4];
+    philox4x32_10((unsigned)g, (unsigned)(g >> 32), 0u, 2u, (unsigned)seed, (unsigned)(seed >> 32), o);
+    const unsigned long long m = ((unsigned long long)o[1] << 32) | o[0];
+    lu2_block[row] = log((double)((m >> 11) + 1) * 0x1.0p-53);
+  }
+}
+
+int launch_hmc_draw_stage2(const unsigned long long* seeds, int64_t C, int64_t first, int64_t B, double* lu2_block, hipStream_t st) {
+  if (B == 0 || C == 0) return 0;
+  ScopedKernelTimer t(K_MISC, st);
+  const int64_t blocks = std::min<int64_t>((B * C + 255) / 256, 16384);
+  hipLaunchKernelGGL(hmc_draw_stage2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seeds, C, first, B, lu2_block);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
 __global__ void sub_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t count,
                            double* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)

@@ -681,6 +681,51 @@ typedef struct {
   double* misfit; int32_t* accepted;            /* [(proposals + 1) x C] or NULL; row 0 is the start */
 } finrom_hmc_stats;
 int finrom_hmc_stats_update(const finrom_hmc_stats* s, void* stream);
+/* Delayed acceptance (hmc.py correct=; Christen & Fox 2005): the trajectory runs under a surrogate (the reduced model, with or
+ * without the learned error), the full-order model decides.  finrom_hmc_end is split into a decision and a commit, and ONE
+ * full-order forward solve at the end point (finrom_fom_solve without w) goes in between:
+ *   finrom_hmc_end_stage1  finrom_hmc_end's arithmetic up to the decision, through the same device function: the half step back,
+ *                          the two sums, Uq[c] = fma(c_lik, loss, 0.5 c_pri dd) (+inf where info != 0, NaN or beyond +-1.7e308),
+ *                          ok1[c] = lu_block[*jt C + c] < H0[c] - H1.  Writes ok1 [C] and Uq [C] and NOTHING else: K, U, dU,
+ *                          accept, trace and the counters are untouched.  Launch shape, argument checks and the C == 0 rule
+ *                          of finrom_hmc_end; ok1 and Uq must not be NULL when C > 0.
+ *   finrom_hmc_end_stage2  one 256-thread workgroup per chain; no fused multiply-add but the one written here.  Thread 0, with
+ *                          d = data (+ c n_obs when data_per_sample), jt = *st->jt, pt = *st->pt, in this order:
+ *                            s = 0;  for o = 0 .. n_obs - 1:  r = qoi_f[c][o] - d[o];  s = fma(r, r, s);   lossF = 0.5 s;
+ *                            Dq = c_lik (lossF - st->loss[c]);
+ *                            good = info_f[c] == 0 && |lossF| <= 1.7e308 && Dq is finite;
+ *                            ok = ok1[c] != 0 && good && lu2_block[jt C + c] < D[c] - Dq;
+ *                            cand_loss_f[c] = good ? lossF : NaN;
+ *                            correction[(pt + 1) C + c] = good ? Dq : NaN            (where correction is given);
+ *                            accept1[c] += ok1[c] != 0;   st->accept[c] += ok;
+ *                            ok:  st->U[c] = Uq[c];  D[c] = Dq;  loss_f[c] = lossF.
+ *                          Behind a barrier all threads run finrom_hmc_end's commit: K = Kq[n_steps & 1] and dU = dUq where ok,
+ *                          the trace row pt + 1 (the new state) where st->trace is given; then *jt += 1, *pt += 1 as there.
+ *                          A rejected chain keeps every bit of K, U, dU, D and loss_f.  The weight is w = exp(-D), D = c_lik
+ *                          (loss_FOM - loss_surrogate): the priors cancel, and with stage 1 reversible for the surrogate's
+ *                          posterior the two stages are reversible for the full-order one.
+ * Neither allocates: both are legal while the stream is capturing.  Checks before any device call (FINROM_ERR_ARG, with a
+ * message): those of finrom_hmc_end; a null descriptor; n_obs < 1; a null pointer other than correction with C > 0.  C == 0:
+ * returns 0 and touches nothing, the counters included. */
+typedef struct {
+  int32_t n_obs; int32_t data_per_sample;
+  const int32_t* ok1; const double* Uq;        /* [C] what finrom_hmc_end_stage1 wrote */
+  const double* qoi_f; const int32_t* info_f;  /* [C x n_obs], [C]: finrom_fom_solve at the end point's field */
+  const double* data;                          /* [n_obs], or [C x n_obs] with data_per_sample */
+  const double* lu2_block;                     /* [B x C] second log-uniforms (finrom_hmc_draw_stage2), row *st->jt */
+  double* D; double* loss_f; int64_t* accept1; /* [C] each, the chain's state: correction and full-order misfit of the current
+                                                  point (caller fills them for the start point), proposals past stage 1 */
+  double* cand_loss_f;                         /* [C] out: the end point's full-order misfit (NaN where flagged) */
+  double* correction;                          /* [(proposals + 1) x C] out or NULL; row 0 is the start's D (the caller's) */
+} finrom_hmc_da;
+int finrom_hmc_end_stage1(const finrom_hmc_state* st, int32_t n_steps, int32_t* ok1, double* Uq, void* stream);
+int finrom_hmc_end_stage2(const finrom_hmc_state* st, int32_t n_steps, const finrom_hmc_da* da, void* stream);
+/* The second log-uniform of a block of B proposals, for stage 2: lu2_block [B x C], row j * C + c for proposal first_proposal + j of
+ * the chain with seed seeds[c] (DEVICE array).  Philox4x32-10, key (s lo, s hi), counter (p lo, p hi, 0, 2), and the conversion
+ * of finrom_hmc_draw's log-uniform: a = (o1 << 32) | o0, u = ((a >> 11) + 1) 2^-53, lu2 = log u, finite and <= 0.  It depends on
+ * (s, p) alone.  One launch, no allocation.  Checks (FINROM_ERR_ARG, with a message): C, B or first_proposal negative, a null
+ * pointer with B x C > 0.  B == 0 or C == 0: returns 0, no launch. */
+int finrom_hmc_draw_stage2(const uint64_t* seeds, int64_t C, int64_t first_proposal, int64_t B, double* lu2_block, void* stream);
 
 /* ---- batched multi-start MAP estimation: a projected L-BFGS on the device ------------------------------------------------------- *
  * The reference minimises 0.5 |y(k) - d|^2 + reg(k) with SciPy's L-BFGS-B, one start after another (bayesian_inference/
