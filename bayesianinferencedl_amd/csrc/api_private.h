@@ -37,6 +37,10 @@ struct finrom_rom_s {
   int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
   bool short_grouped = env_rom_short_grouped();      // (A/B, read at creation: the short half list keeps a group per leading parameter, as before group_pays)
   bool no_roomy = getenv("FINROM_PROJ_NO_ROOMY") != nullptr;      // (A/B, read at creation: the pair path keeps the 200-register one-wave kernel)
+  // the roomy epilogue without fixed waits between dependent MFMAs: where finrom_solve_pairs runs the sweep on its masked
+  // stream.  Read at creation: FINROM_PROJ_FIXED_WAITS=1 never (A/B), FINROM_PROJ_SHORT_WAITS=1 at every batch size (tests)
+  bool fixed_waits = getenv("FINROM_PROJ_FIXED_WAITS") != nullptr, short_waits_always = getenv("FINROM_PROJ_SHORT_WAITS") != nullptr;
+  bool short_waits(bool sweep_masked) const { return !fixed_waits && (short_waits_always || sweep_masked); }
   hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's

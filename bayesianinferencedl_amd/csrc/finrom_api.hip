@@ -1260,10 +1260,11 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
 // A_r, B_r (or, with factor > 0, the factor / the solution) by the form of the reduced operator the handle is set to
 // (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
-                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false) {
+                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false, bool short_waits = false) {
   h->last_form = FINROM_ROM_FORM_FULL;
   roomy = roomy && h->projection == FINROM_PROJECTION_DIRECT && rom_roomy_applies(h->d, factor, w_r, qoi_r);
-  h->last_epilogue = roomy ? FINROM_ROM_EPILOGUE_ROOMY : FINROM_ROM_EPILOGUE_STANDARD;
+  short_waits = roomy && short_waits;
+  h->last_epilogue = !roomy ? FINROM_ROM_EPILOGUE_STANDARD : short_waits ? FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS : FINROM_ROM_EPILOGUE_ROOMY;
   if (h->projection == FINROM_PROJECTION_GRAM)
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
   RomDev d = h->d;
@@ -1274,13 +1275,14 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
     d.ext = (double*)h->ext.p;
     if (d.nkg_m > 0) h->last_form = FINROM_ROM_FORM_HALF;
   }
-  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy);
+  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy, short_waits);
 }
 
 // roomy: finrom_solve_pairs beside the FOM's half sweep -- QoI-only calls at r <= 80 then take the 256-register one-wave kernel at
-// every batch size (rom_roomy_applies); finrom_rom_solve itself never does
+// every batch size (rom_roomy_applies); finrom_rom_solve itself never does.  short_waits: that kernel's form without the fixed waits
+// between accumulate-chained MFMAs (finrom_rom_s::short_waits says where)
 static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
-                          double* B_r, int32_t* info, void* stream, bool roomy) {
+                          double* B_r, int32_t* info, void* stream, bool roomy, bool short_waits = false) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!theta || (!qoi_r && h->d.n_obs > 0)))) { set_error("rom_solve: bad argument"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
@@ -1317,7 +1319,7 @@ static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
         qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
-                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm))) return rc;
+                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm, short_waits))) return rc;
     if (factor >= 2) continue;
     int factored = factor;
     if (want_factor && d.NB > 6) {                                     // wider bases: blocked MFMA Cholesky kernel
@@ -1556,9 +1558,14 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
     if (fst != st) FR_HIP(hipStreamWaitEvent(fst, rom->ev_fork, 0));
   }
   // Beside the HALF sweep (154 registers, 11.8 KB of LDS per wave) a QoI-only projection at r <= 80 takes the roomy one-wave kernel:
-  // 256 + 154 registers still share a SIMD.  The choice depends on the two handles and on what the caller wants back, never on
-  // batch size, stream or mask.  FINROM_PROJ_NO_ROOMY=1 at handle creation: the 200-register kernel, as everywhere else.
-  if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy))) return fail(rc);
+  // 256 + 154 registers still share a SIMD.  Whether the roomy kernel runs depends on the two handles and on what the caller wants
+  // back, never on batch size, stream or mask.  FINROM_PROJ_NO_ROOMY=1 at handle creation: the 200-register kernel, as everywhere else.
+  // WHICH of its two forms runs does depend on the mask: the epilogue drops the fixed waits between accumulate-chained MFMAs (same
+  // bits) only beside a sweep on its masked stream, for the reason the pivot records below have: a batch too small for
+  // the mask is bounded from BELOW by the benchmark's contract (0.662 ms at 4096 samples; with the short waits the step measured
+  // 0.660 and 0.678 ms there, with the fixed ones 0.69).
+  if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy, rom->short_waits(fst != st))))
+    return fail(rc);
   // With a masked FOM stream only the SWEEP runs on it: pack + assembly go to an unmasked stream (they take 0.1 ms there against
   // 2.0 ms on 96 CUs beside the projection's start, and since the grouped projection loop the FOM half is the one that ends
   // last: step 20.46 -> 20.26 ms).  FINROM_FOM_PREPASS_MASKED=1: the whole FOM half on the masked stream, as before.
@@ -1575,7 +1582,7 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   join();
   // a roomy call returns a sample that either half flagged as NaN in qoi_r and err (launch_sub_flagged); every other call keeps
   // what its kernels wrote
-  if (rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY && info != nullptr) {
+  if ((rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY || rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS) && info != nullptr) {
     if ((rc = launch_sub_flagged(qoi, qoi_r, info, fom->d.n_obs, S * (int64_t)fom->d.n_obs, err, st))) return rc;
   } else if (err && (rc = launch_sub(qoi, qoi_r, S * (int64_t)fom->d.n_obs, err, st))) return rc;
   if (tracing) {

@@ -929,7 +929,18 @@ constexpr int ROM_SW_LDS = 16 * 5;      // doubles of LDS per wave (B_r)
 #endif
 template <bool RM> constexpr int rom_sw_lds() { return ROM_SW_LDS + (RM && ROM_ROOMY_LDS_DIAG ? ROM_SW_LDS_DIAG : 0); }
 constexpr int ROM_SW_MFMA_DIAG_TILES = 6;      // block rows with at most this many live tiles factor their diagonal tile on the matrix cores
-template <int NB, bool RM = false>
+// SW (round 13, the roomy variant only): without the fixed waits between MFMAs that accumulate onto their predecessor's result.  The
+// hardware orders an MFMA behind the one that writes its accumulator input -- back to back or with other MFMAs between, the chain
+// returns the bits of the serial sum (tools/mfma_f64_chain.hip) -- so the 80-cycle wait stays only where a result is read as an
+// A / B operand or by compiler-scheduled code: behind the last round of the panel, of the trailing updates and of the extra
+// column's chain.  76 waits per sample become 13 at NB = 5; every product and sum keeps its place.
+// MAINTENANCE: between two chained inline-asm MFMAs no statement names n[t] / acc[..] / e any more, so the form is safe only while
+// hipcc puts no instruction of its own that reads or writes those registers (a move, a copy for register allocation, a spill) into
+// the gaps.  With the compiler this was built with it puts none: in the generated code of every NB the only instruction that
+// touches an in-flight accumulator before the next wait is the next MFMA, taking it whole as C.  Nothing in the source enforces
+// that, and a passing test is no evidence for an inline-asm hazard: after a compiler upgrade, or a change that moves the register
+// pressure of this function, read the epilogue in the .s of rom_proj_roomy_sw_kernel<1..5> again (and check: no scratch).
+template <int NB, bool RM = false, bool SW = false>
 __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (NB + 1) / 2], const double (&bacc)[NB], int q, int c,
                                               double* __restrict__ mt, double& qout) {
   // The extra column is formed LEFT-looking -- G_kb -= sum_{j < kb} U(j, kb)^T Z_j when block row kb is reached -- so that at most
@@ -949,6 +960,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
     for (int g = 0; g < 4; ++g)
       if (q + 4 * g == c && 16 * t + c >= p.r) acc[tidx<NB>(t, t)][g] = 1.0;
   int bad = 0;
+  static_assert(!SW || RM, "the short waits belong to the roomy variant");
   sfor<0, NB>([&](auto kc) {
     constexpr int kb = decltype(kc)::value;
     // G_kb = [B_r | (B_obs Phi)^T | 0] rows of this block: column 0 = B_r, columns 1 .. n_obs = rows of B_obs Phi
@@ -963,13 +975,14 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       if (c == 0) v = bl[row];
       e[0][g] = v;
     }
-    // ... minus what the block rows above contribute: a chain of 4 kb MFMAs on one accumulator (each waits for its
-    // predecessor; the partner wave has the pipe meanwhile), its last wait behind the diagonal tile's factorisation
+    // ... minus what the block rows above contribute: a chain of 4 kb MFMAs on one accumulator (without SW each waits 80 cycles
+    // for its predecessor in software, with SW the hardware's interlock orders them; the partner wave has the pipe meanwhile),
+    // its last wait -- in both forms -- behind the diagonal tile's factorisation
     sfor<0, kb>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        if (j > 0 || g > 0) mfma_drain(e);
+        if (!SW && (j > 0 || g > 0)) mfma_drain(e);
         const double ua = acc[tidx<NB>(j, kb)][g], zb = z[j][g];
         asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0 neg:[1,0,0]" : "+v"(e[0]) : "v"(ua), "v"(zb));
       }
@@ -1033,7 +1046,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
         }
     }
     if constexpr (kb > 0) mfma_drain(e);
-    // (b) one tile at a time: four dependent MFMAs, the wait between them covers the same-accumulator hazard
+    // (b) one tile at a time (the standard variant): four dependent MFMAs with a fixed wait behind each
     auto solve_tile = [&](d4& T) {
       double b[4];
 #pragma unroll
@@ -1049,7 +1062,8 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
     if constexpr (RM) {
       // the roomy variant has the registers for all results of the block row at once: the four-MFMA chains of its NB - kb
       // independent tiles (the extra column last) run interleaved, ONE wait per round instead of one per MFMA; every product and
-      // every sum keeps its place in its own chain, so the bits are those of solve_tile
+      // every sum keeps its place in its own chain, so the bits are those of solve_tile.  (SW: the rounds follow each other
+      // without a wait -- n[t] is only the next round's accumulator input -- and the one wait stands behind round 3.)
       constexpr int NP = NB - kb;
       d4 n[NP];
 #pragma unroll
@@ -1061,7 +1075,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
           const double b = t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)][g] : e[0][g];
           asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(n[t]) : "v"(Am[g]), "v"(b));
         }
-        mfma_drain(n);
+        if (!SW || g == 3) mfma_drain(n);
       }
 #pragma unroll
       for (int t = 0; t + 1 < NP; ++t) acc[tidx<NB>(kb, kb + 1 + t)] = n[t];
@@ -1089,7 +1103,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
         for (int ti = kb + 1; ti < NB; ++ti)
 #pragma unroll
           for (int tj = ti; tj < NB; ++tj) {
-            if (first) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(acc[tidx<NB>(ti, tj)]));
+            if (first && (!SW || g == 3)) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(acc[tidx<NB>(ti, tj)]));
             else asm volatile("" : "+v"(acc[tidx<NB>(ti, tj)]));
             first = false;
           }
@@ -1109,7 +1123,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
   return bad;
 }
 
-template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false, bool RM = false>
+template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false, bool RM = false, bool SW = false>
 __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw, int64_t s, int lane,
                                               double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                               int* __restrict__ info, double* __restrict__ w_r = nullptr,
@@ -1237,7 +1251,7 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
     if constexpr (NW == 1 && NB <= 5 && !SK) {
       if (qoi_only) {
         double qv;
-        bad = fused_solve_sw<NB, RM>(p, acc, bacc, q, c, mt_lds, qv);
+        bad = fused_solve_sw<NB, RM, SW>(p, acc, bacc, q, c, mt_lds, qv);
         if (bad && info != nullptr && lane == 0) atomicOr(&info[s], 2);
         if (lane >= 1 && lane <= p.n_obs) qoi_r[s * p.n_obs + lane - 1] = bad ? __builtin_nan("") : qv;
         return;
@@ -1347,7 +1361,7 @@ __device__ __forceinline__ void rom_proj_entry_splitk(RomDev p, const double* __
 
 // NW waves share one sample (each owns every NW-th tile of the upper block triangle); a
 // workgroup is max(4, NW) waves = max(4, NW)/NW samples.
-template <int NB, int NW, bool GR = false, bool HF = false, bool RM = false>
+template <int NB, int NW, bool GR = false, bool HF = false, bool RM = false, bool SW = false>
 __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restrict__ theta, int64_t S,
                                                        double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                                        int* __restrict__ info, double* __restrict__ w_r, double* __restrict__ qoi_r,
@@ -1393,7 +1407,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
         }
       }
     }
-    rom_proj_body<NB, 1, 0, false, GR, false, RM>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
+    rom_proj_body<NB, 1, 0, false, GR, false, RM, SW>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
                                        half ? kpat + __builtin_amdgcn_readfirstlane(half == 2 ? p.kmg_s : p.kmg_m) : kpat, 0, 1, nullptr,
                                        NB <= 5 ? mt_sw + wave * rom_sw_lds<RM>() : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {

@@ -685,7 +685,10 @@ class RomEngine:
 
     def last_epilogue(self):
         """'roomy' when the most recent projection launch ran the 256-register one-wave kernel (the pair path beside the FOM's half
-        sweep, QoI-only, r <= 80), 'standard' for every other kernel, 'none' before the first call (finrom_rom_last_epilogue)."""
+        sweep, QoI-only, r <= 80) with a fixed wait behind every round of its epilogue's dependent MFMAs, 'roomy-short-waits' when
+        it ran that kernel's form without the waits between accumulate-chained MFMAs (same bits; the pair path beside a sweep on
+        its CU-masked stream, batches of 16 384 and more), 'standard' for every other kernel, 'none' before the first call
+        (finrom_rom_last_epilogue)."""
         rc = lib().finrom_rom_last_epilogue(self._h)
         if rc < 0:
             check(rc, "finrom_rom_last_epilogue")

@@ -433,10 +433,15 @@ int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, in
 int finrom_rom_last_form(finrom_rom_t h);
 /* Which epilogue the most recent projection launch on this handle ran (tests assert on it): FINROM_ROM_EPILOGUE_ROOMY = the
  * 256-register one-wave kernel that finrom_solve_pairs launches beside the FOM's half sweep for QoI-only calls at r <= 80
- * (FINROM_PROJ_NO_ROOMY=1 when the handle is created: never); FINROM_ROM_EPILOGUE_STANDARD = any other kernel. */
+ * (FINROM_PROJ_NO_ROOMY=1 when the handle is created: never); FINROM_ROM_EPILOGUE_STANDARD = any other kernel.
+ * FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS = the roomy kernel whose epilogue waits only where an MFMA's result is read by something
+ * other than the next MFMA's accumulator input -- same bits as FINROM_ROM_EPILOGUE_ROOMY, which keeps a fixed wait behind every
+ * round of dependent MFMAs.  finrom_solve_pairs launches it where the FOM's sweep runs on its CU-masked stream (large batches);
+ * when the handle is created, FINROM_PROJ_FIXED_WAITS=1 says never and FINROM_PROJ_SHORT_WAITS=1 at every batch size. */
 #define FINROM_ROM_EPILOGUE_NONE 0
 #define FINROM_ROM_EPILOGUE_STANDARD 1
 #define FINROM_ROM_EPILOGUE_ROOMY 2
+#define FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS 3
 int finrom_rom_last_epilogue(finrom_rom_t h);
 /* theta [S x P] -> w_r [S x r] (NULL to skip), qoi_r [S x n_obs], info [S] (NULL ok);
  * optional A_r [S x r x r] and B_r [S x r] (the state the reference keeps in
