@@ -197,6 +197,9 @@ SIGNATURES = {
     "finrom_mlp_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "finrom_mlp_stage_reach": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "finrom_mlp_forward_max_in": (C.c_int32, []),
+    "finrom_mlp_misfit_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 4),
+    "finrom_mlp_set_tile_min": (C.c_int, [C.c_void_p, C.c_int64]),
+    "finrom_mlp_last_form": (C.c_int, [C.c_void_p]),
     "finrom_romml_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 6),
     "finrom_hmc_begin": (C.c_int, [C.POINTER(HmcState), C.c_void_p]),
     "finrom_hmc_leapfrog": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32,

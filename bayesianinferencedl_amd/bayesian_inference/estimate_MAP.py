@@ -14,7 +14,8 @@ Here:
   * SolverWrapper / RSolverWrapper / ROMMLSolverWrapper restate the reference's one-sample cost_function / gradient surface with
     its timers, so that the reference's SciPy loop runs unchanged (and is the yardstick of the tests);
   * estimate_map(...) is the reference's study as a function, one batched minimize_device call per model.
-The pure-DL surrogate inversion (MLSolverWrapper) has no counterpart: this project has no surrogate model."""
+The pure-DL surrogate inversion (MLSolverWrapper :147-184, res_ML.npy) is the fourth model, "ml": the network of
+deep_learning/dl_model.py as a model of its own (Surrogate, finrom_mlp_misfit_grad)."""
 from __future__ import annotations
 
 import os
@@ -54,11 +55,12 @@ def _torch_data(data, S=None):
                            device=torch.device("cuda", torch.cuda.current_device()))
 
 
-def objective(kind, data, *, solver=None, solver_r=None, params=None, gamma=None):
+def objective(kind, data, *, solver=None, solver_r=None, params=None, gamma=None, surrogate=None):
     """kind 'fom' (solver: Fin; params None = nodal fields, 'five' / 'nine' = fin conductivities through Fin.gradient_batch),
     'rom' (solver_r: AffineROMFin; fields through finrom_subfin_avg -> finrom_rom_grad, or params='five' / 'nine' with theta the
     nine fin values; the library maps the gradient back with G), 'romml' (solver_r with a device error model; fields:
-    finrom_romml_grad).  gamma: the reference's Tikhonov term 0.5 gamma k^T K1 k (K1 = Fin._unit_stiffness(); fields only;
+    finrom_romml_grad), 'ml' (surrogate: dl_model.Surrogate; fields only: finrom_mlp_misfit_grad; the Tikhonov term needs
+    solver= or solver_r= for K1).  gamma: the reference's Tikhonov term 0.5 gamma k^T K1 k (K1 = Fin._unit_stiffness(); fields only;
     None: no regulariser).  data: the observations [n_obs]."""
     data = np.ascontiguousarray(data, dtype=np.float64)
     dt = {}
@@ -113,8 +115,27 @@ def objective(kind, data, *, solver=None, solver_r=None, params=None, gamma=None
         def host(X):
             r = solver_r.grad_romml_batch(np.asarray(X), data=data)
             return r["loss"], r["grad"], np.asarray(r["info"]) != 0
+    elif kind == "ml":
+        if surrogate is None:
+            raise ValueError("objective('ml'): needs surrogate=Surrogate")
+        if params is not None:
+            raise ValueError("objective('ml'): the surrogate takes nodal fields (params=None)")
+        if data.shape[-1] != surrogate.n_out:
+            raise ValueError(f"objective('ml'): {data.shape[-1]} observations, the surrogate has {surrogate.n_out} outputs")
+        d, gmap = surrogate.n_in, None
+        ops = solver.ops if solver is not None else (solver_r.ops if solver_r is not None else None)
+        if gamma is not None and ops is None:
+            raise ValueError("objective('ml'): the Tikhonov term needs solver= or solver_r= (K1)")
+
+        def dev(X):
+            r = surrogate.misfit_grad_batch(X, data_t())
+            return r["loss"], r["grad"], r["info"].ne(0)
+
+        def host(X):
+            r = surrogate.misfit_grad_batch(np.asarray(X), data)
+            return r["loss"], r["grad"], np.asarray(r["info"]) != 0
     else:
-        raise ValueError(f"unknown model {kind!r} (fom, rom, romml)")
+        raise ValueError(f"unknown model {kind!r} (fom, rom, romml, ml)")
     tik = None
     if gamma is not None:
         if params is not None:
@@ -222,6 +243,37 @@ class ROMMLSolverWrapper:
         return self.grad
 
 
+class MLSolverWrapper:
+    """Surrogate misfit + Tikhonov term, one sample per call (estimate_MAP.py:147-184): cost 1/2 |NN(z) - d|^2 + reg,
+    gradient tf.gradients(loss, input) + grad_reg.  surrogate: dl_model.Surrogate (device or host)."""
+
+    def __init__(self, surrogate_model, data, solver):
+        self.model, self.solver, self.data = surrogate_model, solver, np.asarray(data, dtype=np.float64)
+        self.z = Function(solver.V)
+        self.cost = None
+        self.grad = None
+        self.fwd_time = 0.0
+        self.grad_time = 0.0
+
+    def cost_function(self, z_v):
+        self.z.vector().set_local(z_v)
+        t_i = time.time()
+        y_NN = np.asarray(self.model.predict_batch(np.asarray(z_v, dtype=np.float64)[None, :])["qoi"][0], dtype=np.float64)
+        self.fwd_time += time.time() - t_i
+        self.solver._k.assign(self.z)
+        self.cost = 0.5 * np.linalg.norm(y_NN - self.data) ** 2 + self.solver.reg
+        return self.cost
+
+    def gradient(self, z_v):
+        t_i = time.time()
+        grad_NN = np.asarray(self.model.misfit_grad_batch(np.asarray(z_v, dtype=np.float64)[None, :], self.data)["grad"][0])
+        self.grad_time += time.time() - t_i
+        self.z.vector().set_local(z_v)
+        self.solver._k.assign(self.z)
+        self.grad = grad_NN + self.solver.grad_reg
+        return self.grad
+
+
 # ---- the study ------------------------------------------------------------------------------------------------------------
 def starting_points(V, n_starting_pts=6, seed=0, length=1.6):
     """exp(0.5 U^T xi), xi ~ N(0, I), U = make_cov_chol(V, length) (estimate_MAP.py:246-263) -> [n_starting_pts, n]."""
@@ -246,18 +298,19 @@ def reconstruction_errors(solver, k_true, X, data):
     return obs, l2, pw
 
 
-_FILES = {"fom": "res_FOM.npy", "rom": "res_ROM.npy", "romml": "res_ROMML.npy"}
+_FILES = {"fom": "res_FOM.npy", "rom": "res_ROM.npy", "romml": "res_ROMML.npy", "ml": "res_ML.npy"}
 
 
 def estimate_map(solver, solver_r, k_true, *, n_starting_pts=6, seed=0, length=1.6, models=("fom", "rom", "romml"),
-                 gamma=GAMMA, ftol=1e-10, gtol=1e-8, out_dir=None, device=True, X0=None, **options):
+                 gamma=GAMMA, ftol=1e-10, gtol=1e-8, out_dir=None, device=True, X0=None, surrogate=None, **options):
     """The reference's MAP study (estimate_MAP.py) as a function: synthetic data d = B w(k_true) from an FOM solve, the box
     [0.95 min k_true, 1.05 max k_true], n_starting_pts starts exp(0.5 U^T xi) (or X0), and per model ONE batched minimisation
     of its misfit + the Tikhonov term (lbfgs.minimize_device; device=False: minimize_host over the same callables).
     solver_r must carry the data (set_data) for the ROM models; it is set here.
     Returns {model: dict(x [S, n], fun, nit, nfev, status, message, obs_err, l2_err, pw_err, best (index), time_s)}, with
     `data` and `starts` beside; out_dir: res_FOM.npy / res_ROM.npy / res_ROMML.npy hold each model's best x (by l2_err, as the
-    reference keeps the start of least reconstruction error)."""
+    reference keeps the start of least reconstruction error).  "ml" in models needs surrogate= (dl_model.Surrogate) and writes
+    res_ML.npy."""
     k_true = as_nodal(k_true).astype(np.float64)
     data = np.asarray(solver.qoi_operator(solver.forward(k_true)[0]), dtype=np.float64)
     if solver_r is not None:
@@ -266,7 +319,7 @@ def estimate_map(solver, solver_r, k_true, *, n_starting_pts=6, seed=0, length=1
     bounds = (0.95 * float(k_true.min()), 1.05 * float(k_true.max()))
     out = {"data": data, "starts": X0, "bounds": bounds}
     for kind in models:
-        obj = objective(kind, data, solver=solver, solver_r=solver_r, gamma=gamma)
+        obj = objective(kind, data, solver=solver, solver_r=solver_r, gamma=gamma, surrogate=surrogate)
         t0 = time.perf_counter()
         res = obj.minimize(X0, device=device, bounds=bounds, ftol=ftol, gtol=gtol, **options)
         dt = time.perf_counter() - t0

@@ -609,14 +609,35 @@ def rom_value_and_grad(solver_r, data=None):
     return f
 
 
+def ml_value_and_grad(surrogate, data):
+    """The pure deep-learning surrogate's evaluation (the reference's MLSolverWrapper), batched over chains:
+    dl_model.Surrogate.misfit_grad_batch at nodal fields against the observations `data`; flagged where the loss is not finite."""
+    data = np.ascontiguousarray(data, dtype=np.float64)
+
+    def f(K):
+        res = surrogate.misfit_grad_batch(np.ascontiguousarray(K, dtype=np.float64), data)
+        return np.asarray(res["loss"]), np.asarray(res["grad"]), np.asarray(res["info"]) != 0
+    return f
+
+
 MODELS = ("romml", "rom", "fom")
+MODELS += ("ml",)
 
 
-def _check_model(model, solver_r, solver, data, who):
+def _check_model(model, solver_r, solver, data, who, surrogate=None):
     """ValueError for a model the chains do not know and for a model without what it evaluates with."""
     if model not in MODELS:
-        raise ValueError(f"{who}: unknown model {model!r} (romml, rom, fom)")
-    if model == "fom":
+        raise ValueError(f"{who}: unknown model {model!r} (romml, rom, fom, ml)")
+    if surrogate is not None and model != "ml":
+        raise ValueError(f"{who}: surrogate= belongs to model='ml'; model={model!r} does not evaluate with it")
+    if model == "ml":
+        if surrogate is None:
+            raise ValueError(f"{who}: model='ml' needs surrogate=Surrogate")
+        if data is None:
+            raise ValueError(f"{who}: model='ml' needs data= (the observations)")
+        if solver is not None:
+            raise ValueError(f"{who}: solver= belongs to model='fom'; model='ml' evaluates with surrogate=")
+    elif model == "fom":
         if solver is None:
             raise ValueError(f"{who}: model='fom' needs solver=Fin")
         if data is None:
@@ -631,9 +652,11 @@ def _check_model(model, solver_r, solver, data, who):
     return model
 
 
-def _device_model(model, solver_r, solver, data_t):
+def _device_model(model, solver_r, solver, data_t, surrogate=None):
     """f(F [C, n] device tensor) -> dict(loss [C], grad [C, n], info [C]) on torch's current stream: the calls that
     estimate_MAP.objective(kind).device makes, one adapter per model."""
+    if model == "ml":
+        return lambda Fq: surrogate.misfit_grad_batch(Fq, data_t)
     if model == "romml":
         return lambda Fq: solver_r.grad_romml_batch(Fq, data=data_t)
     if model == "fom":
@@ -653,7 +676,7 @@ def _device_model(model, solver_r, solver, data_t):
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None, model="romml", solver=None, correct=None):
+                     stats=None, model="romml", solver=None, correct=None, surrogate=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -681,13 +704,17 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     on the "field" engine at the candidate's field (Kq[n_leapfrog & 1], or the step's field buffer under a prior; its flags cleared
     in front), finrom_hmc_end_stage2, and the stats launch with the full-order misfit: still one linear chain, captured once.  The
     start point's solve warms the full-order workspace before the capture; under "philox" one finrom_hmc_draw_stage2 launch per
-    block sits beside finrom_hmc_draw, under "numpy" a third uploaded block carries the second uniforms.  No metric form."""
+    block sits beside finrom_hmc_draw, under "numpy" a third uploaded block carries the second uniforms.  No metric form.
+    model "ml" (surrogate=) has no fused step: FINROM_ERR_UNSUPPORTED before anything is touched, so that fused=None falls back."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
-    _check_model(model, solver_r, solver, data, "run_chains_fused")
+    _check_model(model, solver_r, solver, data, "run_chains_fused", surrogate)
     _check_correct(correct, stats, "run_chains_fused", model)
+    from .. import _ffi
+    if model == "ml":
+        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): model='ml' has no fused leapfrog step "
+                               "(pass fused=False)")
     import ctypes as C
     import torch
-    from .. import _ffi
     L = _ffi.lib()
     if model == "fom":
         fom = solver._engine("field")
@@ -929,7 +956,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0, stats=None, model="romml", solver=None, correct=None):
+                      proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -962,6 +989,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     with another model.  `model` of the result names it.
     Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates (model=
     "fom": fom_value_and_grad(solver, data); "rom": rom_value_and_grad(solver_r, data)).
+    model "ml", surrogate: the pure deep-learning surrogate (dl_model.Surrogate on the device; data= required, solver_r may be None):
+    an evaluation is finrom_mlp_misfit_grad, two launches; no fused form.  Same chains as run_chains(ml_value_and_grad(surrogate, data)).
     correct: a Fin, with model "romml" or "rom" (ValueError with "fom", and with ChainStats(resume=...)) -- delayed acceptance
     (module docstring): the trajectory under the surrogate, one full-order forward solve at its end point, the second test.
     Fused: run_chains_fused's launches (no metric form: fused=None then takes this one); here the rule of finrom_hmc_end_stage2 in
@@ -970,7 +999,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     start's D, row q: the candidate's) and n_fom = proposals + 1; stats' misfit is the full-order one.
     Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
-    _check_model(model, solver_r, solver, data, "run_chains_device")
+    _check_model(model, solver_r, solver, data, "run_chains_device", surrogate)
     _check_correct(correct, stats, "run_chains_device", model)
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
@@ -982,7 +1011,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
                                     prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver,
-                                    correct=correct)
+                                    correct=correct, surrogate=surrogate)
         except _ffi.FinromError:
             if fused:
                 raise
@@ -998,7 +1027,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     else:
         mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
     data_t = torch.as_tensor(np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64), **f64)
-    model_eval = _device_model(model, solver_r, solver, data_t)
+    model_eval = _device_model(model, solver_r, solver, data_t, surrogate)
     if seeds64 is None:
         rngs = [np.random.default_rng(s) for s in seeds]
         assert len(rngs) == C

@@ -87,21 +87,32 @@ class LowRankMetric:
         return self._dev
 
 
-def misfit_jacobian(kind, k, *, solver=None, solver_r=None):
+def misfit_jacobian(kind, k, *, solver=None, solver_r=None, surrogate=None, data=None):
     """J [n_obs, n]: the Jacobian of the model's observables with respect to the nodal field, at the field k [n].
     kind 'fom': the full model's, Fin.sensitivity_batch (solver).
     kind 'rom' / 'romml': the reduced model's (solver_r, an AffineROMFin), from ONE batched gradient call of n_obs + 1 rows at the
     same field with per-sample data d, d + e_1, ..., d + e_n_obs: the gradient of 1/2 |d - y(k)|^2 is affine in d, so
     J_i = g(d) - g(d + e_i).  This is the Jacobian the chains' own gradients use: for 'romml' the learned error enters through the
     network's vector-Jacobian product while the averaged basis functions psi stay frozen, as in the reference's grad_romml.
-    (Row 0 of that batch is the value and gradient at the true data: gauss_newton_map uses it, reduced_value_grad_jac.)"""
+    (Row 0 of that batch is the value and gradient at the true data: gauss_newton_map uses it, reduced_value_grad_jac.)
+    kind 'ml': the pure deep-learning surrogate's (surrogate, a dl_model.Surrogate), the same n_obs + 1 rows through
+    Surrogate.misfit_grad_batch: J_i = g(d) - g(d + e_i) = vjp(e_i); data: d (default zeros; J does not depend on it in exact
+    arithmetic)."""
     k = np.ascontiguousarray(k, dtype=np.float64).reshape(-1)
     if kind == "fom":
         if solver is None:
             raise ValueError("misfit_jacobian('fom') needs solver=")
         return np.asarray(solver.sensitivity_batch(k[None, :]))[0]
+    if kind == "ml":
+        if surrogate is None:
+            raise ValueError("misfit_jacobian('ml') needs surrogate=")
+        n_obs = surrogate.n_out
+        d = np.zeros(n_obs) if data is None else np.asarray(data, dtype=np.float64).reshape(n_obs)
+        D = np.vstack([d[None, :], d[None, :] + np.eye(n_obs)])
+        g = np.asarray(surrogate.misfit_grad_batch(np.ascontiguousarray(np.broadcast_to(k, (n_obs + 1, k.size))), D)["grad"], dtype=np.float64)
+        return g[0][None, :] - g[1:]
     if kind not in ("rom", "romml"):
-        raise ValueError(f"misfit_jacobian: kind {kind!r} (one of 'fom', 'rom', 'romml')")
+        raise ValueError(f"misfit_jacobian: kind {kind!r} (one of 'fom', 'rom', 'romml', 'ml')")
     if solver_r is None:
         raise ValueError(f"misfit_jacobian({kind!r}) needs solver_r=")
     return _reduced_jacobian(kind, solver_r, k)[0]

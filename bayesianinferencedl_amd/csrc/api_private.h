@@ -3,6 +3,7 @@
 // includes this header.
 #pragma once
 #include "finrom_internal.h"
+#include "mlp_surrogate.h"
 #include "rom_tables.h"
 
 using namespace finrom;      // (the handle structs are the C ABI's: global names, made of finrom:: parts)
@@ -93,6 +94,12 @@ struct finrom_mlp_s {
   // finrom_hmc_leapfrog: the partial sums of theta the last step left in thp, and the field they belong to (position buffer,
   // momentum buffer, step size, chains): the next step uses them only if it is that field's step
   const double* carry_k = nullptr; const double* carry_mom = nullptr; double carry_eps = 0.0; int64_t carry_S = 0;
+  // finrom_mlp_misfit_grad (mlp_surrogate.hip): the tile form's padded weights (made by the first call that needs them, outside any
+  // capture), the per-sample walk's zero operand, the tile form's row flags; which form the last call took
+  Scratch sur_w, sur_zero, sur_bad;
+  SurPad sur_pad; bool sur_ready = false;
+  int64_t tile_min = 4096;      // (the measured crossover of the two forms at n = 1597: DESIGN 7)
+  int last_form = 0;
 };
 
 namespace finrom {

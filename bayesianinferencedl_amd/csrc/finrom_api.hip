@@ -1691,6 +1691,7 @@ void finrom_mlp_destroy(finrom_mlp_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);
   h->tape.release(); h->theta.release(); h->gth.release(); h->shift.release(); h->qtmp.release(); h->etmp.release(); h->g0.release(); h->y0p.release(); h->thp.release();
+  h->sur_w.release(); h->sur_zero.release(); h->sur_bad.release();
   delete h;
 }
 int finrom_mlp_predict(finrom_mlp_t h, const double* k, int64_t S, double* e, void* stream) {
@@ -1708,6 +1709,61 @@ int32_t finrom_mlp_stage_reach(int32_t n_layers, int32_t n_w, int32_t n_out, int
   return mlp_stage_reach(n_layers, n_w, n_out);
 }
 int32_t finrom_mlp_forward_max_in(void) { return MLP_FORWARD_MAX_IN; }
+int finrom_mlp_set_tile_min(finrom_mlp_t h, int64_t tile_min) {
+  if (!h || tile_min < 1) { set_error("mlp_set_tile_min: null handle or tile_min < 1"); return FINROM_ERR_ARG; }
+  h->tile_min = tile_min;
+  return 0;
+}
+int finrom_mlp_last_form(finrom_mlp_t h) { return h ? h->last_form : 0; }
+int finrom_mlp_misfit_grad(finrom_mlp_t h, const double* k, const double* data, int32_t data_per_sample, int64_t S, double* grad,
+                           double* loss, double* out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  CallGuard cg(st);
+  if (!h || S < 0 || (S > 0 && !k)) { set_error("mlp_misfit_grad: bad argument (null handle or k, or S < 0)"); return FINROM_ERR_ARG; }
+  if ((data == nullptr) != (loss == nullptr)) { set_error("mlp_misfit_grad: data and loss are given or left out together"); return FINROM_ERR_ARG; }
+  if (grad != nullptr && data == nullptr) { set_error("mlp_misfit_grad: the gradient needs data"); return FINROM_ERR_ARG; }
+  if (!grad && !loss && !out) { set_error("mlp_misfit_grad: at least one of grad, loss, out is required"); return FINROM_ERR_ARG; }
+  if (S == 0) return 0;
+  const MlpDev& m = h->d;
+  const bool tile = S >= h->tile_min;
+  if (!tile) { if (int fits = mlp_forward_fits(m)) return fits; }      // (before any device call)
+  const int no = m.n_out;
+  const int64_t stride = data_per_sample ? no : 0;
+  int rc;
+  if (tile && !h->sur_ready) {
+    if (call_captures() || any_capture()) {
+      set_error("mlp_misfit_grad: the tile form's padded weights cannot be made while a stream capture is open: run the same call once "
+                "before the capture begins");
+      return FINROM_ERR_UNSUPPORTED;
+    }
+    if ((rc = h->sur_w.reserve(sur_pad_floats(m) * sizeof(float)))) return rc;
+    if ((rc = launch_sur_pad(m, (float*)h->sur_w.p, &h->sur_pad, st))) return rc;
+    FR_HIP(hipStreamSynchronize(st));                  // (a later call may come on another stream)
+    h->sur_ready = true;
+  }
+  // the per-sample forward writes its tape whatever is asked for; the tile form only for a gradient
+  if (!tile || grad) { if ((rc = h->tape.reserve((size_t)S * (m.n_layers + 1) * m.n_w * sizeof(float)))) return rc; }
+  if (!out) { if ((rc = h->etmp.reserve((size_t)S * no * sizeof(double)))) return rc; out = (double*)h->etmp.p; }
+  if (tile) {
+    if ((rc = h->sur_bad.reserve((size_t)S * sizeof(int)))) return rc;
+    if ((rc = launch_sur_tile_forward(m, h->sur_pad, k, S, data, stride, grad ? (float*)h->tape.p : nullptr, out, loss, (int*)h->sur_bad.p, st))) return rc;
+    if (grad && (rc = launch_sur_tile_backward(m, h->sur_pad, S, (const float*)h->tape.p, data, stride, out, (const int*)h->sur_bad.p, grad, st))) return rc;
+    h->last_form = 2;
+    return 0;
+  }
+  if (grad) {                                          // the walk back's qoi_r operand: zeros (0 + e is exact)
+    const size_t cap0 = h->sur_zero.cap;
+    if ((rc = h->sur_zero.reserve((size_t)S * no * sizeof(double)))) return rc;
+    if (h->sur_zero.cap != cap0) {                     // (grown: outside any capture)
+      FR_HIP(hipMemsetAsync(h->sur_zero.p, 0, h->sur_zero.cap, st));
+      FR_HIP(hipStreamSynchronize(st));
+    }
+  }
+  if ((rc = launch_sur_forward(m, k, S, data, stride, (float*)h->tape.p, out, loss, st))) return rc;
+  if (grad && (rc = launch_sur_backward(m, S, (const float*)h->tape.p, data, stride, (const double*)h->sur_zero.p, out, grad, st))) return rc;
+  h->last_form = 1;
+  return 0;
+}
 }  // extern "C"
 // clears the caller's info for the forms of romml_grad_impl whose kernels only ever flag in (a kernel node, not a memset node: below)
 __global__ __launch_bounds__(256) static void clear_info_kernel(int32_t* __restrict__ info, int64_t S) {

@@ -1,0 +1,39 @@
+// The network as a model of its own (mlp_surrogate.hip, finrom_mlp_misfit_grad): value and gradient of 1/2 |data - NN(k)|^2.
+// Included by mlp_surrogate.hip and the host layer only: a change here rebuilds neither the reduced model's nor the FOM's units.
+#pragma once
+#include "finrom_internal.h"
+
+namespace finrom {
+
+// the tile form's zero-padded copies of the weights (width 64, n_in to a multiple of SUR_KC): one allocation on the handle
+constexpr int SUR_KC = 64;          // inputs per chunk of the streamed first layer (and of its transpose)
+constexpr int SUR_ROWS = 64;        // samples per workgroup: four waves of 16 rows
+struct SurPad {
+  int n_inp = 0;                     // n_in rounded up to a multiple of SUR_KC
+  const float* W0p = nullptr;        // [n_inp][64]
+  const float* b0p = nullptr;        // [64]
+  const float* scp = nullptr; const float* shp = nullptr;      // [(L + 1)][64]
+  const float* Wp = nullptr;  const float* WpT = nullptr;      // [L][64][64]: W_l[i][j] and its transpose
+  const float* bp = nullptr;         // [L][64]
+  const float* Whp = nullptr; const float* WhpT = nullptr;     // [64][64]: Wh[i][o] and its transpose
+  const float* bhp = nullptr;        // [64]
+};
+inline int sur_n_inp(int n_in) { return (n_in + SUR_KC - 1) / SUR_KC * SUR_KC; }
+size_t sur_pad_floats(const MlpDev& m);
+// fills buf (sur_pad_floats(m) floats) from the handle's weights and points *p into it
+int launch_sur_pad(const MlpDev& m, float* buf, SurPad* p, hipStream_t st);
+
+// per-sample form: one 1024-thread workgroup per sample (mlp_forward_body), then the walk back and the first layer's transpose.
+// loss (with data) and tape are optional outputs of the forward launch; out [S x n_out] is required
+int launch_sur_forward(const MlpDev& m, const double* k, int64_t S, const double* data, int64_t data_stride, float* tape, double* out,
+                       double* loss, hipStream_t st);
+int launch_sur_backward(const MlpDev& m, int64_t S, const float* tape, const double* data, int64_t data_stride, const double* zero,
+                        const double* out, double* grad, hipStream_t st);
+// tile form: SUR_ROWS samples per workgroup, the first layer and its transpose on the fp32 matrix cores.  bad [S]: 1 where the row
+// has a non-finite input (written by the forward launch, read by the backward one)
+int launch_sur_tile_forward(const MlpDev& m, const SurPad& p, const double* k, int64_t S, const double* data, int64_t data_stride,
+                            float* tape, double* out, double* loss, int* bad, hipStream_t st);
+int launch_sur_tile_backward(const MlpDev& m, const SurPad& p, int64_t S, const float* tape, const double* data, int64_t data_stride,
+                             const double* out, const int* bad, double* grad, hipStream_t st);
+
+}  // namespace finrom

@@ -398,3 +398,95 @@ def train_error_model(out_path=None, *, n_layers=5, n_weights=50, epochs=5000, b
     if out_path is not None:
         model.save(out_path)
     return model, hist
+
+
+# ---- the pure deep-learning surrogate (reference dl_model.py:202-214 `load_surrogate_model`) ---------------------------------------
+SURROGATE_LAYERS, SURROGATE_WIDTH = 3, 50      # res_bn_fc_model(ELU(), Adam, 3e-4, 3, 50, 1446, 40): the error model's network
+
+
+class Surrogate:
+    """The same network as a model of its own: nodal conductivity -> observables, misfit 1/2 |data - NN(k)|^2.
+    device=True: engine.DeviceErrorModel.misfit_grad (finrom_mlp_misfit_grad: NumPy in, NumPy out; torch in, torch out on the
+    current stream); device=False: the NumPy statement through ResBnFcModel.predict / .vjp (fp32 network, loss and gradient
+    widened to double as the device stores them)."""
+
+    def __init__(self, model, device=True):
+        self.model, self.device = model, bool(device)
+        self.n_in, self.n_out = model.n_in, model.n_out
+        self._dev = None
+        if self.device:
+            from ..engine import DeviceErrorModel
+            self._dev = DeviceErrorModel(model)
+
+    @staticmethod
+    def _pack(loss, grad, qoi):
+        if loss is None:
+            info = None
+        elif hasattr(loss, "is_cuda"):
+            import torch
+            info = (~torch.isfinite(loss)).to(torch.int32)
+        else:
+            info = (~np.isfinite(loss)).astype(np.int32)
+        return {"loss": loss, "grad": grad, "qoi": qoi, "info": info}
+
+    def predict_batch(self, K):
+        """-> dict(loss None, grad None, qoi [S, n_out], info None)."""
+        if self.device:
+            r = self._dev.misfit_grad(K, None, want_grad=False)
+            return self._pack(None, None, r["out"])
+        return self._pack(None, None, np.asarray(self.model.predict(np.asarray(K, dtype=np.float64)), dtype=np.float64))
+
+    def misfit_grad_batch(self, K, data, want_grad=True):
+        """K [S, n]; data [n_out] or [S, n_out] -> dict(loss [S], grad [S, n], qoi [S, n_out], info [S]: 1 where the loss is not finite)."""
+        if self.device:
+            r = self._dev.misfit_grad(K, data, want_grad=want_grad)
+            return self._pack(r["loss"], r["grad"], r["out"])
+        X = np.asarray(K, dtype=np.float64).reshape(-1, self.n_in)
+        out = np.asarray(self.model.predict(X), dtype=np.float64)
+        r = np.asarray(data, dtype=np.float64).reshape(-1, self.n_out) - out
+        loss = 0.5 * np.sum(r * r, axis=1)
+        grad = -np.asarray(self.model.vjp(X, r), dtype=np.float64) if want_grad else None
+        return self._pack(loss, grad, out)
+
+    def set_tile_min(self, tile_min):
+        if self._dev is not None:
+            self._dev.set_tile_min(tile_min)
+
+    def last_form(self):
+        return self._dev.last_form() if self._dev is not None else 0
+
+    def close(self):
+        if self._dev is not None:
+            self._dev.close()
+            self._dev = None
+
+
+def load_surrogate_model(path, randobs=True):
+    """The reference's surrogate (dl_model.py:202-214): 3 units, 50 wide, 40 outputs (randobs) or 9 (sub-fin averages), read from
+    an .npz written by ResBnFcModel.save (Keras checkpoints cannot be read here).  -> ResBnFcModel."""
+    model = ResBnFcModel.load(path)
+    want = (SURROGATE_LAYERS, SURROGATE_WIDTH, 40 if randobs else 9)
+    if (model.n_layers, model.n_weights, model.n_out) != want:
+        raise ValueError(f"load_surrogate_model: {path} holds (units, width, outputs) = {(model.n_layers, model.n_weights, model.n_out)}, "
+                         f"the reference's surrogate is {want}")
+    return model
+
+
+def train_surrogate_model(out_path=None, *, epochs=5000, batch_size=500, lr=lr_schedule, seed=0, data=None, tr_size=6000, v_size=500,
+                          data_dir='../data', device=True, graph=True, **gen_kwargs):
+    """train_error_model for the surrogate: the reference's sizes (3 units, 50 wide, n_obs outputs), targets the FOM observables
+    of the dataset generator (gen_affine_avg_rom_dataset(want_qoi=True)); data = (z_train, qoi_train, z_val, qoi_val) skips the
+    generation.  -> (model, history)."""
+    if data is None:
+        from .generate_fin_dataset import gen_affine_avg_rom_dataset
+        data = []
+        for size in (tr_size, v_size):
+            z, _, q = gen_affine_avg_rom_dataset(size, out_dir=data_dir, want_qoi=True, **gen_kwargs)
+            data += [z, q]
+    z_tr, q_tr, z_v, q_v = (np.asarray(a) for a in data)
+    model = ResBnFcModel(z_tr.shape[1], q_tr.shape[1], SURROGATE_LAYERS, SURROGATE_WIDTH, seed)
+    hist = model.fit(z_tr, q_tr, epochs=epochs, batch_size=batch_size, shuffle=True, validation_data=(z_v, q_v), lr=lr, seed=seed,
+                     device=device, graph=graph)
+    if out_path is not None:
+        model.save(out_path)
+    return model, hist

@@ -29,7 +29,7 @@ def _tags(dataset_size):
 
 def gen_affine_avg_rom_dataset(dataset_size, resolution=40, genrand=False, *, phi=None, seed=None,
                                out_dir='../data', basis_path='../data/basis_nine_param.txt', batch=65536,
-                               device_rng=False, _stop_after_batches=None):
+                               device_rng=False, _stop_after_batches=None, want_qoi=False):
     """Returns (z_s [S, n], qoi_errors [S, n_obs]) like the reference and writes the three .npy files with its names.
 
     Host memory is bounded by one batch: when the files are written (out_dir exists and the size selects a file set) the
@@ -111,4 +111,4 @@ def gen_affine_avg_rom_dataset(dataset_size, resolution=40, genrand=False, *, ph
                 os.replace(prog_path + ".tmp", prog_path)
     if tags and prog_path and os.path.exists(prog_path) and (_stop_after_batches is None):
         os.remove(prog_path)
-    return (z_s, qoi_errors)
+    return (z_s, qoi_errors, qois) if want_qoi else (z_s, qoi_errors)     # (want_qoi: the FOM observables too, the surrogate's targets)

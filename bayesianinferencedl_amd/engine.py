@@ -925,6 +925,39 @@ class DeviceErrorModel:
         check(lib().finrom_mlp_predict(self._h, b.ptr, b.S, ep, b.stream), "finrom_mlp_predict")
         return b.out(e, (b.S, self.n_out))
 
+    def misfit_grad(self, K, data, want_grad=True):
+        """finrom_mlp_misfit_grad: the network as a model of its own (the reference's pure deep-learning surrogate) for a batch of
+        nodal fields K [S, n]: out = NN(K), loss = 1/2 |data - out|^2, grad = -vjp(data - out).  data [n_out] or [S, n_out], or
+        None (prediction only: loss and grad are None).  NumPy in, NumPy out; torch in, torch out on the current stream.
+        -> dict(loss [S], grad [S, n] or None, out [S, n_out])."""
+        n, no = self.n_in, self.n_out
+        b = _Batch(K, n)
+        S = b.S
+        out, op = b.new((S, no), zero=False)
+        if data is None:
+            if want_grad:
+                raise ValueError("misfit_grad: the gradient needs data")
+            check(lib().finrom_mlp_misfit_grad(self._h, b.ptr, None, 0, S, None, None, op, b.stream), "finrom_mlp_misfit_grad")
+            return {"loss": None, "grad": None, "out": b.out(out, (S, no))}
+        data = data if _is_torch(data) else np.ascontiguousarray(data, dtype=np.float64)
+        if data.shape[-1] != no or (data.ndim == 2 and data.shape[0] != S) or data.ndim > 2:
+            raise ValueError(f"misfit_grad: data must be [{no}] or [{S}, {no}], got {tuple(data.shape)}")
+        per_sample = 1 if data.ndim == 2 else 0
+        db = _Batch(data, no)
+        loss, lp = b.new((S,), zero=False)
+        grad, gp = b.new((S, n), zero=False) if want_grad else (None, None)
+        check(lib().finrom_mlp_misfit_grad(self._h, b.ptr, db.ptr, per_sample, S, gp, lp, op, b.stream), "finrom_mlp_misfit_grad")
+        _sync_if_mixed(b, db)
+        return {"loss": b.out(loss, (S,)), "grad": b.out(grad, (S, n)) if want_grad else None, "out": b.out(out, (S, no))}
+
+    def set_tile_min(self, tile_min):
+        """Batches of at least tile_min samples take misfit_grad's tile form (default 4096)."""
+        check(lib().finrom_mlp_set_tile_min(self._h, int(tile_min)), "finrom_mlp_set_tile_min")
+
+    def last_form(self):
+        """The form the last misfit_grad took: 0 none yet, 1 per-sample, 2 tile."""
+        return int(lib().finrom_mlp_last_form(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             _ffi.destroy_handle("finrom_mlp_destroy", self._h)

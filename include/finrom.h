@@ -511,6 +511,24 @@ int32_t finrom_mlp_forward_max_in(void);
 int finrom_romml_grad(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,
                       int32_t data_per_sample, int64_t S, double* grad, double* loss, double* qoi_r, double* e_nn,
                       int32_t* info, void* stream);
+/* The network as a model of its own -- the reference's pure deep-learning surrogate (deep_learning/dl_model.py
+ * load_surrogate_model, bayesian_inference/estimate_MAP.py MLSolverWrapper): out = NN(k) [S x n_out], loss [S] = 1/2 |data - out|^2,
+ * grad [S x n_in] = -(d NN / d k)^T (data - out), network arithmetic in fp32, loss and grad stored as double.  k, data and the
+ * outputs are device pointers; data [n_out] (data_per_sample = 0) or [S x n_out].  grad may be NULL (value only); data and loss
+ * are NULL together (prediction only); out may be NULL; at least one output is required (FINROM_ERR_ARG otherwise, with a message,
+ * before any device call).  S == 0: returns 0, no launch.
+ * Two forms (finrom_mlp_last_form: 0 none yet, 1 per-sample, 2 tile).  S < tile_min: one workgroup per sample, two launches
+ * (forward; walk back and first layer's transpose); n_in <= finrom_mlp_forward_max_in().  S >= tile_min (default 4096: the measured
+ * crossover at n = 1597; finrom_mlp_set_tile_min, >= 1): 64 samples per workgroup, k read once and the first layer and its transpose on the fp32 matrix
+ * cores, every (sample, unit) and (sample, input) product one ordered fma chain: a sample's bits depend neither on S nor on its
+ * position in the batch nor on its neighbours; no limit on n_in.  In the tile form a row with a non-finite input gets NaN in out,
+ * loss and grad, and every other row keeps its bits.  The tile form keeps zero-padded copies of the weights on the handle, made
+ * by the first call that takes it: that call, like one that has to grow a workspace, is refused with FINROM_ERR_UNSUPPORTED and
+ * a message while a stream capture is open -- run the same call (same handle, same S) once before the capture. */
+int finrom_mlp_misfit_grad(finrom_mlp_t h, const double* k, const double* data, int32_t data_per_sample, int64_t S,
+                           double* grad, double* loss, double* out, void* stream);
+int finrom_mlp_set_tile_min(finrom_mlp_t h, int64_t tile_min);   /* default 4096; >= 1 */
+int finrom_mlp_last_form(finrom_mlp_t h);                        /* 0 none yet, 1 per-sample, 2 tile */
 
 /* ---- HMC trajectories on the device (BASELINE configs[4]) ----------------------------------------------------------------------- *
  * PyMC3's sampler calls the reference's value-and-gradient op once per leapfrog step (bayesian_inference/pymc_func_bayes_inverse.py:
