@@ -54,6 +54,13 @@ field only through its sub-fin averages, so under a prior its fused step stays i
 grad_v = (Sop U^T)^T g_theta, no triangular product and no field during a trajectory.  `fom_value_and_grad` / `rom_value_and_grad`
 are the host callables for run_chains.  model="romml" (the default): every path, launch and bit as before.
 
+`model="ml"` (surrogate=Surrogate, data=): the fourth model, the pure deep-learning surrogate; torch-op form by default.  `ml_form=
+"steps" | "trajectory"` on the two device chain functions moves its trajectory into the library (csrc/hmc_ml.hip): a step as three
+launches (finrom_hmc_leapfrog_ml), or all n_leapfrog steps in ONE launch with a 1024-thread workgroup per chain
+(finrom_hmc_trajectory_ml), which leaves the bits of the composed steps.  Under a prior the field is folded into the first layer
+(dl_model.whiten_first_layer, Surrogate.whitened: W0' = U W0, b0' = b0 + W0^T mean) and the chain is the i.i.d. chain of that network
+with mean 0 and tau 1: no triangular product and no field during a trajectory.  ml_form=None: every path, launch and bit as before.
+
 `correct=` on the three chain functions: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under
 a surrogate -- model="romml" or "rom" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway,
 under the surrogate's Hamiltonian; the end point then gets ONE full-order forward solve (QoI only: no adjoint, no gradient), and
@@ -652,6 +659,21 @@ def _check_model(model, solver_r, solver, data, who, surrogate=None):
     return model
 
 
+ML_FORMS = ("steps", "trajectory")
+
+
+def _check_ml_form(ml_form, model, who, fused=None):
+    """ValueError for an ml_form the chains do not know, for one beside another model and for one with fused=False."""
+    if ml_form is None:
+        return
+    if ml_form not in ML_FORMS:
+        raise ValueError(f"{who}: unknown ml_form {ml_form!r} (None, 'steps', 'trajectory')")
+    if model != "ml":
+        raise ValueError(f"{who}: ml_form= belongs to model='ml'; model={model!r} has its own fused step")
+    if fused is not None and not fused:
+        raise ValueError(f"{who}: ml_form={ml_form!r} is a fused form; fused=False asks for the torch-op form")
+
+
 def _device_model(model, solver_r, solver, data_t, surrogate=None):
     """f(F [C, n] device tensor) -> dict(loss [C], grad [C, n], info [C]) on torch's current stream: the calls that
     estimate_MAP.objective(kind).device makes, one adapter per model."""
@@ -676,7 +698,7 @@ def _device_model(model, solver_r, solver, data_t, surrogate=None):
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None, model="romml", solver=None, correct=None, surrogate=None):
+                     stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
     """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
     include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
     front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
@@ -705,14 +727,36 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     in front), finrom_hmc_end_stage2, and the stats launch with the full-order misfit: still one linear chain, captured once.  The
     start point's solve warms the full-order workspace before the capture; under "philox" one finrom_hmc_draw_stage2 launch per
     block sits beside finrom_hmc_draw, under "numpy" a third uploaded block carries the second uniforms.  No metric form.
-    model "ml" (surrogate=) has no fused step: FINROM_ERR_UNSUPPORTED before anything is touched, so that fused=None falls back."""
+    model "ml" (surrogate=) without ml_form: FINROM_ERR_UNSUPPORTED before anything is touched, so that fused=None falls back.
+    ml_form (model "ml" only; None: as above): "steps" -- a proposal is finrom_hmc_begin, n_leapfrog x finrom_hmc_leapfrog_ml (three
+    launches each: forward with the position update and the flag, walk back, kick), finrom_hmc_end; "trajectory" -- finrom_hmc_begin,
+    ONE finrom_hmc_trajectory_ml launch (a 1024-thread workgroup per chain runs all n_leapfrog steps), finrom_hmc_end.  The two forms
+    leave the same bits; evaluation 0 and the proposals that contain a recorded evaluation run in the step form under either.  Under
+    prior= the chain runs on surrogate.whitened(prior) -- the field folded into the first layer, W0' = U W0 and b0' = b0 + W0^T mean
+    -- with mean zeros and tau = 1: no triangular product and no field during a trajectory; K and trace are mapped to fields after
+    the run, stats= and correct= add one finrom_sampler_field launch on the end point per proposal, and `recorded` then holds
+    (index, v, loss, gradient WITH RESPECT TO v) -- whitened coordinates, not (field, loss, field gradient) as elsewhere.  rng=,
+    proposal0=, stats=, correct=Fin, keep_trace=, graph= and block= as for the other models; metric=: FINROM_ERR_UNSUPPORTED.
+    ValueError for an unknown ml_form and for ml_form beside another model, before anything touches the device.  The result carries
+    ml_form."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
     _check_model(model, solver_r, solver, data, "run_chains_fused", surrogate)
     _check_correct(correct, stats, "run_chains_fused", model)
+    _check_ml_form(ml_form, model, "run_chains_fused")
     from .. import _ffi
-    if model == "ml":
+    if model == "ml" and ml_form is None:
         raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): model='ml' has no fused leapfrog step "
                                "(pass fused=False)")
+    if model == "ml":                                                # everything refused before the device is touched
+        if _check_metric(metric, np.shape(K0)[-1]) is not None:
+            raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog steps of model='ml' "
+                                   "have no metric form (pass fused=False and no ml_form)")
+        if np.shape(data)[-1] != surrogate.n_out or np.ndim(data) not in (1, 2):
+            raise ValueError(f"run_chains_fused: data must be [{surrogate.n_out}] or [C, {surrogate.n_out}], got {np.shape(data)}")
+        if np.shape(K0)[-1] != surrogate.n_in:
+            raise ValueError(f"run_chains_fused: the chains have {np.shape(K0)[-1]} coordinates, the surrogate {surrogate.n_in} inputs")
+        if not surrogate.device:
+            raise _ffi.FinromError("run_chains_fused needs the surrogate on the device (Surrogate(model, device=True))")
     import ctypes as C
     import torch
     L = _ffi.lib()
@@ -720,6 +764,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         fom = solver._engine("field")
         fom._enable_gradient()
         rom = mlp = Sop = None
+    elif model == "ml":                                              # under a prior: the field folded into the first layer
+        sur = surrogate.whitened(prior) if prior is not None else surrogate
+        rom, mlp, Sop = None, sur._dev, None
     else:
         rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
         if model == "romml" and mlp is None:
@@ -754,6 +801,7 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     data_t = torch.as_tensor(data_np, **f64)
     per_sample = 1 if data_np.ndim == 2 else 0
     whitened_rom = model == "rom" and prior is not None              # the step never forms the field
+    no_field = whitened_rom or (model == "ml" and prior is not None)   # (nor does the pure surrogate's: surrogate.whitened)
     if model == "rom":                                               # theta = theta0 + A x, gradient A^T g_theta (x: k, or v under a prior)
         S_np = np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64)
         if not np.array_equal(S_np, solver_r.ops.S):                 # (one map serves theta and the chain rule)
@@ -796,6 +844,10 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         return torch.cuda.current_stream().cuda_stream
 
     def leap(state, step, want_grad=False):
+        if model == "ml":
+            _ffi.check(L.finrom_hmc_leapfrog_ml(mlp._h, C.byref(state), step, data_t.data_ptr(), per_sample,
+                                                grad_rec.data_ptr() if want_grad else None, None, stream()), "finrom_hmc_leapfrog_ml")
+            return
         if model == "fom":
             if prior is not None:
                 _ffi.check(L.finrom_hmc_leapfrog_field_fom(fom._h, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
@@ -839,9 +891,9 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             if whitened_rom:                                         # field and field-space gradient, formed for the record alone
                 recorded.append((evals, fs.field(Kq[(step + 1) & 1], mean=fmean).cpu().numpy().copy(), loss.cpu().numpy().copy(),
                                  gth_b.cpu().numpy() @ S_np))
-            elif prior is not None:
+            elif prior is not None and model != "ml":
                 recorded.append((evals, F.cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_f.cpu().numpy().copy()))
-            else:
+            else:                                                    # (model "ml" under a prior: v and the gradient with respect to v)
                 recorded.append((evals, Kq[(step + 1) & 1].cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_rec.cpu().numpy().copy()))
         evals += 1
 
@@ -850,23 +902,27 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             _ffi.check(L.finrom_hmc_begin_metric(C.byref(st), mh._h, stream()), "finrom_hmc_begin_metric")
         else:
             _ffi.check(L.finrom_hmc_begin(C.byref(st), stream()), "finrom_hmc_begin")
-        for i in range(n_leapfrog):                                  # each step's input depends on the previous gradient
-            leap(st, i, want_grad=rec)
-            if rec:
-                note(i)
+        if ml_form == "trajectory" and not rec:                      # all n_leapfrog steps in one launch: the step form's bits
+            _ffi.check(L.finrom_hmc_trajectory_ml(mlp._h, C.byref(st), n_leapfrog, data_t.data_ptr(), per_sample, stream()),
+                       "finrom_hmc_trajectory_ml")
+        else:
+            for i in range(n_leapfrog):                              # each step's input depends on the previous gradient
+                leap(st, i, want_grad=rec)
+                if rec:
+                    note(i)
         if metric is not None:
             _ffi.check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
         elif da is not None:                                         # the surrogate's test, the full-order model at the end point, its test
             _ffi.check(L.finrom_hmc_end_stage1(C.byref(st), n_leapfrog, da.ok1.data_ptr(), da.Uq.data_ptr(), stream()),
                        "finrom_hmc_end_stage1")
-            if whitened_rom:                                         # (no step formed the field; the sums below share it)
+            if no_field:                                             # (no step formed the field; the sums below share it)
                 field_of(Kq[n_leapfrog & 1])
             da.solve(F if prior is not None else Kq[n_leapfrog & 1])
             _ffi.check(L.finrom_hmc_end_stage2(C.byref(st), n_leapfrog, C.byref(da.desc), stream()), "finrom_hmc_end_stage2")
         else:
             _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
         if ds is not None:                                           # (F holds the field of the trajectory's last step: the end point's)
-            if whitened_rom and da is None:                          # (no step formed it: the end point's field, for the sums alone)
+            if no_field and da is None:                              # (no step formed it: the end point's field, for the sums alone)
                 field_of(Kq[n_leapfrog & 1])
             ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss if da is None else da.cand)
 
@@ -883,7 +939,7 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if trace is not None:
         trace[0].copy_(K)
     _restore_chain(stats, K, U, dU)
-    if whitened_rom and (stats is not None or da is not None):      # the start point's field (also the field kernel's workspace, before a capture)
+    if no_field and (stats is not None or da is not None):          # the start point's field (also the field kernel's workspace, before a capture)
         field_of(K)
     if da is not None:                                               # evaluation 0 of the full-order model (warms its workspace up)
         da.start(F if prior is not None else K, loss, c_lik)
@@ -936,6 +992,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         done += nb
     cs = ds.result(K, U, dU) if ds is not None else None
     more = da.result() if da is not None else {}
+    if ml_form is not None:
+        more["ml_form"] = ml_form
     if prior is not None:
         return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs, model=model,
                              **more)
@@ -956,7 +1014,7 @@ def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None):
+                      proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
@@ -990,7 +1048,10 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates (model=
     "fom": fom_value_and_grad(solver, data); "rom": rom_value_and_grad(solver_r, data)).
     model "ml", surrogate: the pure deep-learning surrogate (dl_model.Surrogate on the device; data= required, solver_r may be None):
-    an evaluation is finrom_mlp_misfit_grad, two launches; no fused form.  Same chains as run_chains(ml_value_and_grad(surrogate, data)).
+    an evaluation is finrom_mlp_misfit_grad, two launches; no fused form unless ml_form= names one ("steps" | "trajectory": run_chains_fused's
+    launches, see there; not with fused=False, no metric form, and nothing falls back to the torch-op form then).  Same chains as
+    run_chains(ml_value_and_grad(surrogate, data)); under prior= with ml_form: as run_chains(ml_value_and_grad(surrogate.whitened(prior),
+    data), V0, mean=0.0, tau=1.0) mapped through prior.field.
     correct: a Fin, with model "romml" or "rom" (ValueError with "fom", and with ChainStats(resume=...)) -- delayed acceptance
     (module docstring): the trajectory under the surrogate, one full-order forward solve at its end point, the second test.
     Fused: run_chains_fused's launches (no metric form: fused=None then takes this one); here the rule of finrom_hmc_end_stage2 in
@@ -1001,6 +1062,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
     _check_model(model, solver_r, solver, data, "run_chains_device", surrogate)
     _check_correct(correct, stats, "run_chains_device", model)
+    _check_ml_form(ml_form, model, "run_chains_device", fused)
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
@@ -1011,9 +1073,9 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
             return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
                                     mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
                                     prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver,
-                                    correct=correct, surrogate=surrogate)
+                                    correct=correct, surrogate=surrogate, ml_form=ml_form)
         except _ffi.FinromError:
-            if fused:
+            if fused or ml_form is not None:
                 raise
     _check_prior(prior, mean, "run_chains_device")
     dev = torch.device("cuda", torch.cuda.current_device())

@@ -1691,7 +1691,7 @@ void finrom_mlp_destroy(finrom_mlp_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);
   h->tape.release(); h->theta.release(); h->gth.release(); h->shift.release(); h->qtmp.release(); h->etmp.release(); h->g0.release(); h->y0p.release(); h->thp.release();
-  h->sur_w.release(); h->sur_zero.release(); h->sur_bad.release();
+  h->sur_w.release(); h->sur_zero.release(); h->sur_bad.release(); h->hml_grad.release();
   delete h;
 }
 int finrom_mlp_predict(finrom_mlp_t h, const double* k, int64_t S, double* e, void* stream) {
@@ -2142,6 +2142,65 @@ int finrom_hmc_leapfrog_rom(finrom_rom_t rom, const double* A, const double* the
   if (!rc) rc = finrom_rom_grad(rom, theta, data, data_per_sample, a->C, a->loss, g_theta, nullptr, qoi_r, a->info, stream);
   if (!rc) rc = hmc_kick_impl(a, step, nullptr, g_theta, A, P, grad_out, stream, "hmc_leapfrog_rom");
   return rc;
+}
+
+}  // extern "C"
+// ---- the chains under the pure deep-learning surrogate (hmc_ml.hip; hmc.py model="ml", ml_form=) -----------------------------------
+// everything both entry points refuse before any device call, then the workspaces on the handle: tape and out per chain, the walk
+// back's zero operand (grown outside a capture only: Scratch::reserve refuses inside one, with a message)
+static int hmc_ml_prepare(finrom_mlp_t mlp, const finrom_hmc_state* a, const double* data, double** out, const char* who) {
+  if (!mlp || !data) { set_error(std::string(who) + ": null mlp handle or data"); return FINROM_ERR_ARG; }
+  const MlpDev& m = mlp->d;
+  if (a->n != m.n_in) {
+    set_error(std::string(who) + ": n = " + std::to_string(a->n) + " is not the network's input size (" + std::to_string(m.n_in) + ")");
+    return FINROM_ERR_ARG;
+  }
+  if (a->c_pri == 0.0) { set_error(std::string(who) + ": c_pri = 0"); return FINROM_ERR_ARG; }
+  if (int fits = mlp_forward_fits(m)) return fits;
+  if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_UNSUPPORTED; }
+  if (a->C == 0) return 0;
+  int rc;
+  if ((rc = mlp->tape.reserve((size_t)a->C * (m.n_layers + 1) * m.n_w * sizeof(float)))) return rc;
+  if (!*out) { if ((rc = mlp->etmp.reserve((size_t)a->C * m.n_out * sizeof(double)))) return rc; *out = (double*)mlp->etmp.p; }
+  const size_t cap0 = mlp->sur_zero.cap;
+  if ((rc = mlp->sur_zero.reserve((size_t)a->C * m.n_out * sizeof(double)))) return rc;
+  if (mlp->sur_zero.cap != cap0) {                     // (grown: outside any capture)
+    FR_HIP(hipMemset(mlp->sur_zero.p, 0, mlp->sur_zero.cap));
+  }
+  return 0;
+}
+extern "C" {
+int finrom_hmc_leapfrog_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, int32_t step, const double* data, int32_t data_per_sample,
+                           double* grad_out, double* out, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_leapfrog_ml")) return rc;
+  if (step < 0) { set_error("hmc_leapfrog_ml: step < 0"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_leapfrog_ml")) return rc;
+  if (a->C == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const MlpDev& m = mlp->d;
+  double* g = grad_out;
+  if (!g) { if (int rc = mlp->hml_grad.reserve((size_t)a->C * a->n * sizeof(double))) return rc; g = (double*)mlp->hml_grad.p; }
+  const int64_t stride = data_per_sample ? m.n_out : 0;
+  double* kq = a->Kq[(step + 1) & 1];
+  int rc = launch_hmc_ml_forward(m, h, a->Kq[step & 1], kq, data, stride, (float*)mlp->tape.p, out, a->loss, a->info, st);
+  if (!rc) rc = launch_sur_backward(m, a->C, (const float*)mlp->tape.p, data, stride, (const double*)mlp->sur_zero.p, out, g, st);
+  if (!rc) rc = launch_hmc_kick(h, kq, g, nullptr, nullptr, 0, nullptr, st);
+  return rc;
+}
+int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, int32_t n_steps, const double* data, int32_t data_per_sample,
+                             void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_trajectory_ml")) return rc;
+  if (n_steps < 0) { set_error("hmc_trajectory_ml: n_steps < 0"); return FINROM_ERR_ARG; }
+  double* out = nullptr;
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_trajectory_ml")) return rc;
+  if (a->C == 0) return 0;
+  const MlpDev& m = mlp->d;
+  return launch_hmc_ml_trajectory(m, h, n_steps, a->Kq[0], a->Kq[1], data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p,
+                                  (float*)mlp->tape.p, out, a->loss, a->info, (hipStream_t)stream);
 }
 
 // ---- low-rank metric (hmc_metric.hip) --------------------------------------------------------------------------------------------

@@ -36,4 +36,13 @@ int launch_sur_tile_forward(const MlpDev& m, const SurPad& p, const double* k, i
 int launch_sur_tile_backward(const MlpDev& m, const SurPad& p, int64_t S, const float* tape, const double* data, int64_t data_stride,
                              const double* out, const int* bad, double* grad, hipStream_t st);
 
+// hmc_ml.hip (finrom_hmc_leapfrog_ml / finrom_hmc_trajectory_ml): the chains under this model, one 1024-thread workgroup per chain.
+// forward: k_out = fma(h.eps, h.P, k), the network and the misfit at k_out (tape, out, loss), info = 1 where the loss is not finite
+// else 0 -- the step form's first launch, launch_sur_backward and launch_hmc_kick behind it.  trajectory: n_steps such steps in one
+// launch from kq0 (step s reads kq[s & 1] and writes kq[(s + 1) & 1]), the kick on h.P and h.dUq included; zero: [C x n_out] zeros
+int launch_hmc_ml_forward(const MlpDev& m, const HmcDev& h, const double* k, double* k_out, const double* data, int64_t data_stride,
+                          float* tape, double* out, double* loss, int* info, hipStream_t st);
+int launch_hmc_ml_trajectory(const MlpDev& m, const HmcDev& h, int n_steps, double* kq0, double* kq1, const double* data,
+                             int64_t data_stride, const double* zero, float* tape, double* out, double* loss, int* info, hipStream_t st);
+
 }  // namespace finrom

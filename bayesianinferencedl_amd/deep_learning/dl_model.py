@@ -448,6 +448,12 @@ class Surrogate:
         grad = -np.asarray(self.model.vjp(X, r), dtype=np.float64) if want_grad else None
         return self._pack(loss, grad, out)
 
+    def whitened(self, prior):
+        """The Surrogate of whiten_first_layer(self.model, prior) on the same device setting: its misfit at whitened coordinates v is
+        this one's at the field prior.field(v), its gradient the pullback of this one's (up to the fp32 rounding of the folded first
+        layer).  What the fused chains of hmc.run_chains_fused(model="ml", ml_form=...) run on under a prior."""
+        return Surrogate(whiten_first_layer(self.model, prior), device=self.device)
+
     def set_tile_min(self, tile_min):
         if self._dev is not None:
             self._dev.set_tile_min(tile_min)
@@ -459,6 +465,26 @@ class Surrogate:
         if self._dev is not None:
             self._dev.close()
             self._dev = None
+
+
+def whiten_first_layer(model, prior, dtype=np.float32):
+    """The latent Gaussian-field prior folded into the first layer.  With k = m + U^T v (prior.field),
+        W0^T k + b0 = (U W0)^T v + (b0 + W0^T m),
+    so the network with W0' = U W0 and b0' = b0 + W0^T m evaluated at v is the network evaluated at the field, and its input
+    gradient is the pullback U grad_k: the whitened potential loss(k(v)) / sigma^2 + |v|^2 / 2 is the i.i.d. potential (mean 0,
+    tau = 1) of that network.  Both products are formed in float64 and then cast to `dtype`; every other array is SHARED with
+    `model` (not copied), the optimiser state is not taken over.  -> ResBnFcModel."""
+    U, m = np.asarray(prior.U, dtype=np.float64), np.asarray(prior.mean, dtype=np.float64)
+    if U.shape != (model.n_in, model.n_in) or m.shape != (model.n_in,):
+        raise ValueError(f"whiten_first_layer: the prior has {U.shape[0]} nodes, the network {model.n_in} inputs")
+    W0 = np.asarray(model.W0, dtype=np.float64)
+    out = ResBnFcModel.__new__(ResBnFcModel)
+    out.n_in, out.n_out, out.n_layers, out.n_weights = model.n_in, model.n_out, model.n_layers, model.n_weights
+    out.W0 = np.ascontiguousarray(U @ W0).astype(dtype)
+    out.b0 = (np.asarray(model.b0, dtype=np.float64) + m @ W0).astype(dtype)
+    out.units, out.head = model.units, model.head
+    out.opt = {"t": 0, "epoch": 0, "m": None, "v": None}
+    return out
 
 
 def load_surrogate_model(path, randobs=True):

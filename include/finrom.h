@@ -625,6 +625,29 @@ int finrom_hmc_leapfrog_field_fom(finrom_fom_t fom, finrom_sampler_t prior, cons
 int finrom_hmc_leapfrog_rom(finrom_rom_t rom, const double* A, const double* theta0, const finrom_hmc_state* st, int32_t step,
                             const double* data, int32_t data_per_sample, double* theta, double* g_theta, double* grad_out,
                             double* qoi_r, void* stream);
+/* The chains under the FOURTH model, the pure deep-learning surrogate of finrom_mlp_misfit_grad (hmc.py model="ml", ml_form=): the one
+ * model whose chain needs nothing from any other workgroup, so a whole trajectory can run in one launch.  Same ping-pong convention.
+ *   finrom_hmc_leapfrog_ml    ONE step as a linear chain of three launches: (1) k' = fma(eps, P, k) and the per-sample forward of
+ *                             finrom_mlp_misfit_grad at k' -> st->loss, out [C x n_out] (or the handle's buffer: out NULL), and
+ *                             st->info[c] = 1 where loss[c] is not finite, else 0; (2) its per-sample walk back -> the gradient, into
+ *                             grad_out [C x n] (or the handle's buffer: grad_out NULL); (3) finrom_hmc_kick's kernel with that
+ *                             gradient.  loss and the gradient are the bits finrom_mlp_misfit_grad returns at k' in its per-sample form.
+ *   finrom_hmc_trajectory_ml  steps 0 .. n_steps - 1 in ONE launch: C workgroups of 1024 threads, chain c's workgroup alone carries
+ *                             its position, momentum and flags from step to step (workgroup barriers only; no flags, spins or atomics
+ *                             between workgroups).  On return Kq[n_steps & 1], P, dUq, loss and info hold the bits n_steps calls of
+ *                             finrom_hmc_leapfrog_ml leave there, a flagged chain's included (it keeps stepping: position moved, dUq 0,
+ *                             P untouched); the other position buffer may hold anything.  n_steps == 0: no launch.
+ * Under the latent Gaussian-field prior the field folds into the first layer (W0' = U W0, b0' = b0 + W0^T m: hmc.py,
+ * dl_model.whiten_first_layer): the same two entry points with mean zeros and c_pri = 1, no triangular product and no field in a step.
+ * Checks before any device call: a null state field, handle or data, step / n_steps < 0, c_pri == 0 (FINROM_ERR_ARG); st->n other than
+ * the network's n_in (FINROM_ERR_ARG); n_in > finrom_mlp_forward_max_in() or C > 65535 (FINROM_ERR_UNSUPPORTED).  data [n_out]
+ * (data_per_sample = 0) or [C x n_out].  C == 0: returns 0, no launch.  The workspaces (tape and out per chain, the gradient) live on
+ * the handle and grow in the first call with that C: that call is refused with FINROM_ERR_UNSUPPORTED and a message while a stream
+ * capture is open.  finrom_hmc_begin / _end / _end_stage1 / _end_stage2 around them unchanged: a proposal is 3 launches. */
+int finrom_hmc_leapfrog_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, int32_t step, const double* data, int32_t data_per_sample,
+                           double* grad_out, double* out, void* stream);
+int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, int32_t n_steps, const double* data, int32_t data_per_sample,
+                             void* stream);
 
 /* ---- Laplace-preconditioned HMC: a low-rank metric at the MAP point ------------------------------------------------------------- *
  * The reference's working sampler builds a low-rank Gauss-Newton Hessian of the misfit at the MAP point in prior-whitened
