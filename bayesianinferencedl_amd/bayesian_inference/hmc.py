@@ -5,76 +5,91 @@ drives through the reference's Theano op (bayesian_inference/pymc_func_bayes_inv
 
 PyMC3 / Theano are control plane and out of scope; what the hot path needs from them is the leapfrog recursion
 that makes every evaluation's input depend on the previous evaluation's gradient.  This module is that recursion and
-nothing more: fixed-length leapfrog trajectories with a Metropolis test, independent chains seeded `seed + chain`, and one of
-two priors:
-  * default: an i.i.d. Gaussian prior N(mean, tau^2) per node (the form BASELINE configs[4] measures);
-  * `prior=GaussianFieldPrior(V)` (gaussian_field.py): the reference's own prior, a latent Matern-5/2 Gaussian field
-    (`pm.gp.Latent(Matern52(2, ls=1.2)).prior`, :191-201), sampled as PyMC3 samples it -- non-centred, in whitened coordinates:
-    the chains move v ~ N(0, I), the field is k = mean + U^T v (U the upper Cholesky factor of the covariance), the potential is
-    misfit(k) / sigma^2 + |v|^2 / 2 and its gradient v + U grad_k / sigma^2.  The value-and-gradient call still receives fields
-    and returns field-space gradients; on the device the two dense triangular products around it are library kernels
-    (finrom_sampler_field / _pullback; fused: finrom_hmc_leapfrog_field).
+nothing more: fixed-length leapfrog trajectories with a Metropolis test, in independent chains.  Chains are independent, so C
+chains advance in LOCKSTEP: one device call evaluates the current leapfrog point of every chain (a batch of C samples), each
+chain keeping its own momentum, random stream and accept/reject decision.  On N GPUs a rank owns chains `rank, rank + N, ...` (one
+chain per GPU at N = C) and there is no communication until the traces are gathered.
 
-Chains are independent, so C chains may advance in LOCKSTEP: one device call evaluates the current leapfrog point of every
-chain (a batch of C samples), each chain keeping its own momentum, random stream and accept/reject decision.  On N GPUs a
-rank owns chains `rank, rank + N, ...` (one chain per GPU at N = C) and there is no communication until the traces are
-gathered.
+Three chain functions walk the same chains:
+  run_chains         the host recursion in NumPy over a callable value_and_grad(K) -> (loss, grad, bad): the statement the other
+                     two are tested against (callables: romml_ / fom_ / rom_ / ml_value_and_grad);
+  run_chains_device  the chains resident on the device, a proposal captured once as a HIP graph and replayed; its torch-op form
+                     is a few elementwise kernels around one model call per step and serves every combination below;
+  run_chains_fused   the same with the trajectory's arithmetic inside the library, one step form per (model, prior, metric)
+                     (_fused_form); run_chains_device takes it where the library has the form (fused=None) or is told to (fused=True).
+The two device functions share one scaffold (_DeviceChains) and differ in evaluation 0 and in what a proposal launches.
 
-`metric=LowRankMetric` (laplace.py) on the three chain functions: a constant mass matrix M = I + V diag(lambda) V^T, the
-Gauss-Newton Hessian of the potential at the MAP point (the `scaling` the reference's sampler hands to NUTS, bayesian_inference/
-inference.py:102-140,165).  The random stream is the same: the standard normals xi become momenta p = M^(1/2) xi, the position
-moves by eps M^-1 p and the kinetic energy is p^T M^-1 p / 2 (= |xi|^2 / 2 at the start).  metric=None: every path and bit as before.
+The keywords, on all three functions unless said otherwise:
 
-`rng="philox"` on the three chain functions: the momenta and the Metropolis uniforms come from a counter-based stream (philox.py;
-on the device finrom_hmc_draw, one launch per block of proposals, no host draw and no upload) instead of one NumPy generator per
-chain.  The draw of proposal p of the chain with seed s depends on (s, p) alone, so a chain is the same for any `block`, any deal
-of the chains over ranks, and a run of p1 proposals followed by a run from its end state (K; V under a prior) with proposal0=p1
-and an explicit mean= (the first run's; under a prior the prior carries it) walks the path of one uninterrupted run.
-rng="numpy" (the default): every path and bit as before; a NumPy generator cannot be advanced to a proposal, so proposal0 must be 0.
+`prior=` None: an i.i.d. Gaussian prior N(mean, tau^2) per node (the form BASELINE configs[4] measures; mean=None: the start
+points).  `GaussianFieldPrior(V)` (gaussian_field.py): the reference's own prior, a latent Matern-5/2 Gaussian field
+(`pm.gp.Latent(Matern52(2, ls=1.2)).prior`, :191-201), sampled as PyMC3 samples it -- non-centred, in whitened coordinates: the
+chains move v ~ N(0, I), the field is k = mean + U^T v (U the upper Cholesky factor of the covariance), the potential is
+misfit(k) / sigma^2 + |v|^2 / 2 and its gradient v + U grad_k / sigma^2.  K0 then holds whitened start points, mean must be None
+(the prior carries it) and tau is unused; the value-and-gradient call still receives fields and returns field-space gradients (on
+the device the two triangular products around it are finrom_sampler_field / _pullback); K and trace of the result are fields, V
+the whitened end states.
 
-`stats=ChainStats(burn, batch)` on the three chain functions: what the reference's drivers take from the trace after the run
-(bayesian_inference/inference.py:175-214 `np.mean(trace, 0)`, `np.std(trace, 0)`, the misfit per draw; pymc_func_bayes_inverse.py:
-212-220) accumulated WHILE the chains run, so that no trace is kept: per chain and node the Welford mean and sum of squared
-deviations of the FIELD (under a prior the field, not the whitened state: its variance needs Cov(v) in full) and the Welford moments
-of the means of batches of `batch` consecutive draws, per chain the misfit and the accept flag after every proposal.  On the device
-that is one launch per proposal (finrom_hmc_stats_update, behind the Metropolis test, inside the replayed graph); ChainStats.update
-is the same recursion in NumPy, operation for operation, and the device's sums are its bits.  `res.stats.summarize()` forms the
-pooled mean, standard deviation, R-hat, batch-means effective sample size and Monte-Carlo standard error on the host.  Draws are the
-states after the proposals with GLOBAL index >= burn; everything is indexed by the global proposal index, so the sums do not depend
-on `block`, on graph or stream order, or on where a run was interrupted: `stats=ChainStats(resume=first.stats)` with the
-continuation rule above (rng="philox", proposal0 = the proposals already made) continues every sum.  stats=None: every path and bit
-as before, no launch and no buffer more.
+`metric=LowRankMetric` (laplace.py): a constant mass matrix M = I + V diag(lambda) V^T in the chain's own coordinates (under a
+prior the whitened ones), the Gauss-Newton Hessian of the potential at the MAP point (the `scaling` the reference's sampler hands to
+NUTS, bayesian_inference/inference.py:102-140,165).  The random stream is the same: the standard normals xi become momenta p =
+M^(1/2) xi, the position moves by eps M^-1 p and the kinetic energy is p^T M^-1 p / 2 (= |xi|^2 / 2 at the start).  A metric of rank
+zero is the identity and takes the plain paths.
 
-`model="romml" | "rom" | "fom"` on the two device chain functions: the inverse problem's three models (the reference's driver
-instantiates the full-order operator, pymc_func_bayes_inverse.py:174; the reduced ones are the alternatives beside it, :175-176).
-"fom" takes solver=Fin and data=; "rom" is the plain reduced model, without the learned correction.  The torch-op form evaluates
-through one adapter per model (the calls of estimate_MAP.objective(kind).device); the fused form through finrom_hmc_leapfrog_fom /
-_field_fom / _rom, built from two model-agnostic kernels (finrom_hmc_drift, finrom_hmc_kick).  The plain reduced model sees the
-field only through its sub-fin averages, so under a prior its fused step stays in whitened coordinates: theta = Sop m + (Sop U^T) v,
-grad_v = (Sop U^T)^T g_theta, no triangular product and no field during a trajectory.  `fom_value_and_grad` / `rom_value_and_grad`
-are the host callables for run_chains.  model="romml" (the default): every path, launch and bit as before.
+`rng=`, `seeds=`, `proposal0=`: "numpy" (the default) -- chain c draws from np.random.default_rng(seeds[c]), per proposal n normals
+for the momentum, then one uniform (_HostDraws); on the device the draws are made `block` proposals ahead and uploaded.  "philox" --
+a counter-based stream (philox.py; on the device finrom_hmc_draw, one launch per block of proposals, no host draw and no upload):
+Philox4x32-10 with key = seed and counter = (proposal, pair index, 0) for the Box-Muller pairs of the momentum, (proposal, 0, 1)
+for the uniform; seeds in [0, 2^64).  The draw of proposal p of the chain with seed s depends on (s, p) alone, so a chain is the
+same for any `block` and any deal of the chains over ranks.  THE CONTINUATION RULE: a run of p1 proposals followed by a run from
+its end state (K; V under a prior) with proposal0=p1 and an explicit mean= (the first run's; under a prior the prior carries it)
+walks the path of one uninterrupted run.  It needs rng="philox": a NumPy generator cannot be advanced to a proposal.
 
-`model="ml"` (surrogate=Surrogate, data=): the fourth model, the pure deep-learning surrogate; torch-op form by default.  `ml_form=
-"steps" | "trajectory"` on the two device chain functions moves its trajectory into the library (csrc/hmc_ml.hip): a step as three
-launches (finrom_hmc_leapfrog_ml), or all n_leapfrog steps in ONE launch with a 1024-thread workgroup per chain
-(finrom_hmc_trajectory_ml), which leaves the bits of the composed steps.  Under a prior the field is folded into the first layer
-(dl_model.whiten_first_layer, Surrogate.whitened: W0' = U W0, b0' = b0 + W0^T mean) and the chain is the i.i.d. chain of that network
-with mean 0 and tau 1: no triangular product and no field during a trajectory.  ml_form=None: every path, launch and bit as before.
+`stats=ChainStats(burn, batch)`: what the reference's drivers take from the trace after the run (bayesian_inference/inference.py:
+175-214 `np.mean(trace, 0)`, `np.std(trace, 0)`, the misfit per draw; pymc_func_bayes_inverse.py:212-220) accumulated WHILE the
+chains run, so that no trace is kept: per chain and node the Welford mean and sum of squared deviations of the FIELD (under a prior
+the field, not the whitened state: its variance needs Cov(v) in full) and the Welford moments of the means of batches of `batch`
+consecutive draws, per chain the misfit and the accept flag after every proposal.  On the device that is one launch per proposal
+(finrom_hmc_stats_update, behind the Metropolis test, inside the replayed graph); ChainStats.update is the same recursion in NumPy,
+operation for operation, and the device's sums are its bits.  `res.stats.summarize()` forms the pooled mean, standard deviation,
+R-hat, batch-means effective sample size and Monte-Carlo standard error on the host.  Draws are the states after the proposals with
+GLOBAL index >= burn; everything is indexed by the global proposal index, so the sums do not depend on `block`, on graph or stream
+order, or on where a run was interrupted: `stats=ChainStats(resume=first.stats)` with the continuation rule continues every sum.
 
-`correct=` on the three chain functions: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under
-a surrogate -- model="romml" or "rom" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway,
-under the surrogate's Hamiltonian; the end point then gets ONE full-order forward solve (QoI only: no adjoint, no gradient), and
-stage 2 accepts a candidate that passed stage 1 with probability min(1, w(k') / w(k)), w = exp(-D), D = c_lik (loss_FOM -
-loss_surrogate).  The priors cancel in w; stage 1 is reversible for the surrogate's posterior, so the two stages together are
-reversible for the full-order posterior (the one the reference samples, pymc_func_bayes_inverse.py:174) at one forward solve per
-proposal instead of n_leapfrog value-and-gradient calls.  run_chains takes a callable (fom_value(Fin, data)) and is the NumPy
-statement; the device functions take the Fin.  Lockstep solves all C end points, also those stage 1 stopped.  The second uniform is
-one more draw of the chain's generator per proposal (rng="numpy") or Philox counter word 2 (philox.draw_block_stage2,
-finrom_hmc_draw_stage2).  The result gains accept1 [C] (proposals past stage 1; accept is the final count), correction
-[proposals + 1, C] (row 0 the start's D, row q the candidate's: the surrogate's log-likelihood error along the chain) and n_fom;
-stats= records the full-order misfit.  Not with model="fom", not with ChainStats(resume=...); the fused form has no metric form.
-correct=None: every path, launch and bit as before."""
+`model=`, `solver=`, `surrogate=`, `data=` (device functions): which of the inverse problem's models the chains evaluate (the
+reference's driver instantiates the full-order operator, pymc_func_bayes_inverse.py:174; the reduced ones are the alternatives
+beside it, :175-176).  "romml" (the default): solver_r with a device error model.  "rom": solver_r, the plain reduced model without
+the learned correction; it sees the field only through its sub-fin averages, so under a prior its fused step stays in whitened
+coordinates: theta = Sop m + (Sop U^T) v, grad_v = (Sop U^T)^T g_theta, no triangular product and no field during a trajectory.
+"fom": solver=Fin and data=.  "ml": surrogate=Surrogate and data=, the pure deep-learning surrogate (the reference's
+MLSolverWrapper); an evaluation is finrom_mlp_misfit_grad.  solver_r may be None for "fom" and "ml".
+
+`ml_form=` (device functions, model="ml" only): None -- the torch-op form.  "steps" | "trajectory" -- the trajectory inside the
+library (csrc/hmc_ml.hip): a step as three launches (finrom_hmc_leapfrog_ml), or all n_leapfrog steps in ONE launch with a
+1024-thread workgroup per chain (finrom_hmc_trajectory_ml), which leaves the bits of the composed steps.  Under a prior the field
+is folded into the first layer (dl_model.whiten_first_layer, Surrogate.whitened: W0' = U W0, b0' = b0 + W0^T mean) and the chain is
+the i.i.d. chain of that network with mean 0 and tau 1.  With an ml_form nothing falls back to the torch-op form.
+
+`correct=`: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under a surrogate -- model "romml",
+"rom" or "ml" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway, under the surrogate's
+Hamiltonian; the end point then gets ONE full-order forward solve (QoI only: no adjoint, no gradient), and stage 2 accepts a
+candidate that passed stage 1 with probability min(1, w(k') / w(k)), w = exp(-D), D = c_lik (loss_FOM - loss_surrogate).  The
+priors cancel in w; stage 1 is reversible for the surrogate's posterior, so the two stages together are reversible for the
+full-order posterior (the one the reference samples, pymc_func_bayes_inverse.py:174) at one forward solve per proposal instead of
+n_leapfrog value-and-gradient calls.  run_chains takes a callable (fom_value(Fin, data)) and is the NumPy statement of
+finrom_hmc_end_stage2; the device functions take the Fin.  Lockstep solves all C end points, also those stage 1 stopped.  The second
+uniform is one more draw of the chain's generator per proposal, behind the first and whatever stage 1 said (rng="numpy"), or Philox
+counter word 2 (philox.draw_block_stage2, finrom_hmc_draw_stage2).  The result gains accept1 [C] (proposals past stage 1; accept
+is the final count), correction [proposals + 1, C] (row 0 the start's D, row q the candidate's: the surrogate's log-likelihood error
+along the chain) and n_fom = proposals + 1; stats= records the full-order misfit.  Not with model="fom" (nothing to correct), not
+with ChainStats(resume=...); the fused form has no metric form.
+
+`record=`: a set of evaluation indices whose (input, loss, gradient) are kept in `recorded` for parity checks; on the device the
+proposals that hold one run in stream order.  `keep_trace=`: the states after every proposal, row 0 the start.  `graph=`, `block=`
+(device functions): replay a captured proposal or launch in stream order; how many proposals' draws a block holds."""
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -429,7 +444,7 @@ def _device_draw(seeds64, dev, stage2=False):
 
 
 def _check_correct(correct, stats, who, model=None):
-    """Delayed acceptance corrects a surrogate, and this version does not continue its sums."""
+    """Delayed acceptance corrects a surrogate, and its sums are not continued."""
     if correct is None:
         return
     if model == "fom":
@@ -447,32 +462,45 @@ def _check_metric(metric, n):
     return metric
 
 
+class _HostDraws:
+    """rng="numpy": chain c draws from np.random.default_rng(seeds[c]), per proposal n standard normals (the momentum), one uniform
+    and, under correct=, a second uniform behind it.  Each chain has its own generator and no draw depends on the state, so a
+    proposal's uniforms may be drawn with its momentum, and proposals ahead of the chain."""
+
+    def __init__(self, seeds, n):
+        self.rngs, self.n = [np.random.default_rng(s) for s in seeds], n
+
+    def block(self, nb, second=False, rows=None):
+        """The next nb proposals -> P [rows, C, n], log u [rows, C], second log u [rows, C] (zeros unless second); rows >= nb
+        (default nb), the rows behind nb zero."""
+        rows = nb if rows is None else rows
+        C = len(self.rngs)
+        P, lu, lu2, u = np.zeros((rows, C, self.n)), np.zeros((rows, C)), np.zeros((rows, C)), np.ones((2, C))
+        for j in range(nb):
+            for c, r in enumerate(self.rngs):
+                P[j, c] = r.standard_normal(self.n)
+                u[0, c] = r.uniform()
+                if second:
+                    u[1, c] = r.uniform()
+            with np.errstate(divide="ignore"):
+                lu[j], lu2[j] = np.log(u[0]), np.log(u[1])
+        return P, lu, lu2
+
+
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None, correct=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
     samples whose reduced operator was not positive definite (treated as infinite potential: the proposal is rejected).
-    record: optional set of evaluation indices whose (input, loss, gradient) are kept for parity checks.
-    prior: None (i.i.d. N(mean, tau^2) per node; mean None: the start points) or a GaussianFieldPrior: then K0 holds WHITENED
-    start points v (prior.whiten of a field), mean must be None (the prior carries it) and tau is unused; value_and_grad still
-    receives fields, and `recorded` still holds (field, loss, field gradient).
-    metric: None (identity mass) or a LowRankMetric in the chain's own coordinates (with a prior: the whitened ones).
-    rng: "numpy" -- chain c draws from np.random.default_rng(seeds[c]): n normals for the momentum, then one uniform, per proposal;
-    "philox" -- proposal i of this call takes philox.draw_block's draw of GLOBAL proposal proposal0 + i for seed seeds[c] (Philox4x32-10,
-    key = seed, counter = (proposal, pair index, 0) for the Box-Muller pairs of the momentum and (proposal, 0, 1) for the uniform;
-    seeds in [0, 2^64)).  Continuation: a run of p1 proposals, then a run from its end state (K, or V under a prior) with
-    proposal0=p1 and the first run's mean passed explicitly, is the uninterrupted run.  proposal0 != 0 needs rng="philox".
-    stats: None or a ChainStats (module docstring): `stats` of the result is then the started ChainStats of this run -- the moments
-    of the chains' FIELDS after every proposal with global index >= burn, misfit and accept flag per proposal.
-    correct: None, or f(K [C, n] fields) -> (loss [C], bad [C]) of the model the chain is to be exact for (fom_value): delayed
-    acceptance, the NumPy statement of finrom_hmc_end_stage2 (module docstring).  The start and every trajectory's end point are
-    evaluated by it; the second uniform is one more uniform() of the chain's generator behind the first (rng="numpy"; drawn for
-    every proposal, whatever stage 1 said) or philox.draw_block_stage2's.  The result gains accept1, correction, n_fom and stage
-    [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted); stats' misfit is `correct`'s.
+    Under a prior it still receives fields, and `recorded` still holds (field, loss, field gradient).
+    Under rng="philox" proposal i of this call takes philox.draw_block's draw of GLOBAL proposal proposal0 + i for seed seeds[c].
+    correct: f(K [C, n] fields) -> (loss [C], bad [C]) of the model the chain is to be exact for (fom_value); it evaluates the start
+    and every trajectory's end point.
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
-    trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad) for parity checks;
-    with a prior also V [C, n], the whitened final states)."""
+    trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad), stats = the started
+    ChainStats of this run or None; with a prior also V [C, n], the whitened final states; under correct= also accept1, correction,
+    n_fom and stage [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted))."""
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains")
     _check_correct(correct, stats, "run_chains")
     _check_prior(prior, mean, "run_chains")
@@ -489,8 +517,8 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     else:
         pot = whitened_potential(value_and_grad, prior, sigma)
     if seeds64 is None:
-        rngs = [np.random.default_rng(s) for s in seeds]
-        assert len(rngs) == C
+        draws = _HostDraws(seeds, n)
+        assert len(draws.rngs) == C
     else:
         from . import philox
         assert len(seeds64) == C
@@ -529,10 +557,12 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                                                 max(0, (n_evals - 1) // n_leapfrog))
     while evals + n_leapfrog <= n_evals:
         if seeds64 is None:
-            P = np.stack([r.standard_normal(n) for r in rngs])
+            Pb, lub, lub2 = draws.block(1, second=correct is not None)
         else:
             Pb, lub = philox.draw_block(seeds64, proposal0 + proposals, 1, n)
-            P = Pb[0]
+            if correct is not None:
+                lub2 = philox.draw_block_stage2(seeds64, proposal0 + proposals, 1)
+        P, lu = Pb[0], lub[0]
         H0 = U + 0.5 * np.einsum("cn,cn->c", P, P)                  # (under a metric: |xi|^2 / 2 = p^T M^-1 p / 2)
         if metric is not None:
             P = metric.apply(P, "sqrt")
@@ -544,12 +574,9 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
             Pq = Pq - 0.5 * eps * dUq
         H1 = Uq + 0.5 * np.einsum("cn,cn->c", Pq, Pq if metric is None else metric.apply(Pq, "inv"))
         with np.errstate(over="ignore", invalid="ignore"):
-            lu = np.log(np.array([r.uniform() for r in rngs])) if seeds64 is None else lub[0]
             ok = np.isfinite(H1) & (lu < H0 - H1)
             if correct is not None:                                  # stage 2 (finrom_hmc_end_stage2's rule)
-                lu2 = (np.log(np.array([r.uniform() for r in rngs])) if seeds64 is None
-                       else philox.draw_block_stage2(seeds64, proposal0 + proposals, 1)[0])
-                ok1 = ok
+                lu2, ok1 = lub2[0], ok
                 cand_f, bad_f = correct(last["field"])
                 cand_f = np.asarray(cand_f, dtype=np.float64)
                 Dq = c_lik * (cand_f - np.asarray(last["loss"], dtype=np.float64))
@@ -627,8 +654,7 @@ def ml_value_and_grad(surrogate, data):
     return f
 
 
-MODELS = ("romml", "rom", "fom")
-MODELS += ("ml",)
+MODELS = ("romml", "rom", "fom", "ml")
 
 
 def _check_model(model, solver_r, solver, data, who, surrogate=None):
@@ -696,320 +722,395 @@ def _device_model(model, solver_r, solver, data_t, surrogate=None):
     return f
 
 
-def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
-    """`run_chains_device` with the trajectory's arithmetic INSIDE the library (round 4: finrom_hmc_begin / _leapfrog / _end,
-    include/finrom.h): a leapfrog step is the four launches of finrom_romml_grad and nothing else -- the position update rides in
-    front of the contraction and the error model's forward pass, the momentum update behind the gradient -- and a proposal is
-    1 + 4 n_leapfrog + 2 launches, captured once and replayed.  Same random numbers, same order of evaluations and the same chains
-    as `run_chains` (the host recursion) up to the rounding of fused multiply-adds; same return value as `run_chains_device`.
-    Raises _ffi.FinromError (FINROM_ERR_UNSUPPORTED) where the library has no one-sample form for the model -- callers fall back to
-    `run_chains_device(..., fused=False)`.
-    prior: a GaussianFieldPrior -- the state is whitened (K0 = v, mean None, tau unused) and a leapfrog step is
-    finrom_hmc_leapfrog_field: field kernel, the plain finrom_romml_grad launches at the field, pullback kernel with the momentum
-    update; finrom_hmc_begin / _end unchanged (mean 0, c_pri 1).  The trace is mapped to fields after the run.
-    metric: a LowRankMetric in the whitened coordinates (needs prior=; FINROM_ERR_UNSUPPORTED otherwise, so that fused=None falls
-    back): finrom_hmc_begin_metric, finrom_hmc_leapfrog_field_metric (one launch more per step: the velocity M^-1 p), _end_metric.
-    rng, proposal0: as for run_chains.  Under "philox" nothing is drawn on the host or uploaded: one finrom_hmc_draw launch per block,
-    in stream order between two blocks' replays, writes the draws of proposals proposal0 + done .. into the block buffers the
-    graph reads (standard normals, also under a metric); the chain does not depend on `block`.
-    stats: a ChainStats -- one finrom_hmc_stats_update launch behind finrom_hmc_end / _end_metric in every proposal (captured with
-    it), on the step's field buffer under a prior and on the end point's position buffer otherwise: no triangular product more.
-    model, solver: "fom" (solver=Fin, data= required) -- a step is finrom_hmc_leapfrog_fom (drift kernel, finrom_fom_gradient's
-    launches, kick kernel), under a prior finrom_hmc_leapfrog_field_fom; "rom" -- finrom_hmc_leapfrog_rom for both priors: A = Sop
-    under the i.i.d. prior, A = Sop U^T and theta0 = Sop mean in whitened coordinates, where no field exists during a trajectory
-    (stats= adds one finrom_sampler_field launch on the end point per proposal; recorded evaluations form field and field-space
-    gradient step by step).  No metric forms (FINROM_ERR_UNSUPPORTED: fused=None falls back).
-    correct: a Fin (model "romml" or "rom") -- delayed acceptance: finrom_hmc_end_stage1 in the place of finrom_hmc_end, then one
-    finrom_sampler_field launch on the end point for the whitened plain ROM alone (shared with stats=), finrom_fom_solve without w
-    on the "field" engine at the candidate's field (Kq[n_leapfrog & 1], or the step's field buffer under a prior; its flags cleared
-    in front), finrom_hmc_end_stage2, and the stats launch with the full-order misfit: still one linear chain, captured once.  The
-    start point's solve warms the full-order workspace before the capture; under "philox" one finrom_hmc_draw_stage2 launch per
-    block sits beside finrom_hmc_draw, under "numpy" a third uploaded block carries the second uniforms.  No metric form.
-    model "ml" (surrogate=) without ml_form: FINROM_ERR_UNSUPPORTED before anything is touched, so that fused=None falls back.
-    ml_form (model "ml" only; None: as above): "steps" -- a proposal is finrom_hmc_begin, n_leapfrog x finrom_hmc_leapfrog_ml (three
-    launches each: forward with the position update and the flag, walk back, kick), finrom_hmc_end; "trajectory" -- finrom_hmc_begin,
-    ONE finrom_hmc_trajectory_ml launch (a 1024-thread workgroup per chain runs all n_leapfrog steps), finrom_hmc_end.  The two forms
-    leave the same bits; evaluation 0 and the proposals that contain a recorded evaluation run in the step form under either.  Under
-    prior= the chain runs on surrogate.whitened(prior) -- the field folded into the first layer, W0' = U W0 and b0' = b0 + W0^T mean
-    -- with mean zeros and tau = 1: no triangular product and no field during a trajectory; K and trace are mapped to fields after
-    the run, stats= and correct= add one finrom_sampler_field launch on the end point per proposal, and `recorded` then holds
-    (index, v, loss, gradient WITH RESPECT TO v) -- whitened coordinates, not (field, loss, field gradient) as elsewhere.  rng=,
-    proposal0=, stats=, correct=Fin, keep_trace=, graph= and block= as for the other models; metric=: FINROM_ERR_UNSUPPORTED.
-    ValueError for an unknown ml_form and for ml_form beside another model, before anything touches the device.  The result carries
-    ml_form."""
-    seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_fused")
-    _check_model(model, solver_r, solver, data, "run_chains_fused", surrogate)
-    _check_correct(correct, stats, "run_chains_fused", model)
-    _check_ml_form(ml_form, model, "run_chains_fused")
-    from .. import _ffi
-    if model == "ml" and ml_form is None:
-        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): model='ml' has no fused leapfrog step "
-                               "(pass fused=False)")
-    if model == "ml":                                                # everything refused before the device is touched
-        if _check_metric(metric, np.shape(K0)[-1]) is not None:
-            raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog steps of model='ml' "
-                                   "have no metric form (pass fused=False and no ml_form)")
-        if np.shape(data)[-1] != surrogate.n_out or np.ndim(data) not in (1, 2):
-            raise ValueError(f"run_chains_fused: data must be [{surrogate.n_out}] or [C, {surrogate.n_out}], got {np.shape(data)}")
-        if np.shape(K0)[-1] != surrogate.n_in:
-            raise ValueError(f"run_chains_fused: the chains have {np.shape(K0)[-1]} coordinates, the surrogate {surrogate.n_in} inputs")
-        if not surrogate.device:
-            raise _ffi.FinromError("run_chains_fused needs the surrogate on the device (Surrogate(model, device=True))")
-    import ctypes as C
-    import torch
-    L = _ffi.lib()
-    if model == "fom":
-        fom = solver._engine("field")
-        fom._enable_gradient()
-        rom = mlp = Sop = None
-    elif model == "ml":                                              # under a prior: the field folded into the first layer
-        sur = surrogate.whitened(prior) if prior is not None else surrogate
-        rom, mlp, Sop = None, sur._dev, None
-    else:
-        rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
-        if model == "romml" and mlp is None:
-            raise _ffi.FinromError("run_chains_fused needs the error model on the device (a ResBnFcModel)")
-        solver_r._ensure_gradient()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    f64 = dict(dtype=torch.float64, device=dev)
-    i64 = dict(dtype=torch.int64, device=dev)
-    _check_prior(prior, mean, "run_chains_fused")
-    metric = _check_metric(metric, np.shape(K0)[-1])
-    if metric is not None and prior is None:
-        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog step under the i.i.d. "
-                               "prior has no metric form (pass prior=, or fused=False)")
-    if metric is not None and model != "romml":
-        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the fused leapfrog steps of model={model!r} "
-                               "have no metric form (pass fused=False)")
-    if metric is not None and correct is not None:
-        raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): delayed acceptance (correct=) has no metric "
-                               "form of the fused step (pass fused=False)")
-    K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
-    Cn, n = K.shape
-    if prior is not None:                                            # whitened: N(0, I), c_pri = 1
-        mean_t, tau = torch.zeros_like(K), 1.0
-        fs = prior.device()
-        fmean = torch.as_tensor(prior.mean, **f64)
-        F, grad_f = torch.zeros_like(K), torch.zeros_like(K)         # the step's field and misfit gradient
-        if metric is not None:
-            mh, vel = metric.device(), torch.zeros_like(K)           # the step's velocity M^-1 p
-    else:
-        mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (Cn, n)).copy(), **f64)
-    data_np = np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64)
-    data_t = torch.as_tensor(data_np, **f64)
-    per_sample = 1 if data_np.ndim == 2 else 0
-    whitened_rom = model == "rom" and prior is not None              # the step never forms the field
-    no_field = whitened_rom or (model == "ml" and prior is not None)   # (nor does the pure surrogate's: surrogate.whitened)
-    if model == "rom":                                               # theta = theta0 + A x, gradient A^T g_theta (x: k, or v under a prior)
-        S_np = np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64)
-        if not np.array_equal(S_np, solver_r.ops.S):                 # (one map serves theta and the chain rule)
-            raise _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): the reduced model's averaging operator "
-                                   "and dsigma_dk differ (pass fused=False)")
-        A_t = torch.as_tensor(np.ascontiguousarray(S_np @ prior.U.T) if prior is not None else S_np, **f64)
-        th0 = torch.as_tensor(S_np @ prior.mean, **f64) if prior is not None else None
-        theta_b, gth_b = torch.zeros(Cn, S_np.shape[0], **f64), torch.zeros(Cn, S_np.shape[0], **f64)
-    if seeds64 is None:
-        rngs = [np.random.default_rng(s) for s in seeds]
-        assert len(rngs) == Cn
-    else:
-        assert len(seeds64) == Cn
-        draw = _device_draw(seeds64, dev)
-    c_lik, c_pri = 1.0 / sigma ** 2, 1.0 / tau ** 2
-    n_prop = max(0, (n_evals - 1) // n_leapfrog)
-    B = max(1, min(block, n_prop))
-    Kq = [torch.empty_like(K), torch.empty_like(K)]
-    P, dUq, dU = torch.zeros_like(K), torch.zeros_like(K), torch.zeros_like(K)
-    U, H0, loss = torch.zeros(Cn, **f64), torch.zeros(Cn, **f64), torch.zeros(Cn, **f64)
-    info = torch.zeros(Cn, dtype=torch.int32, device=dev)
-    P_dev, lu_dev = torch.zeros(B, Cn, n, **f64), torch.zeros(B, Cn, **f64)
-    jt, pt, acc = torch.zeros(1, **i64), torch.zeros(1, **i64), torch.zeros(Cn, **i64)
-    trace = torch.zeros(n_prop + 1, Cn, n, **f64) if keep_trace else None
-    grad_rec = torch.zeros_like(K)                                   # raw misfit gradient, written only for recorded evaluations
-    st = _ffi.HmcState(C=Cn, n=n, eps=eps, c_lik=c_lik, c_pri=c_pri, mean=mean_t.data_ptr(), K=K.data_ptr(), U=U.data_ptr(),
-                       dU=dU.data_ptr(), Kq=(C.c_void_p * 2)(Kq[0].data_ptr(), Kq[1].data_ptr()), P=P.data_ptr(), dUq=dUq.data_ptr(),
-                       H0=H0.data_ptr(), P_block=P_dev.data_ptr(), lu_block=lu_dev.data_ptr(), jt=jt.data_ptr(), pt=pt.data_ptr(),
-                       accept=acc.data_ptr(), trace=trace.data_ptr() if trace is not None else None, loss=loss.data_ptr(),
-                       info=info.data_ptr())
-    st0 = _ffi.HmcState.from_buffer_copy(st)                         # evaluation 0: a "step" of length zero from K itself
-    st0.eps = 0.0
-    da = None
-    if correct is not None:                                          # delayed acceptance: the buffers of finrom_hmc_end_stage1 / _stage2
-        da = _DeviceDA(correct, Cn, n, data_t, per_sample, B, n_prop, dev)
-        if seeds64 is not None:
-            draw2 = _device_draw(seeds64, dev, stage2=True)
+class _DeviceChains:
+    """What device-resident chains are in either form: the checks, the state and block tensors, the draws, the capture recipe, the
+    block loop with its records, and the result.  `a` holds the chain function's arguments by name.  A form calls, in this order,
+    allocate(), start() behind its evaluation 0, start_stats(), capture() and run(); it supplies `proposal(rec)` -- one proposal on
+    torch's current stream on the tensors below, with note() behind every evaluation when rec.
 
-    def stream():
-        return torch.cuda.current_stream().cuda_stream
+    Tensors (static: a captured proposal reads and writes the same buffers at every replay): K [C, n], U [C], dU [C, n] the state with
+    its potential and gradient; P_dev [B, C, n], lu_dev [B, C] (da.lu2 under correct=) the draws of a block of B proposals; jt the
+    proposal inside the block, pt the proposal of the chain (trace row), acc [C] the accept counters; trace [proposals + 1, C, n] or
+    None; mean_t [C, n] (zeros under a prior, with c_pri = 1); data_t; fs, fmean the prior's sampler and mean (None without one);
+    da, ds the buffers of correct= and stats= (None without)."""
 
-    def leap(state, step, want_grad=False):
-        if model == "ml":
-            _ffi.check(L.finrom_hmc_leapfrog_ml(mlp._h, C.byref(state), step, data_t.data_ptr(), per_sample,
-                                                grad_rec.data_ptr() if want_grad else None, None, stream()), "finrom_hmc_leapfrog_ml")
-            return
-        if model == "fom":
-            if prior is not None:
-                _ffi.check(L.finrom_hmc_leapfrog_field_fom(fom._h, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
-                                                           C.byref(state), step, data_t.data_ptr(), per_sample, None, stream()),
-                           "finrom_hmc_leapfrog_field_fom")
-            else:                                                    # (the gradient between the model's launches and the kick: grad_rec)
-                _ffi.check(L.finrom_hmc_leapfrog_fom(fom._h, C.byref(state), step, data_t.data_ptr(), per_sample, grad_rec.data_ptr(),
-                                                     None, stream()), "finrom_hmc_leapfrog_fom")
-            return
-        if model == "rom":
-            _ffi.check(L.finrom_hmc_leapfrog_rom(rom._h, A_t.data_ptr(), th0.data_ptr() if th0 is not None else None, C.byref(state),
-                                                 step, data_t.data_ptr(), per_sample, theta_b.data_ptr(), gth_b.data_ptr(),
-                                                 grad_rec.data_ptr() if want_grad and prior is None else None, None, stream()),
-                       "finrom_hmc_leapfrog_rom")
-            return
-        if metric is not None:
-            _ffi.check(L.finrom_hmc_leapfrog_field_metric(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(),
-                                                          grad_f.data_ptr(), C.byref(state), step, data_t.data_ptr(), per_sample,
-                                                          None, None, mh._h, vel.data_ptr(), stream()),
-                       "finrom_hmc_leapfrog_field_metric")
-            Sop.used_on(stream())
-            return
-        if prior is not None:
-            _ffi.check(L.finrom_hmc_leapfrog_field(rom._h, mlp._h, Sop.ptr, fs._h, fmean.data_ptr(), F.data_ptr(), grad_f.data_ptr(),
-                                                   C.byref(state), step, data_t.data_ptr(), per_sample, None, None, stream()),
-                       "finrom_hmc_leapfrog_field")
-            Sop.used_on(stream())
-            return
-        _ffi.check(L.finrom_hmc_leapfrog(rom._h, mlp._h, Sop.ptr, C.byref(state), step, data_t.data_ptr(), per_sample,
-                                         grad_rec.data_ptr() if want_grad else None, None, None, stream()), "finrom_hmc_leapfrog")
-        Sop.used_on(stream())
+    def __init__(self, who, a):
+        self.a = a
+        self.seeds64 = _check_rng(a.rng, a.seeds, a.proposal0, who)
+        _check_model(a.model, a.solver_r, a.solver, a.data, who, a.surrogate)
+        _check_correct(a.correct, a.stats, who, a.model)
+        _check_ml_form(a.ml_form, a.model, who, a.fused)
 
-    def field_of(V):
-        _ffi.check(L.finrom_sampler_field(fs._h, fmean.data_ptr(), V.data_ptr(), Cn, F.data_ptr(), stream()), "finrom_sampler_field")
-
-    recorded, evals = [], 0
-
-    def note(step):
-        nonlocal evals
-        if record is not None and evals in record:
-            if whitened_rom:                                         # field and field-space gradient, formed for the record alone
-                recorded.append((evals, fs.field(Kq[(step + 1) & 1], mean=fmean).cpu().numpy().copy(), loss.cpu().numpy().copy(),
-                                 gth_b.cpu().numpy() @ S_np))
-            elif prior is not None and model != "ml":
-                recorded.append((evals, F.cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_f.cpu().numpy().copy()))
-            else:                                                    # (model "ml" under a prior: v and the gradient with respect to v)
-                recorded.append((evals, Kq[(step + 1) & 1].cpu().numpy().copy(), loss.cpu().numpy().copy(), grad_rec.cpu().numpy().copy()))
-        evals += 1
-
-    def proposal(rec=False):
-        if metric is not None:
-            _ffi.check(L.finrom_hmc_begin_metric(C.byref(st), mh._h, stream()), "finrom_hmc_begin_metric")
+    def allocate(self):
+        import torch
+        a = self.a
+        dev = torch.device("cuda", torch.cuda.current_device())
+        f64, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int64, device=dev)
+        K = self.K = torch.as_tensor(np.ascontiguousarray(a.K0, dtype=np.float64), **f64).clone()
+        Cn, n = K.shape
+        tau, self.fs, self.fmean = a.tau, None, None
+        if a.prior is not None:                                      # whitened: N(0, I), c_pri = 1
+            self.mean_t, tau = torch.zeros_like(K), 1.0
+            self.fs, self.fmean = a.prior.device(), torch.as_tensor(a.prior.mean, **f64)
         else:
-            _ffi.check(L.finrom_hmc_begin(C.byref(st), stream()), "finrom_hmc_begin")
-        if ml_form == "trajectory" and not rec:                      # all n_leapfrog steps in one launch: the step form's bits
-            _ffi.check(L.finrom_hmc_trajectory_ml(mlp._h, C.byref(st), n_leapfrog, data_t.data_ptr(), per_sample, stream()),
-                       "finrom_hmc_trajectory_ml")
+            self.mean_t = K.clone() if a.mean is None else torch.as_tensor(
+                np.broadcast_to(np.asarray(a.mean, dtype=np.float64), (Cn, n)).copy(), **f64)
+        self.data_t = torch.as_tensor(np.ascontiguousarray(a.solver_r.data if a.data is None else a.data, dtype=np.float64), **f64)
+        self.per_sample = 1 if self.data_t.ndim == 2 else 0
+        self.c_lik, self.c_pri = 1.0 / a.sigma ** 2, 1.0 / tau ** 2
+        self.n_prop = max(0, (a.n_evals - 1) // a.n_leapfrog)
+        B = self.B = max(1, min(a.block, self.n_prop))
+        self.U, self.dU = torch.zeros(Cn, **f64), torch.zeros_like(K)
+        self.P_dev, self.lu_dev = torch.zeros(B, Cn, n, **f64), torch.zeros(B, Cn, **f64)
+        self.jt, self.pt, self.acc = torch.zeros(1, **i64), torch.zeros(1, **i64), torch.zeros(Cn, **i64)
+        self.trace = torch.zeros(self.n_prop + 1, Cn, n, **f64) if a.keep_trace else None
+        self.da = self.ds = None
+        if a.correct is not None:
+            self.da = _DeviceDA(a.correct, Cn, n, self.data_t, self.per_sample, B, self.n_prop, dev)
+        if self.seeds64 is None:
+            self.host_draws = _HostDraws(a.seeds, n)
+            assert len(self.host_draws.rngs) == Cn
         else:
-            for i in range(n_leapfrog):                              # each step's input depends on the previous gradient
-                leap(st, i, want_grad=rec)
-                if rec:
-                    note(i)
-        if metric is not None:
-            _ffi.check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
-        elif da is not None:                                         # the surrogate's test, the full-order model at the end point, its test
-            _ffi.check(L.finrom_hmc_end_stage1(C.byref(st), n_leapfrog, da.ok1.data_ptr(), da.Uq.data_ptr(), stream()),
-                       "finrom_hmc_end_stage1")
-            if no_field:                                             # (no step formed the field; the sums below share it)
-                field_of(Kq[n_leapfrog & 1])
-            da.solve(F if prior is not None else Kq[n_leapfrog & 1])
-            _ffi.check(L.finrom_hmc_end_stage2(C.byref(st), n_leapfrog, C.byref(da.desc), stream()), "finrom_hmc_end_stage2")
-        else:
-            _ffi.check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
-        if ds is not None:                                           # (F holds the field of the trajectory's last step: the end point's)
-            if no_field and da is None:                              # (no step formed it: the end point's field, for the sums alone)
-                field_of(Kq[n_leapfrog & 1])
-            ds.update(F if prior is not None else Kq[n_leapfrog & 1], loss if da is None else da.cand)
+            assert len(self.seeds64) == Cn
+            self.draw = _device_draw(self.seeds64, dev)
+            self.draw2 = _device_draw(self.seeds64, dev, stage2=True) if self.da is not None else None
+        self.recorded, self.evals, self._moved = [], 0, []
 
-    # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
-    Kq[0].copy_(K)
-    leap(st0, 0, want_grad=True)                                     # Kq[1] = K + 0 * P, dUq = grad U / c_pri at K
-    note(0)
-    D = K - mean_t
-    Uv = torch.linalg.vecdot(D, D).mul_(0.5 * c_pri).add_(loss, alpha=c_lik)
-    U.copy_(torch.nan_to_num_(Uv, nan=float("inf"), posinf=float("inf"), neginf=float("inf")).masked_fill_(info.ne(0), float("inf")))
-    if not bool(torch.isfinite(U).all()):
-        raise ValueError("HMC start point has an indefinite reduced operator")
-    dU.copy_(dUq)
-    if trace is not None:
-        trace[0].copy_(K)
-    _restore_chain(stats, K, U, dU)
-    if no_field and (stats is not None or da is not None):          # the start point's field (also the field kernel's workspace, before a capture)
-        field_of(K)
-    if da is not None:                                               # evaluation 0 of the full-order model (warms its workspace up)
-        da.start(F if prior is not None else K, loss, c_lik)
-    ds = None if stats is None else _DeviceStats(stats, F if prior is not None else K, loss if da is None else da.loss_f, proposal0,
-                                                 n_prop, pt, acc)
-    g = None
-    if graph and n_prop > 0:
-        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else []) + (da.buffers() if da is not None else [])
-        state = [t.clone() for t in moved]
+    def note(self, read, *args):
+        """Behind an evaluation made in stream order: if `record` lists it, read(*args) -> (input, loss, gradient), device tensors
+        or arrays, is copied out."""
+        if self.a.record is not None and self.evals in self.a.record:
+            self.recorded.append((self.evals,) + tuple(x if isinstance(x, np.ndarray) else x.cpu().numpy().copy() for x in read(*args)))
+        self.evals += 1
+
+    def start(self, Uv, dUq):
+        """Behind evaluation 0: its potential Uv [C] and gradient dUq [C, n] (/ c_pri) become the state's (ValueError for a start that
+        is flagged or not finite), row 0 of the trace, and a resumed chain takes its saved values (_restore_chain)."""
+        import torch
+        self.U.copy_(Uv)
+        if not bool(torch.isfinite(self.U).all()):
+            raise ValueError("HMC start point has an indefinite reduced operator")
+        self.dU.copy_(dUq)
+        if self.trace is not None:
+            self.trace[0].copy_(self.K)
+        _restore_chain(self.a.stats, self.K, self.U, self.dU)
+
+    def start_stats(self, field0, loss0):
+        """stats=: the sums start from the start point's field [C, n] and the misfit [C] they record (the correcting model's under correct=)."""
+        if self.a.stats is not None:
+            self.ds = _DeviceStats(self.a.stats, field0, loss0, self.a.proposal0, self.n_prop, self.pt, self.acc)
+
+    def capture(self, proposal):
+        """-> proposal() captured as a torch.cuda.CUDAGraph, or None under graph=False or with no proposal to make.  The warm-up
+        torch's recipe asks for moves the state, the counters and the sums of stats= and correct=; they are put back (restore)."""
+        import torch
+        if not self.a.graph or self.n_prop == 0:
+            return None
+        moved = [self.K, self.U, self.dU, self.acc, self.jt, self.pt]
+        moved += (self.ds.buffers() if self.ds is not None else []) + (self.da.buffers() if self.da is not None else [])
+        self._moved = [(t, t.clone()) for t in moved]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                               # warm-up on a side stream, as torch's graph recipe asks
+        with torch.cuda.stream(side):                               # warm-up on a side stream
             proposal()
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             proposal()
-        for t, t0 in zip(moved, state):                             # (the warm-up moved the state; the capture does not run)
+        self.restore()                                              # (the warm-up moved the state; the capture does not run)
+        return g
+
+    def restore(self):
+        for t, t0 in self._moved:
             t.copy_(t0)
-        if trace is not None:
-            trace[1].zero_()
-    done = 0
-    while done < n_prop:
-        nb = min(B, n_prop - done)
-        if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
-            draw(proposal0 + done, nb, P_dev, lu_dev)
-            if da is not None:
-                draw2(proposal0 + done, nb, da.lu2)
-        else:
-            P_host, lu_host, lu2_host = np.zeros((B, Cn, n)), np.zeros((B, Cn)), np.zeros((B, Cn))
-            for j in range(nb):                                     # the host chain's draws, in its order
-                for c_, r in enumerate(rngs):
-                    P_host[j, c_] = r.standard_normal(n)
-                with np.errstate(divide="ignore"):
-                    lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-                    if da is not None:                              # (the second uniform, behind the first, for every proposal)
-                        lu2_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-            P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
-            if da is not None:
-                da.lu2.copy_(torch.from_numpy(lu2_host))
-        jt.zero_()
-        for j in range(nb):
-            first = 1 + (done + j) * n_leapfrog
-            if record is not None and any(first <= e < first + n_leapfrog for e in record):
-                assert evals == first
-                proposal(rec=True)
+
+    def run(self, proposal, g, **labels):
+        """All proposals, block by block -> the HmcResult (result).  A block's draws are one finrom_hmc_draw launch behind the previous
+        block's replays (rng="philox"), or the host chain's, drawn without waiting for the device -- they do not depend on the state,
+        so the host draws while the device works on the previous block -- and uploaded.  A proposal that holds an evaluation listed
+        in `record` runs in stream order, proposal(True); every other one is a replay of g, or proposal(False) without a graph."""
+        import torch
+        a, da, L = self.a, self.da, self.a.n_leapfrog
+        done = 0
+        while done < self.n_prop:
+            nb = min(self.B, self.n_prop - done)
+            if self.seeds64 is not None:
+                self.draw(a.proposal0 + done, nb, self.P_dev, self.lu_dev)
+                if da is not None:
+                    self.draw2(a.proposal0 + done, nb, da.lu2)
             else:
-                g.replay() if g is not None else proposal()
-                evals += n_leapfrog
-        done += nb
-    cs = ds.result(K, U, dU) if ds is not None else None
-    more = da.result() if da is not None else {}
-    if ml_form is not None:
-        more["ml_form"] = ml_form
-    if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=True, stats=cs, model=model,
-                             **more)
-    return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=True, stats=cs, model=model,
-                     **more)
+                P, lu, lu2 = self.host_draws.block(nb, second=da is not None, rows=self.B)
+                self.P_dev.copy_(torch.from_numpy(P)); self.lu_dev.copy_(torch.from_numpy(lu))
+                if da is not None:
+                    da.lu2.copy_(torch.from_numpy(lu2))
+            self.jt.zero_()
+            for j in range(nb):
+                first = 1 + (done + j) * L                          # evaluation indices of this proposal: first .. first + L - 1
+                if a.record is not None and any(first <= e < first + L for e in a.record):
+                    assert self.evals == first
+                    proposal(True)
+                else:
+                    g.replay() if g is not None else proposal(False)
+                    self.evals += L
+            done += nb
+        return self.result(graph=g is not None, **labels)
+
+    def result(self, graph, fused, **more):
+        """Synchronises.  Under a prior the states are v: K and trace are mapped to fields by the library, after the run (outside any
+        replayed graph), and V holds the whitened end states."""
+        K, V, trace = self.K, None, self.trace
+        cs = self.ds.result(K, self.U, self.dU) if self.ds is not None else None
+        da = self.da.result() if self.da is not None else {}
+        if self.fs is not None:
+            V, K = K, self.fs.field(K, mean=self.fmean)
+            if trace is not None:
+                trace = self.fs.field(trace.reshape(-1, K.shape[1]), mean=self.fmean).reshape(trace.shape)
+        return HmcResult(K=K.cpu().numpy(), **({} if V is None else {"V": V.cpu().numpy()}), accept=self.acc.cpu().numpy(),
+                         proposals=self.n_prop, n_evals=self.evals, recorded=self.recorded,
+                         trace=trace.cpu().numpy() if trace is not None else None, graph=graph, fused=fused, stats=cs,
+                         model=self.a.model, **da, **more)
 
 
-def _field_result(fs, fmean, V, acc, n_prop, evals, recorded, trace, **kw):
-    """Device chains under a prior: the whitened end states V and trace mapped to fields by the library, after the run (outside
-    any replayed graph)."""
-    n = V.shape[1]
-    K = fs.field(V, mean=fmean)
-    tr = fs.field(trace.reshape(-1, n), mean=fmean).reshape(trace.shape) if trace is not None else None
-    return HmcResult(K=K.cpu().numpy(), V=V.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals,
-                     recorded=recorded, trace=tr.cpu().numpy() if tr is not None else None, **kw)
+def _fused_form(a):
+    """The fused step form of (model, prior, metric), chosen before anything is allocated: raises what the combination is refused
+    with -- _ffi.FinromError with status FINROM_ERR_UNSUPPORTED where the library has no such step, so that fused=None falls back --
+    or returns bind(ch, Kq, loss) -- ch the allocated _DeviceChains, Kq the state's two position buffers, loss its misfit buffer --
+    which acquires the model's handles, allocates the form's own buffers and returns the form:
+      step(state, i, want_grad)  leapfrog step i on a finrom_hmc_state, on torch's current stream; want_grad: the raw misfit
+                                 gradient is kept for read()
+      read(i)                    (input, loss, gradient) of the evaluation step i made, as `recorded` holds it
+      field, needs_field         the tensor with the field of the point a step moved to (None: the position buffer is the field);
+                                 needs_field: no step forms it, one finrom_sampler_field launch does where stats= or correct= ask
+      mh                         the metric's handle (finrom_hmc_begin_metric / _end_metric around the trajectory), or None
+      trajectory(state)          all n_leapfrog steps in one launch (ml_form="trajectory"), or None.
+
+      model    prior  metric   step
+      romml    -      -        finrom_hmc_leapfrog
+      romml    field  -        finrom_hmc_leapfrog_field
+      romml    field  M        finrom_hmc_leapfrog_field_metric
+      fom      -      -        finrom_hmc_leapfrog_fom
+      fom      field  -        finrom_hmc_leapfrog_field_fom
+      rom      -      -        finrom_hmc_leapfrog_rom, A = Sop
+      rom      field  -        finrom_hmc_leapfrog_rom, A = Sop U^T, theta0 = Sop mean: whitened, no field during a trajectory
+      ml       any    -        finrom_hmc_leapfrog_ml (finrom_hmc_trajectory_ml), under a prior on surrogate.whitened(prior):
+                               whitened, no field during a trajectory, and read() gives (v, loss, gradient with respect to v)."""
+    from .. import _ffi
+    model, prior, solver_r, surrogate = a.model, a.prior, a.solver_r, a.surrogate
+    n = np.shape(a.K0)[-1]
+
+    def unsupported(what):
+        return _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): {what}")
+
+    if model == "ml":                                                # everything refused before the device is touched
+        if a.ml_form is None:
+            raise unsupported("model='ml' has no fused leapfrog step (pass fused=False)")
+        metric = _check_metric(a.metric, n)
+        if metric is not None:
+            raise unsupported("the fused leapfrog steps of model='ml' have no metric form (pass fused=False and no ml_form)")
+        if np.shape(a.data)[-1] != surrogate.n_out or np.ndim(a.data) not in (1, 2):
+            raise ValueError(f"run_chains_fused: data must be [{surrogate.n_out}] or [C, {surrogate.n_out}], got {np.shape(a.data)}")
+        if n != surrogate.n_in:
+            raise ValueError(f"run_chains_fused: the chains have {n} coordinates, the surrogate {surrogate.n_in} inputs")
+        if not surrogate.device:
+            raise _ffi.FinromError("run_chains_fused needs the surrogate on the device (Surrogate(model, device=True))")
+        _check_prior(prior, a.mean, "run_chains_fused")
+    else:
+        if model == "romml" and solver_r._dev_model is None:
+            raise _ffi.FinromError("run_chains_fused needs the error model on the device (a ResBnFcModel)")
+        _check_prior(prior, a.mean, "run_chains_fused")
+        metric = _check_metric(a.metric, n)
+        if metric is not None and prior is None:
+            raise unsupported("the fused leapfrog step under the i.i.d. prior has no metric form (pass prior=, or fused=False)")
+        if metric is not None and model != "romml":
+            raise unsupported(f"the fused leapfrog steps of model={model!r} have no metric form (pass fused=False)")
+        if metric is not None and a.correct is not None:
+            raise unsupported("delayed acceptance (correct=) has no metric form of the fused step (pass fused=False)")
+        if model == "rom":                                           # theta = theta0 + A x, gradient A^T g_theta (x: k, or v under a prior)
+            S_np = np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64)
+            if not np.array_equal(S_np, solver_r.ops.S):             # (one map serves theta and the chain rule)
+                raise unsupported("the reduced model's averaging operator and dsigma_dk differ (pass fused=False)")
+
+    def bind(ch, Kq, loss):                                          # (a step holds, by name, every tensor it passes by address)
+        import ctypes as C
+        import torch
+        L, check = _ffi.lib(), _ffi.check
+        K, data_p, per = ch.K, ch.data_t.data_ptr(), ch.per_sample
+        f64 = dict(dtype=torch.float64, device=K.device)
+        grad_rec = torch.zeros_like(K)                               # raw misfit gradient, written only for recorded evaluations
+        form = SimpleNamespace(field=None, needs_field=False, mh=None, trajectory=None, read=lambda i: (Kq[(i + 1) & 1], loss, grad_rec))
+        if prior is not None:
+            F, grad_f = torch.zeros_like(K), torch.zeros_like(K)     # the step's field and misfit gradient
+            form.field, fs_h, fmean_p = F, ch.fs._h, ch.fmean.data_ptr()
+
+        def stream():
+            return torch.cuda.current_stream().cuda_stream
+
+        def kept(want_grad):
+            return grad_rec.data_ptr() if want_grad else None
+
+        if model == "ml":                                            # under a prior: the field folded into the first layer
+            mlp = (surrogate.whitened(prior) if prior is not None else surrogate)._dev
+            form.needs_field = prior is not None
+
+            def step(state, i, want_grad):
+                check(L.finrom_hmc_leapfrog_ml(mlp._h, C.byref(state), i, data_p, per, kept(want_grad), None, stream()),
+                      "finrom_hmc_leapfrog_ml")
+            if a.ml_form == "trajectory":
+                def trajectory(state):
+                    check(L.finrom_hmc_trajectory_ml(mlp._h, C.byref(state), a.n_leapfrog, data_p, per, stream()),
+                          "finrom_hmc_trajectory_ml")
+                form.trajectory = trajectory
+        elif model == "fom":
+            fom = a.solver._engine("field")
+            fom._enable_gradient()
+            if prior is not None:
+                form.read = lambda i: (F, loss, grad_f)
+
+                def step(state, i, want_grad):
+                    check(L.finrom_hmc_leapfrog_field_fom(fom._h, fs_h, fmean_p, F.data_ptr(), grad_f.data_ptr(), C.byref(state), i,
+                                                          data_p, per, None, stream()), "finrom_hmc_leapfrog_field_fom")
+            else:
+                def step(state, i, want_grad):                      # (the gradient between the model's launches and the kick: grad_rec)
+                    check(L.finrom_hmc_leapfrog_fom(fom._h, C.byref(state), i, data_p, per, grad_rec.data_ptr(), None, stream()),
+                          "finrom_hmc_leapfrog_fom")
+        elif model == "rom":
+            rom = solver_r._rom
+            solver_r._ensure_gradient()
+            A_t = torch.as_tensor(np.ascontiguousarray(S_np @ prior.U.T) if prior is not None else S_np, **f64)
+            th0 = torch.as_tensor(S_np @ prior.mean, **f64) if prior is not None else None
+            theta_b, gth_b = torch.zeros(K.shape[0], S_np.shape[0], **f64), torch.zeros(K.shape[0], S_np.shape[0], **f64)
+            if prior is not None:                                    # field and field-space gradient, formed for the record alone
+                form.needs_field = True
+                form.read = lambda i: (ch.fs.field(Kq[(i + 1) & 1], mean=ch.fmean), loss, gth_b.cpu().numpy() @ S_np)
+
+            def step(state, i, want_grad):
+                check(L.finrom_hmc_leapfrog_rom(rom._h, A_t.data_ptr(), th0.data_ptr() if th0 is not None else None, C.byref(state), i,
+                                                data_p, per, theta_b.data_ptr(), gth_b.data_ptr(), kept(want_grad and prior is None),
+                                                None, stream()), "finrom_hmc_leapfrog_rom")
+        else:
+            rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
+            solver_r._ensure_gradient()
+            if prior is not None:
+                form.read = lambda i: (F, loss, grad_f)
+            if metric is not None:
+                mh, vel = metric.device(), torch.zeros_like(K)      # the step's velocity M^-1 p
+                form.mh = mh
+
+                def step(state, i, want_grad):
+                    check(L.finrom_hmc_leapfrog_field_metric(rom._h, mlp._h, Sop.ptr, fs_h, fmean_p, F.data_ptr(), grad_f.data_ptr(),
+                                                             C.byref(state), i, data_p, per, None, None, mh._h, vel.data_ptr(),
+                                                             stream()), "finrom_hmc_leapfrog_field_metric")
+                    Sop.used_on(stream())
+            elif prior is not None:
+                def step(state, i, want_grad):
+                    check(L.finrom_hmc_leapfrog_field(rom._h, mlp._h, Sop.ptr, fs_h, fmean_p, F.data_ptr(), grad_f.data_ptr(),
+                                                      C.byref(state), i, data_p, per, None, None, stream()), "finrom_hmc_leapfrog_field")
+                    Sop.used_on(stream())
+            else:
+                def step(state, i, want_grad):
+                    check(L.finrom_hmc_leapfrog(rom._h, mlp._h, Sop.ptr, C.byref(state), i, data_p, per, kept(want_grad), None, None,
+                                                stream()), "finrom_hmc_leapfrog")
+                    Sop.used_on(stream())
+        form.step = step
+        return form
+    return bind
+
+
+def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
+                     keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
+                     stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
+    """Device-resident chains with the trajectory's arithmetic INSIDE the library (include/finrom.h).  A proposal is finrom_hmc_begin,
+    n_leapfrog steps of the form _fused_form chose -- each the model's own launches with the position update in front and the
+    momentum update behind -- and finrom_hmc_end; under metric= finrom_hmc_begin_metric, the metric step, finrom_hmc_end_metric;
+    under ml_form="trajectory" ONE finrom_hmc_trajectory_ml launch in the place of the steps (the steps' bits; evaluation 0 and the
+    proposals with a recorded evaluation run in the step form).  correct=Fin: finrom_hmc_end_stage1 in the place of finrom_hmc_end,
+    finrom_fom_solve without w at the end point's field (flags cleared in front), finrom_hmc_end_stage2.  stats=: one
+    finrom_hmc_stats_update launch behind that, on the end point's field.  Where the step forms no field (the whitened forms of
+    "rom" and "ml"), one finrom_sampler_field launch per proposal forms the end point's for correct= and stats= together.  All of it
+    is one linear chain of launches, captured once and replayed; a capture that fails raises.
+    Raises _ffi.FinromError (FINROM_ERR_UNSUPPORTED) where the library has no such step (_fused_form) before anything is allocated:
+    run_chains_device(fused=None) then takes the torch-op form.
+    Same random numbers, same order of evaluations and the same chains as run_chains up to the rounding of fused multiply-adds; the
+    result of run_chains_device with fused=True, and ml_form where one was named.  `recorded` holds (field, loss, field gradient);
+    for model="ml" under a prior (v, loss, gradient with respect to v): that chain runs on surrogate.whitened(prior) and knows no
+    field-space gradient."""
+    a = SimpleNamespace(fused=None, **locals())
+    ch = _DeviceChains("run_chains_fused", a)
+    bind = _fused_form(a)
+    import ctypes as C
+    import torch
+    from .. import _ffi
+    L, check = _ffi.lib(), _ffi.check
+    ch.allocate()
+    K, da = ch.K, ch.da
+    Cn, n = K.shape
+    f64 = dict(dtype=torch.float64, device=K.device)
+    Kq = [torch.empty_like(K), torch.empty_like(K)]
+    P, dUq = torch.zeros_like(K), torch.zeros_like(K)
+    H0, loss, info = torch.zeros(Cn, **f64), torch.zeros(Cn, **f64), torch.zeros(Cn, dtype=torch.int32, device=K.device)
+    st = _ffi.HmcState(C=Cn, n=n, eps=eps, c_lik=ch.c_lik, c_pri=ch.c_pri, mean=ch.mean_t.data_ptr(), K=K.data_ptr(), U=ch.U.data_ptr(),
+                       dU=ch.dU.data_ptr(), Kq=(C.c_void_p * 2)(Kq[0].data_ptr(), Kq[1].data_ptr()), P=P.data_ptr(), dUq=dUq.data_ptr(),
+                       H0=H0.data_ptr(), P_block=ch.P_dev.data_ptr(), lu_block=ch.lu_dev.data_ptr(), jt=ch.jt.data_ptr(),
+                       pt=ch.pt.data_ptr(), accept=ch.acc.data_ptr(), trace=ch.trace.data_ptr() if ch.trace is not None else None,
+                       loss=loss.data_ptr(), info=info.data_ptr())
+    st0 = _ffi.HmcState.from_buffer_copy(st)                         # evaluation 0: a "step" of length zero from K itself
+    st0.eps = 0.0
+    form = bind(ch, Kq, loss)
+    step, mh = form.step, form.mh
+
+    def stream():
+        return torch.cuda.current_stream().cuda_stream
+
+    def field_at(X):
+        """The tensor that holds the field of the point X the last step moved to (or of the start point)."""
+        if form.field is None:
+            return X
+        if form.needs_field:
+            check(L.finrom_sampler_field(ch.fs._h, ch.fmean.data_ptr(), X.data_ptr(), Cn, form.field.data_ptr(), stream()),
+                  "finrom_sampler_field")
+        return form.field
+
+    def proposal(rec=False):
+        if mh is not None:
+            check(L.finrom_hmc_begin_metric(C.byref(st), mh._h, stream()), "finrom_hmc_begin_metric")
+        else:
+            check(L.finrom_hmc_begin(C.byref(st), stream()), "finrom_hmc_begin")
+        if form.trajectory is not None and not rec:
+            form.trajectory(st)
+        else:
+            for i in range(n_leapfrog):                              # each step's input depends on the previous gradient
+                step(st, i, rec)
+                if rec:
+                    ch.note(form.read, i)
+        if mh is not None:
+            check(L.finrom_hmc_end_metric(C.byref(st), mh._h, n_leapfrog, stream()), "finrom_hmc_end_metric")
+        elif da is not None:                                         # the surrogate's test; the full-order model's follows below
+            check(L.finrom_hmc_end_stage1(C.byref(st), n_leapfrog, da.ok1.data_ptr(), da.Uq.data_ptr(), stream()), "finrom_hmc_end_stage1")
+        else:
+            check(L.finrom_hmc_end(C.byref(st), n_leapfrog, stream()), "finrom_hmc_end")
+        if da is not None or ch.ds is not None:
+            Fq = field_at(Kq[n_leapfrog & 1])                        # the end point's field: one launch at most, shared
+        if da is not None:
+            da.solve(Fq)
+            check(L.finrom_hmc_end_stage2(C.byref(st), n_leapfrog, C.byref(da.desc), stream()), "finrom_hmc_end_stage2")
+        if ch.ds is not None:
+            ch.ds.update(Fq, loss if da is None else da.cand)
+
+    # evaluation 0: the starting point (also warms the library up: workspaces, function attributes)
+    Kq[0].copy_(K)
+    step(st0, 0, True)                                               # Kq[1] = K + 0 * P, dUq = grad U / c_pri at K
+    ch.note(form.read, 0)
+    D = K - ch.mean_t
+    Uv = torch.linalg.vecdot(D, D).mul_(0.5 * ch.c_pri).add_(loss, alpha=ch.c_lik)
+    ch.start(torch.nan_to_num_(Uv, nan=float("inf"), posinf=float("inf"), neginf=float("inf")).masked_fill_(info.ne(0), float("inf")), dUq)
+    F0 = field_at(K) if stats is not None or da is not None else None   # (also warms the field kernel's workspace up, before a capture)
+    if da is not None:                                               # evaluation 0 of the full-order model (warms its workspace up)
+        da.start(F0, loss, ch.c_lik)
+    ch.start_stats(F0, loss if da is None else da.loss_f)
+    g = ch.capture(proposal)
+    if g is not None and ch.trace is not None:                       # (the warm-up's row; proposal 0 writes it again)
+        ch.trace[1].zero_()
+    return ch.run(proposal, g, fused=True, **({} if ml_form is None else {"ml_form": ml_form}))
 
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
@@ -1017,115 +1118,57 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
                       proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
-    steps of (a few elementwise kernels around ONE library call, finrom_romml_grad on the tensors in place), Hamiltonians,
-    accept / reject, state update -- is captured once in a HIP graph (torch.cuda.CUDAGraph: the library launches on torch's capture
-    stream) and replayed: one graph launch per proposal, no synchronisation until the chain ends.  The random numbers are the
-    host chain's: every chain's NumPy generator is drawn in the same order (n normals for the momentum, then one uniform), `block`
-    proposals ahead -- the draws do not depend on the state -- while the device works on the previous block, and uploaded
-    block by block; the graph picks its proposal's slice by a device-side counter.  (First version: one graph per leapfrog step
-    and one synchronisation per proposal; the ~25 small launches and two copies around each trajectory were a quarter of
-    the time, tools/graph_call_cost.py.)
+    steps, Hamiltonians, accept / reject, state update -- is captured once in a HIP graph (torch.cuda.CUDAGraph: the library
+    launches on torch's capture stream) and replayed: one graph launch per proposal, no synchronisation until the chain ends; the
+    graph picks its proposal's draws out of the block by a device-side counter.  graph=False: the same launches in stream order.
+    Proposals that contain an evaluation index listed in `record` run in stream order too, step by step, so that the evaluation's
+    input, loss and gradient can be copied out.
 
-    Proposals that contain an evaluation index listed in `record` run the same operations in stream order, step by step, so that
-    the evaluation's input, loss and gradient can be copied out.  graph=False: everything in stream order.
-
-    prior: a GaussianFieldPrior (run_chains: K0 whitened, mean None, tau unused); every evaluation is FieldSampler.field, the
-    romml call at the field, FieldSampler.pullback of its gradient (fused: finrom_hmc_leapfrog_field); K and trace are fields, V the
-    whitened end states.
-    metric: a LowRankMetric in the chain's own coordinates (run_chains); its maps are finrom_metric_apply launches on the static
-    tensors (engine.MetricHandle), fused: run_chains_fused's kernels (needs prior=).
-    rng, proposal0: as for run_chains (the same stream, the same continuation rule).  Under "philox" the host loop and the two uploads
-    per block are one finrom_hmc_draw launch per block, with first_proposal = proposal0 + the proposals done; the chain is then the
-    same for any `block`.
-    stats: a ChainStats -- one finrom_hmc_stats_update launch behind the state update of every proposal (captured with it), on the
-    last evaluation's field under a prior and on Kq otherwise; `stats` of the result as for run_chains, the device's sums.
-    model, solver: which of the inverse problem's three models the chains evaluate -- "romml" (solver_r with a device error model),
-    "rom" (solver_r, the plain reduced model) or "fom" (solver=Fin and data= required; solver_r may be None).  Here the evaluation
-    is one adapter per model (_device_model: the calls of estimate_MAP.objective(kind).device), everything around it unchanged, so
-    prior=, metric=, rng=, stats=, record=, keep_trace= and graph= serve all three; fused: run_chains_fused's steps (no metric forms
-    for "fom" and "rom": fused=None then takes this form).  ValueError for an unknown model, "fom" without solver= or data=, solver=
-    with another model.  `model` of the result names it.
-    Same chains as run_chains(romml_value_and_grad(solver_r), ..., rng=rng) up to the rounding of the elementwise updates (model=
-    "fom": fom_value_and_grad(solver, data); "rom": rom_value_and_grad(solver_r, data)).
-    model "ml", surrogate: the pure deep-learning surrogate (dl_model.Surrogate on the device; data= required, solver_r may be None):
-    an evaluation is finrom_mlp_misfit_grad, two launches; no fused form unless ml_form= names one ("steps" | "trajectory": run_chains_fused's
-    launches, see there; not with fused=False, no metric form, and nothing falls back to the torch-op form then).  Same chains as
-    run_chains(ml_value_and_grad(surrogate, data)); under prior= with ml_form: as run_chains(ml_value_and_grad(surrogate.whitened(prior),
-    data), V0, mean=0.0, tau=1.0) mapped through prior.field.
-    correct: a Fin, with model "romml" or "rom" (ValueError with "fom", and with ChainStats(resume=...)) -- delayed acceptance
-    (module docstring): the trajectory under the surrogate, one full-order forward solve at its end point, the second test.
-    Fused: run_chains_fused's launches (no metric form: fused=None then takes this one); here the rule of finrom_hmc_end_stage2 in
-    torch ops around correct.forward_batch(field, want_w=False) on device tensors, which serves metric= too.  Same chains as
-    run_chains(..., correct=fom_value(correct, data)).  The result gains accept1 [C], correction [proposals + 1, C] (row 0: the
-    start's D, row q: the candidate's) and n_fom = proposals + 1; stats' misfit is the full-order one.
-    Returns HmcResult(K [C, n] (NumPy), accept, proposals, n_evals, recorded, trace, graph: whether a graph was replayed)."""
-    seeds64 = _check_rng(rng, seeds, proposal0, "run_chains_device")
-    _check_model(model, solver_r, solver, data, "run_chains_device", surrogate)
-    _check_correct(correct, stats, "run_chains_device", model)
-    _check_ml_form(ml_form, model, "run_chains_device", fused)
+    fused=True: run_chains_fused.  fused=None (the default): run_chains_fused, and where it refuses the combination
+    (_ffi.FinromError) and no ml_form is named, the form below.  fused=False, the torch-op form: a step is a few elementwise torch
+    kernels around ONE model call (_device_model; under a prior FieldSampler.field in front of it and FieldSampler.pullback behind),
+    the metric's maps are finrom_metric_apply launches (engine.MetricHandle), correct= is the rule of finrom_hmc_end_stage2 in torch
+    ops around correct.forward_batch(field, want_w=False), stats= one finrom_hmc_stats_update launch behind the state update.  It
+    serves every model, prior and metric.  A capture that fails is warned about and the proposals run in stream order.
+    Same chains as run_chains over the model's host callable (romml_value_and_grad(solver_r), fom_value_and_grad(solver, data),
+    rom_value_and_grad(solver_r, data), ml_value_and_grad(surrogate, data)) up to the rounding of the elementwise updates.
+    Returns HmcResult(K [C, n] (NumPy; fields), V under a prior, accept, proposals, n_evals, recorded, trace, graph: whether a graph
+    was replayed, fused, stats, model; under correct= accept1, correction, n_fom; ml_form where one was named)."""
+    a = SimpleNamespace(**locals())
+    ch = _DeviceChains("run_chains_device", a)
     import torch
     metric = _check_metric(metric, np.shape(K0)[-1])
     if fused is None or fused:
-        # the trajectory's arithmetic inside the library (round 4); fused=None: fall back to the torch-op form below where the
-        # library has no one-sample form for this model (FINROM_ERR_UNSUPPORTED)
         from .. import _ffi
+        kw = dict(vars(a), metric=metric)
+        del kw["fused"]
         try:
-            return run_chains_fused(solver_r, K0, n_evals, seeds=seeds, eps=eps, n_leapfrog=n_leapfrog, sigma=sigma, tau=tau,
-                                    mean=mean, record=record, keep_trace=keep_trace, graph=graph, data=data, block=block,
-                                    prior=prior, metric=metric, rng=rng, proposal0=proposal0, stats=stats, model=model, solver=solver,
-                                    correct=correct, surrogate=surrogate, ml_form=ml_form)
+            return run_chains_fused(**kw)
         except _ffi.FinromError:
             if fused or ml_form is not None:
                 raise
     _check_prior(prior, mean, "run_chains_device")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    f64 = dict(dtype=torch.float64, device=dev)
-    K = torch.as_tensor(np.ascontiguousarray(K0, dtype=np.float64), **f64).clone()
+    ch.allocate()
+    K, U, dU, jt, pt, da, fs, fmean, mean_t, c_lik, c_pri = ch.K, ch.U, ch.dU, ch.jt, ch.pt, ch.da, ch.fs, ch.fmean, ch.mean_t, ch.c_lik, ch.c_pri
     C, n = K.shape
-    if prior is not None:                                            # whitened: N(0, I), c_pri = 1
-        mean_t, tau = torch.zeros_like(K), 1.0
-        fs = prior.device()
-        fmean = torch.as_tensor(prior.mean, **f64)
-    else:
-        mean_t = K.clone() if mean is None else torch.as_tensor(np.broadcast_to(np.asarray(mean, dtype=np.float64), (C, n)).copy(), **f64)
-    data_t = torch.as_tensor(np.ascontiguousarray(solver_r.data if data is None else data, dtype=np.float64), **f64)
-    model_eval = _device_model(model, solver_r, solver, data_t, surrogate)
-    if seeds64 is None:
-        rngs = [np.random.default_rng(s) for s in seeds]
-        assert len(rngs) == C
-    else:
-        assert len(seeds64) == C
-        draw = _device_draw(seeds64, dev)
-    c_lik, c_pri = 1.0 / sigma ** 2, 1.0 / tau ** 2
+    f64 = dict(dtype=torch.float64, device=K.device)
+    model_eval = _device_model(model, solver_r, solver, ch.data_t, surrogate)
     mh = metric.device() if metric is not None else None
-    n_prop = max(0, (n_evals - 1) // n_leapfrog)
-    B = max(1, min(block, n_prop))
-    # static tensors (the graph's operands): state K, U, dU | work Kq, Pq, D, dUq | inputs P_dev, lu_dev | counters
+    # work tensors (static, like the state: the graph's operands)
     Kq, Pq, D, dUq = (torch.empty_like(K) for _ in range(4))
-    U, dU = torch.zeros(C, **f64), torch.zeros_like(K)
-    P_dev, lu_dev = torch.zeros(B, C, n, **f64), torch.zeros(B, C, **f64)
     P0, lu = torch.zeros(1, C, n, **f64), torch.zeros(1, C, **f64)
-    jt = torch.zeros(1, dtype=torch.int64, device=dev)                # proposal inside the uploaded block
-    pt = torch.zeros(1, dtype=torch.int64, device=dev)                # proposal of the chain (trace row)
-    acc = torch.zeros(C, dtype=torch.int64, device=dev)
-    trace = torch.zeros(n_prop + 1, C, n, **f64) if keep_trace else None
     out = {}
-    da = None
-    if correct is not None:                                          # delayed acceptance: finrom_hmc_end_stage2's state and rule in torch ops
-        da = _DeviceDA(correct, C, n, data_t, 1 if data_t.ndim == 2 else 0, B, n_prop, dev)
-        lu2 = torch.zeros(1, C, **f64)
-        nan_c = torch.full((C,), float("nan"), **f64)
-        if seeds64 is not None:
-            draw2 = _device_draw(seeds64, dev, stage2=True)
+    if da is not None:                                               # delayed acceptance: finrom_hmc_end_stage2's state and rule in torch ops
+        lu2, nan_c = torch.zeros(1, C, **f64), torch.full((C,), float("nan"), **f64)
 
     def fom_misfit(Fq):
         """(loss_f [C], flagged [C]) of the correcting model at the fields Fq: one forward solve, no adjoint."""
         res = correct.forward_batch(Fq, want_w=False)
-        r = res["qoi"] - data_t
+        r = res["qoi"] - ch.data_t
         return (r * r).sum(dim=1).mul_(0.5), res["info"].ne(0)
 
     def evaluate():
-        """dUq (= grad U / c_pri), out <- value and gradient at Kq (all static tensors: the same buffers at every call once captured)."""
+        """dUq (= grad U / c_pri), out <- value and gradient at Kq."""
         Fq = fs.field(Kq, mean=fmean) if prior is not None else Kq  # (with a prior, Kq is v and the misfit is taken at its field)
         res = model_eval(Fq)
         gq = fs.pullback(res["grad"]) if prior is not None else res["grad"]
@@ -1134,10 +1177,8 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         dUq.masked_fill_(res["info"].ne(0)[:, None], 0.0)           # an indefinite reduced operator: no force, rejected below
         out["loss"], out["grad"], out["info"], out["field"] = res["loss"], res["grad"], res["info"], Fq
 
-    def step():
-        Kq.add_(Pq if mh is None else mh.apply(Pq, "inv"), alpha=eps)
-        evaluate()
-        Pq.add_(dUq, alpha=-eps * c_pri)                           # two half steps; the ends of a trajectory correct by +- eps/2
+    def read():
+        return out["field"], out["loss"], out["grad"]
 
     inf = float("inf")
 
@@ -1146,25 +1187,20 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         Uv = torch.add(torch.linalg.vecdot(D, D).mul_(0.5 * c_pri), out["loss"], alpha=c_lik)
         return torch.nan_to_num_(Uv, nan=inf, posinf=inf, neginf=inf).masked_fill_(out["info"].ne(0), inf)
 
-    recorded, evals = [], 0
-
-    def note():
-        nonlocal evals
-        if record is not None and evals in record:
-            recorded.append((evals, out["field"].cpu().numpy().copy(), out["loss"].cpu().numpy().copy(), out["grad"].cpu().numpy().copy()))
-        evals += 1
-
-    def proposal(hook=None):
+    def proposal(rec=False):
         """One proposal on the static tensors: momentum and log u of slice jt, trajectory, Metropolis test, state update."""
-        torch.index_select(P_dev, 0, jt, out=P0)
-        torch.index_select(lu_dev, 0, jt, out=lu)
+        ds = ch.ds
+        torch.index_select(ch.P_dev, 0, jt, out=P0)
+        torch.index_select(ch.lu_dev, 0, jt, out=lu)
         H0 = torch.add(U, torch.linalg.vecdot(P0[0], P0[0]), alpha=0.5)
         Kq.copy_(K); dUq.copy_(dU)
         torch.add(P0[0] if mh is None else mh.apply(P0[0], "sqrt"), dUq, alpha=-0.5 * eps * c_pri, out=Pq)     # first half step
         for _ in range(n_leapfrog):                                 # each step's input depends on the previous gradient
-            step()
-            if hook is not None:
-                hook()
+            Kq.add_(Pq if mh is None else mh.apply(Pq, "inv"), alpha=eps)
+            evaluate()
+            Pq.add_(dUq, alpha=-eps * c_pri)                       # two half steps; the ends of a trajectory correct by +- eps/2
+            if rec:
+                ch.note(read)
         Pq.add_(dUq, alpha=0.5 * eps * c_pri)                       # the last update was a whole step: back to a half
         Uq = potential_now()
         H1 = torch.add(Uq, torch.linalg.vecdot(Pq, Pq) if mh is None else mh.apply(Pq, "inv", want_quad=True)[1], alpha=0.5)
@@ -1179,10 +1215,10 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
             torch.where(ok, Dq, da.D, out=da.D); torch.where(ok, lossF, da.loss_f, out=da.loss_f)
             torch.where(good, lossF, nan_c, out=da.cand)
         torch.where(ok[:, None], Kq, K, out=K); torch.where(ok, Uq, U, out=U); torch.where(ok[:, None], dUq, dU, out=dU)
-        acc.add_(ok)
+        ch.acc.add_(ok)
         jt.add_(1); pt.add_(1)
-        if trace is not None:
-            trace.index_copy_(0, pt, K[None])
+        if ch.trace is not None:
+            ch.trace.index_copy_(0, pt, K[None])
         if da is not None:
             da.correction.index_copy_(0, pt, torch.where(good, Dq, nan_c)[None])
         if ds is not None:                                          # (out holds the last evaluation: the end point's)
@@ -1190,76 +1226,21 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
 
     Kq.copy_(K); Pq.zero_()
     evaluate()                                                      # evaluation 0: the starting point (also warms the library up)
-    note()
-    U.copy_(potential_now())
-    if not bool(torch.isfinite(U).all()):
-        raise ValueError("HMC start point has an indefinite reduced operator")
-    dU.copy_(dUq)
-    if trace is not None:
-        trace[0].copy_(K)
-    _restore_chain(stats, K, U, dU)
+    ch.note(read)
+    ch.start(potential_now(), dUq)
     if da is not None:                                               # evaluation 0 of the correcting model
         lossF, flagged = fom_misfit(out["field"])
         D0 = (lossF - out["loss"]).mul_(c_lik)
         if bool(flagged.any()) or not bool(torch.isfinite(lossF).all()) or not bool(torch.isfinite(D0).all()):
             raise ValueError("HMC start point: the correcting model is flagged or not finite there")
         da.loss_f.copy_(lossF); da.D.copy_(D0); da.correction[0].copy_(D0)
-    ds = None if stats is None else _DeviceStats(stats, out["field"], out["loss"] if da is None else da.loss_f, proposal0, n_prop, pt, acc)
-    g = None
-    if graph and n_prop > 0:
-        moved = [K, U, dU, acc, jt, pt] + (ds.buffers() if ds is not None else []) + (da.buffers() if da is not None else [])
-        state = [t.clone() for t in moved]
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                           # warm-up on a side stream, as torch's graph recipe asks
-                proposal()
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                proposal()
-            for t, t0 in zip(moved, state):                         # (the warm-up moved the state; the capture does not run)
-                t.copy_(t0)
-        except Exception as exc:                                    # no graph support for this sequence: plain stream order
-            import warnings
-            warnings.warn(f"hmc: HIP graph capture failed ({exc!r}); the proposals are launched kernel by kernel")
-            g = None
-            for t, t0 in zip(moved, state):
-                t.copy_(t0)
-    done = 0
-    while done < n_prop:
-        nb = min(B, n_prop - done)
-        if seeds64 is not None:                                     # the block's draws on the device, behind the previous block's replays
-            draw(proposal0 + done, nb, P_dev, lu_dev)
-            if da is not None:
-                draw2(proposal0 + done, nb, da.lu2)
-        else:
-            P_host, lu_host, lu2_host = np.zeros((B, C, n)), np.zeros((B, C)), np.zeros((B, C))
-            for j in range(nb):                                     # the host chain's draws, in its order (overlaps the device's
-                for c_, r in enumerate(rngs):                       #  work on the previous block: nothing here waits for it)
-                    P_host[j, c_] = r.standard_normal(n)
-                with np.errstate(divide="ignore"):
-                    lu_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-                    if da is not None:                              # (the second uniform, behind the first, for every proposal)
-                        lu2_host[j] = np.log(np.array([r.uniform() for r in rngs]))
-            P_dev.copy_(torch.from_numpy(P_host)); lu_dev.copy_(torch.from_numpy(lu_host))
-            if da is not None:
-                da.lu2.copy_(torch.from_numpy(lu2_host))
-        jt.zero_()
-        for j in range(nb):
-            first = 1 + (done + j) * n_leapfrog                     # evaluation indices of this proposal: first .. first + L - 1
-            if record is not None and any(first <= e < first + n_leapfrog for e in record):
-                assert evals == first
-                proposal(hook=note)
-            else:
-                g.replay() if g is not None else proposal()
-                evals += n_leapfrog
-        done += nb
-    cs = ds.result(K, U, dU) if ds is not None else None
-    more = da.result() if da is not None else {}
-    if prior is not None:
-        return _field_result(fs, fmean, K, acc, n_prop, evals, recorded, trace, graph=g is not None, fused=False, stats=cs, model=model,
-                             **more)
-    return HmcResult(K=K.cpu().numpy(), accept=acc.cpu().numpy(), proposals=n_prop, n_evals=evals, recorded=recorded,
-                     trace=trace.cpu().numpy() if trace is not None else None, graph=g is not None, fused=False, stats=cs, model=model,
-                     **more)
+    ch.start_stats(out["field"], out["loss"] if da is None else da.loss_f)
+    try:
+        g = ch.capture(proposal)
+    except Exception as exc:                                        # no graph support for this sequence: plain stream order
+        import warnings
+        warnings.warn(f"hmc: HIP graph capture failed ({exc!r}); the proposals are launched kernel by kernel")
+        g = None
+        ch.restore()
+    return ch.run(proposal, g, fused=False)
+
