@@ -1,6 +1,12 @@
-// Private to the host layer (finrom_api.hip, fom_band_tables.hip, rom_tables.hip): the handle structs behind
-// include/finrom.h's opaque pointers, and the few helpers one of those units defines and another calls.  No kernel source
-// includes this header.
+// Private to the host layer (api_runtime.hip, api_fom.hip, api_rom.hip, api_infer.hip, api_hmc.hip, fom_band_tables.hip,
+// rom_tables.hip): the handle structs behind include/finrom.h's opaque pointers, and the few helpers one of those units defines
+// and another calls.  No kernel source includes this header.  Who defines what is shared:
+//   api_runtime.hip      overlap_enabled (and finrom_core.h's set_error, CallGuard, Scratch, dev_free, defer_or_run,
+//                        ScopedKernelTimer)
+//   api_fom.hip          env_no_band, fom_chunk_samples, fom_solve_stages       (called by api_rom.hip: finrom_solve_pairs)
+//   api_infer.hip        field_prior_ws, romml_grad_impl (with struct HmcStep)  (called by api_hmc.hip)
+//   fom_band_tables.hip  validate_band, validate_band_mirror, derive_post_functionals, derive_pivot_records, check_pivot_records
+//   rom_tables.hip       what rom_tables.h declares
 #pragma once
 #include "finrom_internal.h"
 #include "mlp_surrogate.h"
@@ -114,7 +120,7 @@ int up(std::vector<void*>& owned, const T** dst, const T* host, size_t count) {
   return 0;
 }
 
-// the runtime part of finrom_api.hip
+// api_runtime.hip
 bool overlap_enabled();                    // finrom_set_overlap's flag (finrom_solve_pairs reads it)
 
 // fom_band_tables.hip (host only)
@@ -128,10 +134,18 @@ void derive_pivot_records(const finrom_fom_band_desc* a, const std::vector<doubl
 int check_pivot_records(const finrom_fom_band_desc* a, const std::vector<double>& cw, const std::vector<int>& piv_row,
                         const std::vector<int>& piv_off, const BandFinRec* fin_rec, const BandPostRec* post_rec);
 
-// the FOM half as finrom_solve_pairs runs it, in stages (finrom_api.hip)
+// the FOM half as finrom_solve_pairs runs it, in stages (api_fom.hip)
 bool env_no_band();                        // FINROM_NO_BAND, read once per process
 int64_t fom_chunk_samples(const FomDev& d, const BandDev* band = nullptr);
 // records = false: a half plan in the functional form sweeps on its tables although pivot records are installed
 int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages,
                      bool records = true);
+
+// api_infer.hip, for the HMC steps of api_hmc.hip
+int field_prior_ws(finrom_sampler_t h, int64_t S);
+// (hs: the call is a leapfrog step -- finrom_hmc_leapfrog: position update in front, momentum update behind; one-sample form only)
+struct HmcStep { const double* mom; double eps; double* k_out; HmcTail tail; const double* theta_parts_in; };
+int romml_grad_impl(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, const double* k, const double* data,
+                    int32_t data_per_sample, int64_t S, double* grad, double* loss, double* qoi_r, double* e_nn,
+                    int32_t* info, void* stream, const HmcStep* hs);
 }  // namespace finrom

@@ -47,7 +47,7 @@ struct ScopedKernelTimer {
   ~ScopedKernelTimer();
 };
 
-// ---- stream capture and device memory (finrom_api.hip) ---------------------------------------------------------------------
+// ---- stream capture and device memory (api_runtime.hip) --------------------------------------------------------------------
 // While a stream is being captured into a HIP graph (torch.cuda.graph: global capture mode) hipFree / hipMalloc / a synchronous
 // hipMemset from ANY thread are "unsafe" calls that invalidate the capture or wait on it.  The library therefore never issues
 // one while it knows of an open capture: frees and handle destructions are queued (dev_free, defer_or_run) and flushed by the
@@ -185,6 +185,7 @@ int launch_philox_normal(unsigned long long seed, int64_t first, int64_t S, int 
 int launch_hmc_draw(const unsigned long long* seeds, int64_t C, int n, int64_t first, int64_t B, double* P_block, double* lu_block,
                     hipStream_t st);
 int launch_hmc_draw_stage2(const unsigned long long* seeds, int64_t C, int64_t first, int64_t B, double* lu2_block, hipStream_t st);
+int launch_clear_info(int32_t* info, int64_t S, hipStream_t st);      // info[0 .. S) = 0, as a kernel node of a captured graph
 
 // frontal band sweep (fom_band.hip, finrom_fom_set_band): per-sample workspace [AB | L | Lx | y -> w], sample-blocked
 struct BandDev {

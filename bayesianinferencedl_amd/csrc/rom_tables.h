@@ -1,4 +1,4 @@
-// Host-only tables of the reduced model (rom_tables.hip): what finrom_rom_create / _set_mirror / _set_mirror_short (finrom_api.hip)
+// Host-only tables of the reduced model (rom_tables.hip): what finrom_rom_create / _set_mirror / _set_mirror_short (api_rom.hip)
 // need of them.
 #pragma once
 #include "finrom_core.h"

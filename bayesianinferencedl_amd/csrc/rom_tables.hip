@@ -1,5 +1,5 @@
 // Host-only tables of the reduced model: the descriptor validators, the pattern-uniform k-steps and their packers, the grouped
-// tables, the half lists of a mirror-symmetric ROM.  No kernel and no HIP runtime call (rom_tables.h: what finrom_api.hip uses).
+// tables, the half lists of a mirror-symmetric ROM.  No kernel and no HIP runtime call (rom_tables.h: what api_rom.hip uses).
 #include "rom_tables.h"
 
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Small helper kernels of the hot path: sub-fin averages, Gaussian-field sampler, difference.
+// Small helper kernels of the hot path: sub-fin averages, Gaussian-field sampler, difference, the info clear.
 #include "finrom_core.h"
 #include <algorithm>
 #include <type_traits>
@@ -550,6 +550,20 @@ int launch_sub_flagged(const double* a, double* b, const int* info, int n_obs, i
   int64_t blocks = (count + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(sub_flagged_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, info, n_obs, count, out);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
+// clears a call's info in front of kernels that only ever flag in (romml_grad_impl's forms other than the one-sample one; the HMC
+// steps around finrom_fom_gradient and finrom_rom_grad)
+// (by a kernel, not hipMemsetAsync: inside a captured graph the memset node cleared info in the first replay only, and the
+// chains of every later replay kept the flags they came with -- tests/test_gpu_hmc_leapfrog_field.py starts them at 5)
+__global__ __launch_bounds__(256) static void clear_info_kernel(int32_t* __restrict__ info, int64_t S) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < S) info[i] = 0;
+}
+int launch_clear_info(int32_t* info, int64_t S, hipStream_t st) {
+  hipLaunchKernelGGL(clear_info_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, info, S);
   FR_HIP(hipGetLastError());
   return 0;
 }

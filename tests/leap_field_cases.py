@@ -1,5 +1,5 @@
 """Reference and case builder for the leapfrog step in whitened coordinates (finrom_hmc_leapfrog_field / _field_metric,
-csrc/finrom_api.hip: hmc_velocity_kernel, field_prior_kernel<false> in its fused form, the plain finrom_romml_grad launches,
+csrc/api_hmc.hip: hmc_velocity_kernel, field_prior_kernel<false> in its fused form, the plain finrom_romml_grad launches,
 field_prior_kernel<true> with its tail), shared by tests/test_hmc_leapfrog_field_host.py (which ties this reference to
 hmc.run_chains and checks that the cases are what they claim) and tests/test_gpu_hmc_leapfrog_field.py (which checks the kernels
 against it).  Imports without a GPU.

@@ -1,5 +1,5 @@
 """The leapfrog step in whitened coordinates, driven directly on hand-made state (finrom_hmc_leapfrog_field / _field_metric,
-csrc/finrom_api.hip: hmc_velocity_kernel, field_prior_kernel<false> with the fused operand w = fma(eps, q, v) and its write-back,
+csrc/api_hmc.hip: hmc_velocity_kernel, field_prior_kernel<false> with the fused operand w = fma(eps, q, v) and its write-back,
 the plain finrom_romml_grad launches, field_prior_kernel<true> with its momentum tail) against the reference of
 tests/leap_field_cases.py (checked against hmc.run_chains in tests/test_hmc_leapfrog_field_host.py).  Three steps per case; after
 each one: the position update, the momentum update and its dU bit for bit against exact fused multiply-adds; the field bitwise the
