@@ -218,6 +218,8 @@ SIGNATURES = {
     "finrom_hmc_leapfrog_ml": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "finrom_hmc_trajectory_ml": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "finrom_hmc_nuts_ml": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "finrom_metric_create": (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "finrom_metric_destroy": (None, [C.c_void_p]),
     "finrom_metric_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -70,6 +70,18 @@ library (csrc/hmc_ml.hip): a step as three launches (finrom_hmc_leapfrog_ml), or
 is folded into the first layer (dl_model.whiten_first_layer, Surrogate.whitened: W0' = U W0, b0' = b0 + W0^T mean) and the chain is
 the i.i.d. chain of that network with mean 0 and tau 1.  With an ml_form nothing falls back to the torch-op form.
 
+`nuts=Nuts(max_depth)` (nuts.py): the No-U-turn sampler the reference runs (bayesian_inference/inference.py:165-166 `pm.NUTS(scaling=G_INV,
+max_treedepth=7, target_accept=0.98)`) in the place of the fixed-length trajectory and its Metropolis test: multinomial NUTS with the
+generalised U-turn criterion, identity mass, eps the caller's (no adaptation).  A call makes (n_evals - 1) // n_leapfrog transitions,
+the draws the same call makes without nuts=.  run_chains: nuts.transition_iterative over any callable, chain by chain.  Device
+functions: model="ml" alone -- a transition is ONE finrom_hmc_nuts_ml call (the tree's kernel, one 1024-thread workgroup per chain, and the counters'
+advance behind it: csrc/hmc_nuts.hip);
+it implies the library form (ml_form None or "trajectory").  It needs rng="philox" (momenta as before, the tree's direction bits and
+uniforms from counter words 3 and 4, philox.nuts_top / nuts_leaf).  The result gains tree [proposals, C, 4] int32 (depth, leapfrog
+steps, stop reason: 0 depth limit, 1 tree turned, 2 sub-tree turned, 3 diverged; moved) and accept_stat [proposals, C], the mean of
+min(1, exp(H0 - H)) over the leaves: what dual averaging would consume.  accept counts the transitions whose draw is not the point
+they started from.  Not with metric=, correct= or record=.
+
 `correct=`: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under a surrogate -- model "romml",
 "rom" or "ml" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway, under the surrogate's
 Hamiltonian; the end point then gets ONE full-order forward solve (QoI only: no adjoint, no gradient), and stage 2 accepts a
@@ -488,7 +500,7 @@ class _HostDraws:
 
 
 def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
-               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None, correct=None):
+               keep_trace=False, prior=None, metric=None, rng="numpy", proposal0=0, stats=None, correct=None, nuts=None):
     """Advance C = len(K0) chains in lockstep for `n_evals` value-and-gradient evaluations per chain.
 
     value_and_grad(K [C, n]) -> (loss [C], grad [C, n], bad [C] bool): ONE device call per leapfrog point; `bad` marks
@@ -500,8 +512,14 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     Returns HmcResult(K [C, n] final states (fields), accept [C] accepted proposals, proposals, n_evals (per chain),
     trace [proposals + 1, C, n] if keep_trace (fields), recorded = list of (eval index, K copy, loss, grad), stats = the started
     ChainStats of this run or None; with a prior also V [C, n], the whitened final states; under correct= also accept1, correction,
-    n_fom and stage [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted))."""
+    n_fom and stage [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted)); under nuts= also tree, accept_stat
+    and margin (_run_chains_nuts)."""
+    _check_nuts(nuts, rng, metric, correct, record, "run_chains")
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains")
+    if nuts is not None:
+        _check_prior(prior, mean, "run_chains")
+        return _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigma, tau, mean, keep_trace, prior, proposal0,
+                                stats, nuts)
     _check_correct(correct, stats, "run_chains")
     _check_prior(prior, mean, "run_chains")
     metric = _check_metric(metric, np.shape(K0)[-1])
@@ -601,6 +619,77 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                          trace=prior.field(np.stack(trace)) if keep_trace else None, stats=cs, **da)
     return HmcResult(K=K, accept=accept, proposals=proposals, n_evals=evals, recorded=recorded,
                      trace=np.stack(trace) if keep_trace else None, stats=cs, **da)
+
+
+def _check_nuts(nuts, rng, metric, correct, record, who):
+    """nuts=Nuts(max_depth): what the No-U-turn transition is refused beside, each with its reason."""
+    if nuts is None:
+        return
+    from .nuts import MAX_DEPTH_LIMIT
+    depth = getattr(nuts, "max_depth", None)
+    if depth is None or int(depth) != depth or not 1 <= depth <= MAX_DEPTH_LIMIT:
+        raise ValueError(f"{who}: nuts= takes Nuts(max_depth) with max_depth in 1 .. {MAX_DEPTH_LIMIT}, not {depth!r}")
+    if rng != "philox":
+        raise ValueError(f"{who}: nuts= needs rng='philox' (a NumPy generator cannot serve a data-dependent number of draws reproducibly)")
+    if metric is not None:
+        raise ValueError(f"{who}: nuts= with metric=: the No-U-turn transition has an identity mass (a rank-zero metric included: pass none)")
+    if correct is not None:
+        raise ValueError(f"{who}: nuts= with correct=: delayed acceptance is a Metropolis test, the No-U-turn transition has none")
+    if record is not None:
+        raise ValueError(f"{who}: nuts= with record=: a tree's evaluations have no fixed indices to list")
+
+
+def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigma, tau, mean, keep_trace, prior, proposal0, stats, nuts):
+    """run_chains under nuts=: (n_evals - 1) // n_leapfrog transitions of nuts.transition_iterative per chain, the momenta
+    philox.draw_block's.  Works for any callable; a chain's tree is its own, so the chains are evaluated one row at a time.  Under a
+    prior the chains move v with mean 0 and c_pri = 1 and the callable is wrapped in prior.field / prior.pullback.
+    The result gains tree [proposals, C, 4] int32 (depth, leapfrog steps, stop reason -- 0 depth limit, 1 tree turned, 2 sub-tree
+    turned, 3 diverged --, moved), accept_stat [proposals, C] (the mean of min(1, w) over the leaves) and margin (the smallest decision
+    margin of the run); accept counts the transitions whose draw is not the point they started from; n_evals is 1 + the largest
+    number of leaves any chain made."""
+    from . import nuts as N
+    from . import philox
+    K = np.array(K0, dtype=np.float64, copy=True)
+    C, n = K.shape
+    assert len(seeds64) == C
+    c_lik = 1.0 / sigma ** 2
+    if prior is None:
+        c_pri, field = 1.0 / tau ** 2, (lambda X: X)
+        mean = K.copy() if mean is None else np.broadcast_to(np.asarray(mean, dtype=np.float64), K.shape)
+        f = value_and_grad
+    else:
+        c_pri, field, mean = 1.0, prior.field, np.zeros_like(K)
+
+        def f(V):
+            loss, grad, bad = value_and_grad(prior.field(V))
+            return loss, prior.pullback(np.asarray(grad, dtype=np.float64)), bad
+    loss, grad, bad = f(K)                                           # evaluation 0: the starting point
+    loss, d = np.array(loss, dtype=np.float64), K - mean
+    dU = (c_lik / c_pri) * np.asarray(grad, dtype=np.float64) + d
+    U = c_lik * loss + 0.5 * c_pri * np.einsum("cn,cn->c", d, d)
+    if np.any(bad) or not np.all(np.isfinite(U)):
+        raise ValueError("HMC start point has an indefinite reduced operator")
+    n_prop = max(0, (n_evals - 1) // n_leapfrog)
+    trace = [np.array(field(K))] if keep_trace else None
+    accept = np.zeros(C, np.int64)
+    tree, accept_stat, margin = np.zeros((n_prop, C, 4), np.int32), np.zeros((n_prop, C)), np.inf
+    cs = None if stats is None else stats.begin(field(K), loss, proposal0, n_prop)
+    for q in range(n_prop):
+        P = philox.draw_block(seeds64, proposal0 + q, 1, n)[0][0]
+        for c in range(C):
+            r = N.transition_iterative(f, K[c], U[c], dU[c], loss[c], P[c], seed=seeds64[c], proposal=proposal0 + q, eps=eps, c_lik=c_lik,
+                                       c_pri=c_pri, mean=mean[c], max_depth=nuts.max_depth)
+            K[c], U[c], dU[c], loss[c] = r.k, r.U, r.dU, r.loss
+            tree[q, c], accept_stat[q, c], margin = r.tree, r.accept_stat, min(margin, r.margin)
+        accept += tree[q, :, 3]
+        if cs is not None:
+            cs.update(field(K), loss.copy(), tree[q, :, 3] != 0, proposal0 + q)
+        if keep_trace:
+            trace.append(np.array(field(K)))
+    more = dict(tree=tree, accept_stat=accept_stat, margin=margin, nuts=nuts.max_depth)
+    evals = 1 + (int(tree[:, :, 1].sum(axis=0).max()) if n_prop else 0)
+    return HmcResult(K=field(K).copy(), **({} if prior is None else {"V": K}), accept=accept, proposals=n_prop, n_evals=evals, recorded=[],
+                     trace=np.stack(trace) if keep_trace else None, stats=cs, **more)
 
 
 def romml_value_and_grad(solver_r):
@@ -740,6 +829,15 @@ class _DeviceChains:
         _check_model(a.model, a.solver_r, a.solver, a.data, who, a.surrogate)
         _check_correct(a.correct, a.stats, who, a.model)
         _check_ml_form(a.ml_form, a.model, who, a.fused)
+        _check_nuts(a.nuts, a.rng, a.metric, a.correct, a.record, who)
+        if a.nuts is not None:                                       # the device has the transition for one model, in one form
+            if a.model != "ml":
+                raise ValueError(f"{who}: nuts= on the device belongs to model='ml'; model={a.model!r} has the host statement "
+                                 f"(run_chains(..., nuts=))")
+            if a.fused is not None and not a.fused:
+                raise ValueError(f"{who}: nuts= is a library form (finrom_hmc_nuts_ml); fused=False asks for the torch-op form")
+            if a.ml_form == "steps":
+                raise ValueError(f"{who}: nuts= is one launch per transition; ml_form='steps' asks for three launches per step")
 
     def allocate(self):
         import torch
@@ -800,14 +898,14 @@ class _DeviceChains:
         if self.a.stats is not None:
             self.ds = _DeviceStats(self.a.stats, field0, loss0, self.a.proposal0, self.n_prop, self.pt, self.acc)
 
-    def capture(self, proposal):
+    def capture(self, proposal, extra=()):
         """-> proposal() captured as a torch.cuda.CUDAGraph, or None under graph=False or with no proposal to make.  The warm-up
         torch's recipe asks for moves the state, the counters and the sums of stats= and correct=; they are put back (restore)."""
         import torch
         if not self.a.graph or self.n_prop == 0:
             return None
         moved = [self.K, self.U, self.dU, self.acc, self.jt, self.pt]
-        moved += (self.ds.buffers() if self.ds is not None else []) + (self.da.buffers() if self.da is not None else [])
+        moved += (self.ds.buffers() if self.ds is not None else []) + (self.da.buffers() if self.da is not None else []) + list(extra)
         self._moved = [(t, t.clone()) for t in moved]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -902,7 +1000,7 @@ def _fused_form(a):
         return _ffi.FinromError(f"run_chains_fused failed (status {_ffi.ERR_UNSUPPORTED}): {what}")
 
     if model == "ml":                                                # everything refused before the device is touched
-        if a.ml_form is None:
+        if a.ml_form is None and a.nuts is None:
             raise unsupported("model='ml' has no fused leapfrog step (pass fused=False)")
         metric = _check_metric(a.metric, n)
         if metric is not None:
@@ -950,7 +1048,7 @@ def _fused_form(a):
 
         if model == "ml":                                            # under a prior: the field folded into the first layer
             mlp = (surrogate.whitened(prior) if prior is not None else surrogate)._dev
-            form.needs_field = prior is not None
+            form.needs_field, form.mlp = prior is not None, mlp
 
             def step(state, i, want_grad):
                 check(L.finrom_hmc_leapfrog_ml(mlp._h, C.byref(state), i, data_p, per, kept(want_grad), None, stream()),
@@ -1018,7 +1116,7 @@ def _fused_form(a):
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
-                     stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
+                     stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None, nuts=None):
     """Device-resident chains with the trajectory's arithmetic INSIDE the library (include/finrom.h).  A proposal is finrom_hmc_begin,
     n_leapfrog steps of the form _fused_form chose -- each the model's own launches with the position update in front and the
     momentum update behind -- and finrom_hmc_end; under metric= finrom_hmc_begin_metric, the metric step, finrom_hmc_end_metric;
@@ -1028,6 +1126,10 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     finrom_hmc_stats_update launch behind that, on the end point's field.  Where the step forms no field (the whitened forms of
     "rom" and "ml"), one finrom_sampler_field launch per proposal forms the end point's for correct= and stats= together.  All of it
     is one linear chain of launches, captured once and replayed; a capture that fails raises.
+    nuts=Nuts(max_depth) (model="ml"): a proposal is ONE finrom_hmc_nuts_ml call (the tree's kernel and the counters' advance) -- a whole No-U-turn transition of every chain, the
+    statement nuts.transition_iterative -- in the place of begin, steps and end; the momenta are finrom_hmc_draw's, finrom_sampler_field
+    and finrom_hmc_stats_update follow where prior= / stats= ask for them, under a prior the chain runs on surrogate.whitened(prior).
+    The result gains tree and accept_stat as run_chains has them.
     Raises _ffi.FinromError (FINROM_ERR_UNSUPPORTED) where the library has no such step (_fused_form) before anything is allocated:
     run_chains_device(fused=None) then takes the torch-op form.
     Same random numbers, same order of evaluations and the same chains as run_chains up to the rounding of fused multiply-adds; the
@@ -1070,6 +1172,17 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                   "finrom_sampler_field")
         return form.field
 
+    if nuts is not None:
+        seeds_t = torch.as_tensor(ch.seeds64.view(np.int64), dtype=torch.int64, device=K.device)
+        tree = torch.zeros(ch.n_prop, Cn, 4, dtype=torch.int32, device=K.device)
+        accept_stat = torch.zeros(ch.n_prop, Cn, **f64)
+
+    def transition(rec=False):
+        check(L.finrom_hmc_nuts_ml(form.mlp._h, C.byref(st), seeds_t.data_ptr(), proposal0, nuts.max_depth, ch.data_t.data_ptr(),
+                                   ch.per_sample, tree.data_ptr(), accept_stat.data_ptr(), stream()), "finrom_hmc_nuts_ml")
+        if ch.ds is not None:                                        # (Kq[0] and loss hold the draw: where it moved, the sums take it)
+            ch.ds.update(field_at(Kq[0]), loss)
+
     def proposal(rec=False):
         if mh is not None:
             check(L.finrom_hmc_begin_metric(C.byref(st), mh._h, stream()), "finrom_hmc_begin_metric")
@@ -1107,6 +1220,14 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     if da is not None:                                               # evaluation 0 of the full-order model (warms its workspace up)
         da.start(F0, loss, ch.c_lik)
     ch.start_stats(F0, loss if da is None else da.loss_f)
+    if nuts is not None:                                             # (loss is the state's misfit here: the warm-up moves it too)
+        g = ch.capture(transition, extra=[loss, Kq[0], tree, accept_stat])
+        if g is not None and ch.trace is not None:
+            ch.trace[1].zero_()
+        res = ch.run(transition, g, fused=True, nuts=nuts.max_depth, **({} if ml_form is None else {"ml_form": ml_form}))
+        res["tree"], res["accept_stat"] = tree.cpu().numpy(), accept_stat.cpu().numpy()
+        res["n_evals"] = 1 + (int(res["tree"][:, :, 1].sum(axis=0).max()) if ch.n_prop else 0)
+        return res
     g = ch.capture(proposal)
     if g is not None and ch.trace is not None:                       # (the warm-up's row; proposal 0 writes it again)
         ch.trace[1].zero_()
@@ -1115,7 +1236,7 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
 
 def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                       keep_trace=False, graph=True, data=None, block=32, fused=None, prior=None, metric=None, rng="numpy",
-                      proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None):
+                      proposal0=0, stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None, nuts=None):
     """`run_chains` with the chains RESIDENT ON THE DEVICE (torch tensors on the current CUDA device): positions, momenta,
     potentials, the Metropolis test and the accept counters never visit the host.  A whole PROPOSAL -- momentum in, n_leapfrog
     steps, Hamiltonians, accept / reject, state update -- is captured once in a HIP graph (torch.cuda.CUDAGraph: the library
@@ -1145,7 +1266,7 @@ def run_chains_device(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, 
         try:
             return run_chains_fused(**kw)
         except _ffi.FinromError:
-            if fused or ml_form is not None:
+            if fused or ml_form is not None or nuts is not None:
                 raise
     _check_prior(prior, mean, "run_chains_device")
     ch.allocate()

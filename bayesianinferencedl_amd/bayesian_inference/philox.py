@@ -6,6 +6,9 @@ For the chain with seed s (0 <= s < 2^64) and GLOBAL proposal index p, Philox4x3
     u2 in [0, 1), and Box-Muller turns them into the standard normals xi[2 jb], xi[2 jb + 1] (for odd n the last pair gives one);
   * Metropolis uniform: counter (p lo, p hi, 0, 1); a = (o1 << 32) | o0, u = ((a >> 11) + 1) 2^-53 in (0, 1], lu = log u <= 0, finite;
   * second-stage uniform (hmc.py correct=, finrom_hmc_draw_stage2): counter (p lo, p hi, 0, 2), the same conversion.
+  * the No-U-turn transition (hmc.py nuts=, nuts.py; on the device drawn inside finrom_hmc_nuts_ml): doubling j: counter (p lo, p hi, j,
+    3), direction = o2 & 1 (1: forward), u_top from (o1 o0); leaf m = 1, 2, ...: counter (p lo, p hi, m, 4), u_m from (o1 o0); both
+    uniforms (a >> 11) 2^-53 in [0, 1);
 A draw depends on (s, p) and on nothing else: a chain is the same for any block size, any deal of the chains over ranks, and for a
 run continued from its end state at the proposal index it stopped at."""
 from __future__ import annotations
@@ -105,3 +108,26 @@ def momentum(seed, p, n):
 def log_uniform(seed, p):
     """log u of the Metropolis test of proposal p of the chain with `seed`: finite and <= 0."""
     return float(draw_block([seed], p, 1, 1)[1][0, 0])
+
+
+def _nuts_words(seed, p, index, word):
+    """The output words of counter (p lo, p hi, index, word) under the key `seed`, as Python ints."""
+    s = int(check_seeds([seed])[0])
+    p, index = int(p), int(index)
+    if not 0 <= p < 1 << 63 or not 0 <= index < 1 << 32:
+        raise ValueError(f"rng='philox': proposal {p} or index {index} is out of range")
+    o = philox4x32_10([p & 0xFFFFFFFF, p >> 32, index, word], s & 0xFFFFFFFF, s >> 32)
+    return [int(w) for w in o]
+
+
+def nuts_top(seed, p, j):
+    """Doubling j of the NUTS transition (nuts.py) of proposal p of the chain with `seed`: counter (p lo, p hi, j, 3) ->
+    (forward: o2 & 1, u_top = ((o1 o0) >> 11) 2^-53 in [0, 1)).  A function of (seed, p, j) alone."""
+    o = _nuts_words(seed, p, j, 3)
+    return bool(o[2] & 1), float(((o[1] << 32) | o[0]) >> 11) * 2.0 ** -53
+
+
+def nuts_leaf(seed, p, m):
+    """Leaf m = 1, 2, ... of that transition: counter (p lo, p hi, m, 4) -> u_m = ((o1 o0) >> 11) 2^-53 in [0, 1)."""
+    o = _nuts_words(seed, p, m, 4)
+    return float(((o[1] << 32) | o[0]) >> 11) * 2.0 ** -53

@@ -351,6 +351,29 @@ int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, int32_
   return launch_hmc_ml_trajectory(m, h, n_steps, a->Kq[0], a->Kq[1], data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p,
                                   (float*)mlp->tape.p, out, a->loss, a->info, (hipStream_t)stream);
 }
+int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, const uint64_t* seeds, int64_t proposal0, int32_t max_depth,
+                       const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_nuts_ml")) return rc;
+  if (max_depth < 1 || max_depth > NUTS_MAX_DEPTH) {
+    set_error("hmc_nuts_ml: max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH)); return FINROM_ERR_ARG;
+  }
+  if (proposal0 < 0) { set_error("hmc_nuts_ml: proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (!seeds) { set_error("hmc_nuts_ml: null seeds"); return FINROM_ERR_ARG; }
+  double* out = nullptr;
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_nuts_ml")) return rc;
+  if (a->C == 0) return 0;
+  const MlpDev& m = mlp->d;
+  const int64_t wsd = hmc_nuts_ws_doubles(a->C, a->n);
+  if (int rc = mlp->nuts_ws.reserve((size_t)(wsd + (2 + NUTS_SCALARS) * a->C) * sizeof(double))) return rc;      // (grown outside a capture only)
+  NutsDev nd;
+  nd.max_depth = max_depth; nd.proposal0 = proposal0; nd.seeds = (const unsigned long long*)seeds;
+  nd.ws = (double*)mlp->nuts_ws.p; nd.wloss = nd.ws + wsd; nd.winfo = (int*)(nd.wloss + a->C); nd.scal = nd.wloss + 2 * a->C; nd.st_loss = a->loss;
+  nd.tree = tree; nd.accept_stat = accept_stat;
+  return launch_hmc_nuts_ml(m, h, nd, data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p, (float*)mlp->tape.p, out,
+                            (hipStream_t)stream);
+}
 
 // ---- low-rank metric (hmc_metric.hip) --------------------------------------------------------------------------------------------
 int finrom_metric_create(const double* Vt, const double* lam, int32_t n, int32_t rho, finrom_metric_t* out) {

@@ -104,7 +104,7 @@ void finrom_mlp_destroy(finrom_mlp_t h) {
   if (!h) return;
   for (void* p : h->owned) dev_free(p);
   h->tape.release(); h->theta.release(); h->gth.release(); h->shift.release(); h->qtmp.release(); h->etmp.release(); h->g0.release(); h->y0p.release(); h->thp.release();
-  h->sur_w.release(); h->sur_zero.release(); h->sur_bad.release(); h->hml_grad.release();
+  h->sur_w.release(); h->sur_zero.release(); h->sur_bad.release(); h->hml_grad.release(); h->nuts_ws.release();
   delete h;
 }
 int finrom_mlp_predict(finrom_mlp_t h, const double* k, int64_t S, double* e, void* stream) {

@@ -103,6 +103,7 @@ struct finrom_mlp_s {
   // finrom_mlp_misfit_grad (mlp_surrogate.hip): the tile form's padded weights (made by the first call that needs them, outside any
   // capture), the per-sample walk's zero operand, the tile form's row flags; which form the last call took
   Scratch sur_w, sur_zero, sur_bad;
+  Scratch nuts_ws;                     // finrom_hmc_nuts_ml: the trees' per-chain arrays, a leaf's misfit and flag behind them
   Scratch hml_grad;                    // finrom_hmc_leapfrog_ml without grad_out: the gradient between the walk back and the kick
   SurPad sur_pad; bool sur_ready = false;
   int64_t tile_min = 4096;      // (the measured crossover of the two forms at n = 1597: DESIGN 7)

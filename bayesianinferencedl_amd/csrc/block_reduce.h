@@ -50,4 +50,31 @@ __device__ __forceinline__ double block_max_256(double v, double* red) {
   return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
+// 1024 threads (the one-workgroup-per-chain kernels of hmc_nuts.hip): the same butterfly inside each of the 16 waves, then the 16 wave
+// sums added pairwise in index order, ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)) and so on up the tree.  Every thread gets the
+// sum.  red: 16 doubles of LDS per value; consecutive calls may share it.
+__device__ __forceinline__ double wave_sums_16(const double* r) {
+  return (((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))) +
+         (((r[8] + r[9]) + (r[10] + r[11])) + ((r[12] + r[13]) + (r[14] + r[15])));
+}
+__device__ __forceinline__ double block_sum_1024(double v, double* red) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return wave_sums_16(red);
+}
+
+// two block_sum_1024 at once (each value summed in the same order as alone: the same bits), one LDS exchange.  red: 32 doubles.
+__device__ __forceinline__ void block_sum2_1024(double& a, double& b, double* red) {
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { red[wave] = a; red[16 + wave] = b; }
+  __syncthreads();
+  a = wave_sums_16(red);
+  b = wave_sums_16(red + 16);
+}
+
 }  // namespace finrom

@@ -18,48 +18,11 @@
 // LDS: the input's n_in floats are dead once the first layer has been summed (mlp_forward_body's second barrier), so wave 0's
 // scratch -- the squared residuals, g, up, the flag: HMC_ML_SCRATCH bytes -- lies over them and the kernels' static LDS is
 // mlp_forward_body's alone (MLP_FORWARD_STATIC_LDS): n_in <= MLP_FORWARD_MAX_IN is exactly what fits 64 KB.
-#include "mlp_device.h"
-#include "mlp_surrogate.h"
-
-// (behind the headers: their device functions keep the contraction they have in mlp_surrogate.hip)
-#pragma clang fp contract(off)
+#include "hmc_ml_device.h"
 
 namespace finrom {
 
 namespace {
-
-constexpr int HMC_ML_THREADS = 1024;
-constexpr int HMC_ML_SCRATCH = MLP_MAX_W * 8 + 2 * MLP_MAX_W * 4 + 16;      // rr [64] doubles, g, up [64] floats, the flag
-
-struct MlScratch {
-  double* rr; float* g; float* up; int* flag;
-  __device__ explicit MlScratch(float* dyn) : rr((double*)dyn), g(dyn + 2 * MLP_MAX_W), up(dyn + 3 * MLP_MAX_W), flag((int*)(dyn + 4 * MLP_MAX_W)) {}
-};
-
-// k' = fma(eps, P, k) -> k_out and the network at it (tape, out), then by wave 0: loss[c] = 1/2 |data - out|^2 as sur_forward_kernel
-// sums it, info[c] = 1 where that is not finite (Surrogate._pack's rule), else 0; the flag also into LDS.  The waves behind the
-// first come back as soon as the first layer is summed.
-__device__ __forceinline__ void ml_forward_loss(const MlpDev& m, const double* k, const double* mom, double eps, double* k_out, int64_t c,
-                                                const double* __restrict__ data, int64_t data_stride, float* tape, double* out,
-                                                double* loss, int* info, float* dyn, int tid) {
-  mlp_forward_body<HMC_ML_THREADS>(m, k, c, nullptr, 0, tape, out, nullptr, nullptr, 0, nullptr, dyn, tid, mom, eps, k_out);
-  if (tid >= 64) return;
-  const MlScratch s(dyn);
-  if (tid < m.n_out) {
-    const double r = data[(data_stride ? c * data_stride : 0) + tid] - out[c * m.n_out + tid];
-    s.rr[tid] = r * r;
-  }
-  wave_sync();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int o = 0; o < m.n_out; ++o) t += s.rr[o];
-    const double l = 0.5 * t;
-    const int bad = __builtin_isfinite(l) ? 0 : 1;
-    loss[c] = l;
-    info[c] = bad;
-    *s.flag = bad;
-  }
-}
 
 __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_ml_forward_kernel(MlpDev m, const double* k, const double* mom, double eps,
                                                                         double* k_out, const double* __restrict__ data,
@@ -77,7 +40,7 @@ __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_ml_trajectory_kernel(MlpDe
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   const MlScratch s(dyn);
   const int64_t c = blockIdx.x;
-  const int tid = threadIdx.x, nw = m.n_w, n = m.n_in;
+  const int tid = threadIdx.x, n = m.n_in;
   for (int step = 0; step < n_steps; ++step) {          // (uniform over the workgroup, and so is every barrier below)
     const double* k = step & 1 ? kq1 : kq0;
     double* kn = step & 1 ? kq0 : kq1;
@@ -86,19 +49,7 @@ __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_ml_trajectory_kernel(MlpDe
     __syncthreads();
     const bool flagged = *s.flag != 0;
     for (int i = tid; i < n; i += HMC_ML_THREADS) {     // sur_backward_kernel's row, then hmc_kick_kernel's element
-      const float* __restrict__ wrow = m.W0 + (int64_t)i * nw;
-      float a4[4] = {0.f, 0.f, 0.f, 0.f};
-      int j = 0;
-      for (; j + 16 <= nw; j += 16) {
-        float wv[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) wv[u] = wrow[j + u];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) a4[u & 3] = fmaf(s.g[j + u], wv[u], a4[u & 3]);
-      }
-      for (; j < nw; ++j) a4[0] = fmaf(s.g[j], wrow[j], a4[0]);
-      const float acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      const double gr = -(double)acc;
+      const double gr = ml_grad_row(m, s.g, i);
       const int64_t o = c * n + i;
       if (flagged) { dUq[o] = 0.0; continue; }
       const double du = fma(coef, gr, kn[o] - mean[o]);
@@ -107,11 +58,6 @@ __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_ml_trajectory_kernel(MlpDe
     }
     __syncthreads();                                    // g and the flag have been read: the next step's input may overwrite them
   }
-}
-
-size_t hmc_ml_dyn_bytes(const MlpDev& m) {
-  const size_t in = (size_t)m.n_in * sizeof(float);
-  return in > (size_t)HMC_ML_SCRATCH ? in : (size_t)HMC_ML_SCRATCH;
 }
 
 }  // namespace

@@ -648,6 +648,34 @@ int finrom_hmc_leapfrog_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, int32_t
                            double* grad_out, double* out, void* stream);
 int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, int32_t n_steps, const double* data, int32_t data_per_sample,
                              void* stream);
+/* The No-U-turn sampler for the same chains (hmc.py model="ml" with nuts=Nuts(max_depth); the statement: bayesian_inference/nuts.py
+ * transition_iterative): ONE launch is one transition of every chain, one 1024-thread workgroup per chain, followed by the counters'
+ * advance.  It replaces finrom_hmc_begin, the steps and finrom_hmc_end.  Multinomial NUTS with the generalised U-turn criterion
+ * (Betancourt 2017), identity mass, st->eps the step size (no adaptation):
+ *   start      p0 = row jt of P_block (finrom_hmc_draw's), H0 = U + |p0|^2 / 2, both edges the state, rho = p0, W = 1, the candidate
+ *              the state itself;
+ *   doubling   j = 0 .. max_depth - 1: Philox counter (p lo, p hi, j, 3) under the chain's seed, p = proposal0 + *pt: direction o2 & 1
+ *              (1: forward), u_top from (o1 o0); 2^j leapfrog steps from that direction's edge, each finrom_hmc_leapfrog_ml's
+ *              arithmetic with full-step momenta: p1/2 = fma(-d h, dU, p), k' = fma(d eps, p1/2, k), dU' = fma(c_lik / c_pri, grad,
+ *              k' - mean), p' = fma(-d h, dU', p1/2), h = 0.5 eps c_pri;
+ *   leaf m     (1, 2, ... over the transition) dE = U' + |p'|^2 / 2 - H0; flagged, dE not finite or dE > 1000: the sub-tree is
+ *              discarded and the transition ends (stop reason 3).  Else w = exp(-dE), W_sub += w, u_m from counter (p lo, p hi, m, 4),
+ *              the sub-tree's candidate becomes the leaf when u_m W_sub < w, rho_sub += p'.  U-turns inside the sub-tree by O(depth)
+ *              checkpoints (nuts.py): turning discards the sub-tree and ends the transition (2);
+ *   adoption   the candidate is replaced when u_top W < W_sub; W += W_sub, rho += rho_sub, the edge moves; the transition ends when
+ *              rho . p_left <= 0 or rho . p_right <= 0 (1) or at max_depth (0).
+ * Both uniforms are ((o1 o0) >> 11) 2^-53 in [0, 1).  Sums (|p|^2, |k - mean|^2, the U-turn products) in a fixed order: thread t chains
+ * fused multiply-adds over i = t, t + 1024, ..., a butterfly inside each of the 16 waves, the wave sums pairwise in index order.
+ * On return chain c's K, U, dU and loss hold the draw (loss [C] is the STATE's misfit here: it must hold the start point's on the first
+ * call), Kq[0] its position (finrom_hmc_stats_update's cand), accept[c] += moved, trace row *pt + 1 the position, tree [rows x C x 4]
+ * row *pt = (depth, leapfrog steps, stop reason, moved) and accept_stat [rows x C] row *pt the mean of min(1, w) over the leaves (a
+ * diverged leaf counts 0); then jt and pt advance.  tree and accept_stat may be NULL.  P, dUq, H0, lu_block, Kq[1] and info are not used.
+ * Refused before any device call: a null state field, handle, data or seeds, c_pri == 0, proposal0 < 0, max_depth outside 1 .. 10,
+ * st->n other than the network's n_in (FINROM_ERR_ARG); n_in > finrom_mlp_forward_max_in() or C > 65535 (FINROM_ERR_UNSUPPORTED).
+ * C == 0: returns 0, no launch.  The per-chain workspace (edges, walker, candidates, rho, checkpoints) lives on the handle and grows in
+ * the first call with that C: that call is refused with FINROM_ERR_UNSUPPORTED and a message while a stream capture is open. */
+int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, const uint64_t* seeds, int64_t proposal0, int32_t max_depth,
+                       const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream);
 
 /* ---- Laplace-preconditioned HMC: a low-rank metric at the MAP point ------------------------------------------------------------- *
  * The reference's working sampler builds a low-rank Gauss-Newton Hessian of the misfit at the MAP point in prior-whitened
