@@ -228,6 +228,8 @@ SIGNATURES = {
                                                    C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
+    "finrom_hmc_nuts_ml_metric": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_stats_update": (C.c_int, [C.POINTER(HmcStats), C.c_void_p]),
     "finrom_hmc_end_stage1": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

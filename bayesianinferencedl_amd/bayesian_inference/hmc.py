@@ -81,6 +81,12 @@ uniforms from counter words 3 and 4, philox.nuts_top / nuts_leaf).  The result g
 steps, stop reason: 0 depth limit, 1 tree turned, 2 sub-tree turned, 3 diverged; moved) and accept_stat [proposals, C], the mean of
 min(1, exp(H0 - H)) over the leaves: what dual averaging would consume.  accept counts the transitions whose draw is not the point
 they started from.  Not with metric=, correct= or record=.
+`Nuts(max_depth, metric=LowRankMetric)`: the transition under the Laplace metric -- the reference's `scaling`, on the sampler object as
+it is there (the metric= keyword beside nuts= stays refused) -- in the chain's own coordinates: under prior= the whitened ones
+(LowRankMetric.from_jacobian(J, prior, sigma)), under the i.i.d. prior the field's.  The momenta are M^(1/2) xi of the same standard
+normals, the position moves by eps M^-1 p, the kinetic energy is p . M^-1 p / 2 and the U-turn criterion takes M^-1 p (nuts.py).  On the
+device a transition is ONE finrom_hmc_nuts_ml_metric call with metric.device(); a metric of rank zero or None is the call above, bit
+for bit.  A metric whose n is not the chains' is refused with both numbers.  The result gains metric_rho.
 
 `correct=`: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under a surrogate -- model "romml",
 "rom" or "ml" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway, under the surrogate's
@@ -632,7 +638,8 @@ def _check_nuts(nuts, rng, metric, correct, record, who):
     if rng != "philox":
         raise ValueError(f"{who}: nuts= needs rng='philox' (a NumPy generator cannot serve a data-dependent number of draws reproducibly)")
     if metric is not None:
-        raise ValueError(f"{who}: nuts= with metric=: the No-U-turn transition has an identity mass (a rank-zero metric included: pass none)")
+        raise ValueError(f"{who}: nuts= with metric=: the No-U-turn transition's metric belongs to the sampler object, pass it as "
+                         f"Nuts(max_depth, metric=...) (a rank-zero metric included: pass none beside nuts=)")
     if correct is not None:
         raise ValueError(f"{who}: nuts= with correct=: delayed acceptance is a Metropolis test, the No-U-turn transition has none")
     if record is not None:
@@ -646,12 +653,14 @@ def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigm
     The result gains tree [proposals, C, 4] int32 (depth, leapfrog steps, stop reason -- 0 depth limit, 1 tree turned, 2 sub-tree
     turned, 3 diverged --, moved), accept_stat [proposals, C] (the mean of min(1, w) over the leaves) and margin (the smallest decision
     margin of the run); accept counts the transitions whose draw is not the point they started from; n_evals is 1 + the largest
-    number of leaves any chain made."""
+    number of leaves any chain made.  Nuts(max_depth, metric=LowRankMetric): the transition under the metric (nuts.py), in the
+    chain's own coordinates -- under a prior the whitened ones, LowRankMetric.from_jacobian's; the result gains metric_rho."""
     from . import nuts as N
     from . import philox
     K = np.array(K0, dtype=np.float64, copy=True)
     C, n = K.shape
     assert len(seeds64) == C
+    metric = N.Nuts.metric_for(nuts, n, "run_chains")
     c_lik = 1.0 / sigma ** 2
     if prior is None:
         c_pri, field = 1.0 / tau ** 2, (lambda X: X)
@@ -678,7 +687,7 @@ def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigm
         P = philox.draw_block(seeds64, proposal0 + q, 1, n)[0][0]
         for c in range(C):
             r = N.transition_iterative(f, K[c], U[c], dU[c], loss[c], P[c], seed=seeds64[c], proposal=proposal0 + q, eps=eps, c_lik=c_lik,
-                                       c_pri=c_pri, mean=mean[c], max_depth=nuts.max_depth)
+                                       c_pri=c_pri, mean=mean[c], max_depth=nuts.max_depth, metric=metric)
             K[c], U[c], dU[c], loss[c] = r.k, r.U, r.dU, r.loss
             tree[q, c], accept_stat[q, c], margin = r.tree, r.accept_stat, min(margin, r.margin)
         accept += tree[q, :, 3]
@@ -686,7 +695,7 @@ def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigm
             cs.update(field(K), loss.copy(), tree[q, :, 3] != 0, proposal0 + q)
         if keep_trace:
             trace.append(np.array(field(K)))
-    more = dict(tree=tree, accept_stat=accept_stat, margin=margin, nuts=nuts.max_depth)
+    more = dict(tree=tree, accept_stat=accept_stat, margin=margin, nuts=nuts.max_depth, metric_rho=0 if metric is None else metric.rho)
     evals = 1 + (int(tree[:, :, 1].sum(axis=0).max()) if n_prop else 0)
     return HmcResult(K=field(K).copy(), **({} if prior is None else {"V": K}), accept=accept, proposals=n_prop, n_evals=evals, recorded=[],
                      trace=np.stack(trace) if keep_trace else None, stats=cs, **more)
@@ -838,6 +847,8 @@ class _DeviceChains:
                 raise ValueError(f"{who}: nuts= is a library form (finrom_hmc_nuts_ml); fused=False asks for the torch-op form")
             if a.ml_form == "steps":
                 raise ValueError(f"{who}: nuts= is one launch per transition; ml_form='steps' asks for three launches per step")
+            from .nuts import Nuts
+            self.nuts_metric = Nuts.metric_for(a.nuts, np.shape(a.K0)[-1], who)     # (refused here where its n is not the chains')
 
     def allocate(self):
         import torch
@@ -1176,10 +1187,16 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         seeds_t = torch.as_tensor(ch.seeds64.view(np.int64), dtype=torch.int64, device=K.device)
         tree = torch.zeros(ch.n_prop, Cn, 4, dtype=torch.int32, device=K.device)
         accept_stat = torch.zeros(ch.n_prop, Cn, **f64)
+        nmh = ch.nuts_metric.device() if ch.nuts_metric is not None else None      # (a rank-zero or absent metric: the plain tree)
 
     def transition(rec=False):
-        check(L.finrom_hmc_nuts_ml(form.mlp._h, C.byref(st), seeds_t.data_ptr(), proposal0, nuts.max_depth, ch.data_t.data_ptr(),
-                                   ch.per_sample, tree.data_ptr(), accept_stat.data_ptr(), stream()), "finrom_hmc_nuts_ml")
+        if nmh is not None:
+            check(L.finrom_hmc_nuts_ml_metric(form.mlp._h, C.byref(st), nmh._h, seeds_t.data_ptr(), proposal0, nuts.max_depth,
+                                              ch.data_t.data_ptr(), ch.per_sample, tree.data_ptr(), accept_stat.data_ptr(), stream()),
+                  "finrom_hmc_nuts_ml_metric")
+        else:
+            check(L.finrom_hmc_nuts_ml(form.mlp._h, C.byref(st), seeds_t.data_ptr(), proposal0, nuts.max_depth, ch.data_t.data_ptr(),
+                                       ch.per_sample, tree.data_ptr(), accept_stat.data_ptr(), stream()), "finrom_hmc_nuts_ml")
         if ch.ds is not None:                                        # (Kq[0] and loss hold the draw: where it moved, the sums take it)
             ch.ds.update(field_at(Kq[0]), loss)
 
@@ -1224,7 +1241,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         g = ch.capture(transition, extra=[loss, Kq[0], tree, accept_stat])
         if g is not None and ch.trace is not None:
             ch.trace[1].zero_()
-        res = ch.run(transition, g, fused=True, nuts=nuts.max_depth, **({} if ml_form is None else {"ml_form": ml_form}))
+        res = ch.run(transition, g, fused=True, nuts=nuts.max_depth, metric_rho=0 if ch.nuts_metric is None else ch.nuts_metric.rho,
+                     **({} if ml_form is None else {"ml_form": ml_form}))
         res["tree"], res["accept_stat"] = tree.cpu().numpy(), accept_stat.cpu().numpy()
         res["n_evals"] = 1 + (int(res["tree"][:, :, 1].sum(axis=0).max()) if ch.n_prop else 0)
         return res

@@ -26,7 +26,20 @@ the form the kernel executes.  Both report `margin`: the smallest relative gap b
 product relative to |rho| |p|, a selection test relative to its larger side), so that a test can require its inputs to decide clearly.
 
 `fma(a, x, y)` and `dot(x, y)` may be given: the defaults are the plain NumPy expressions; tests/hmc_cases.fma and the emulated
-block_sum_1024 make the iterative form the kernel's arithmetic bit for bit."""
+block_sum_1024 make the iterative form the kernel's arithmetic bit for bit.
+
+UNDER A METRIC (Nuts(max_depth, metric=LowRankMetric), the reference's `scaling`: M = I + V diag(lambda) V^T, laplace.py; the statement
+finrom_hmc_nuts_ml_metric is tested against).  metric None or of rank zero: every line and bit above.  Otherwise, with the velocity
+    v(x) = M^-1 x = x + sum_j a_j V_j,   a_j = c_inv[j] dot_metric(V_j, x),   c_inv = -lambda / (1 + lambda)   (laplace._coef's forms),
+the terms added j ascending, one fma(a_j, V_j, .) each:
+START: the proposal's standard normals xi (the same Philox words), p0 = M^(1/2) xi by the same map with c_sqrt = lambda / (sqrt(1 +
+lambda) + 1), v0 = v(p0), H0 = U + dot(p0, v0) / 2, both edges (k, p0, v0, dU), rho = p0.
+LEAF: p1/2 = fma(-d h, dU, p); k' = fma(d eps, v(p1/2), k); evaluate at k', dU' as above; p' = fma(-d h, dU', p1/2); v' = v(p');
+dE = (U' + dot(p', v') / 2) - H0; divergence, weight, streamed selection and rho_sub += p' as above.
+U-TURNS, the generalised criterion with p# = M^-1 p (Betancourt 2017, A.4.2): a checkpoint stores (p, v, rho_sub), rho_s = (rho_sub -
+rho_ckpt) + p_ckpt; a sub-tree is turning when dot(rho_s, v_ckpt) <= 0 or dot(rho_s, v') <= 0, the tree when dot(rho, v_left) <= 0 or
+dot(rho, v_right) <= 0; `margin` takes these products relative to |rho| |v|.
+`dot_metric(V_j, x)` may be given like `dot`: the default is np.dot; the kernel's is one wave's (tests/nuts_metric_cases.py)."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -41,12 +54,26 @@ STOP_DEPTH, STOP_TREE_TURNED, STOP_SUBTREE_TURNED, STOP_DIVERGED = 0, 1, 2, 3
 
 
 class Nuts:
-    """nuts=Nuts(max_depth): at most 2^max_depth - 1 leapfrog steps per transition (the reference: 7)."""
+    """nuts=Nuts(max_depth, metric=None): at most 2^max_depth - 1 leapfrog steps per transition (the reference: 7); metric: a
+    laplace.LowRankMetric in the chain's own coordinates (whitened ones under prior=), the reference's `scaling`."""
 
-    def __init__(self, max_depth=7):
+    def __init__(self, max_depth=7, metric=None):
         if int(max_depth) != max_depth or not 1 <= max_depth <= MAX_DEPTH_LIMIT:
             raise ValueError(f"Nuts: max_depth = {max_depth} is outside 1 .. {MAX_DEPTH_LIMIT}")
+        if metric is not None and not all(hasattr(metric, a) for a in ("rho", "n", "Vt", "lam")):
+            raise ValueError("Nuts: metric= takes a laplace.LowRankMetric (Vt [rho, n], lam [rho])")
         self.max_depth = int(max_depth)
+        self.metric = metric
+
+    def metric_for(self, n, who="Nuts"):
+        """The metric of chains with n coordinates, where n is first known: None for no metric or one of rank zero (the identity:
+        the plain transition, bit for bit)."""
+        metric = getattr(self, "metric", None)
+        if metric is None or metric.rho == 0:
+            return None
+        if metric.n != n:
+            raise ValueError(f"{who}: Nuts(metric=): the metric has n = {metric.n}, the chains have {n} coordinates")
+        return metric
 
 
 def _plain_fma(a, x, y):
@@ -62,26 +89,49 @@ def _rel(a, b):
 class _Transition:
     """What both forms share: the start, the leaf (one leapfrog step, its energy, the streamed selection), the adoption."""
 
-    def __init__(self, value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot):
-        Nuts(max_depth)
-        self.f, self.fma, self.dot = value_and_grad, fma or _plain_fma, dot or np.dot
+    def __init__(self, value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot, metric=None,
+                 dot_metric=None):
+        self.metric = Nuts(max_depth, metric).metric_for(np.shape(k)[-1], "nuts.transition")
+        self.f, self.fma, self.dot, self.dot_metric = value_and_grad, fma or _plain_fma, dot or np.dot, dot_metric or np.dot
         self.seed, self.proposal, self.eps, self.c_lik, self.c_pri, self.max_depth = seed, int(proposal), eps, c_lik, c_pri, max_depth
         self.mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), np.shape(k))
         self.h, self.coef = 0.5 * eps * c_pri, c_lik / c_pri
         p0 = np.array(p0, dtype=np.float64)
-        self.H0 = U + 0.5 * self.dot(p0, p0)
-        start = (np.array(k, dtype=np.float64), p0, np.array(dU, dtype=np.float64))
+        if self.metric is not None:                                  # p0 holds the standard normals xi: p0 = M^(1/2) xi
+            from .laplace import _coef
+            self.c_inv = _coef(self.metric.lam, "inv")
+            p0 = self.low_rank(p0, _coef(self.metric.lam, "sqrt"))
+        v0 = self.velocity(p0)
+        self.H0 = U + self.kinetic(p0, v0)
+        start = (np.array(k, dtype=np.float64), p0, np.array(dU, dtype=np.float64), v0)
         self.edge = {-1: start, 1: start}
         self.rho, self.W = p0.copy(), 1.0
         self.cand = (start[0], start[2], U, loss)
         self.m, self.sum_acc, self.margin = 0, 0.0, np.inf
         self.depth, self.moved, self.reason, self.directions = 0, 0, STOP_DEPTH, []
 
+    def low_rank(self, x, coef):
+        """x + sum_j a_j V_j, a_j = coef[j] dot_metric(V_j, x), j ascending, one fma per term."""
+        Vt = self.metric.Vt
+        a = [coef[j] * self.dot_metric(Vt[j], x) for j in range(len(coef))]
+        y = x
+        for j in range(len(coef)):
+            y = self.fma(a[j], Vt[j], y)
+        return y
+
+    def velocity(self, p):
+        """M^-1 p (p itself without a metric)."""
+        return p if self.metric is None else self.low_rank(p, self.c_inv)
+
+    def kinetic(self, p, v):
+        """p . M^-1 p / 2"""
+        return 0.5 * self.dot(p, v)
+
     def note(self, a, b):
         self.margin = min(self.margin, _rel(a, b))
 
     def turning(self, rho, pa, pb):
-        """rho . pa <= 0 or rho . pb <= 0, each product's gap from zero relative to |rho| |p| noted."""
+        """rho . pa <= 0 or rho . pb <= 0, each product's gap from zero relative to |rho| |p| noted (pa, pb: velocities under a metric)."""
         out = False
         nr = np.sqrt(np.dot(rho, rho))
         for p in (pa, pb):
@@ -99,20 +149,21 @@ class _Transition:
         self.W_sub, self.rho_sub, self.sub_cand = 0.0, np.zeros_like(self.rho), None
 
     def leaf(self):
-        """One leapfrog step of the walker -> its momentum, or None: diverged."""
-        k, p, dU = self.walker
+        """One leapfrog step of the walker -> its (momentum, velocity), or None: diverged."""
+        k, p, dU, _ = self.walker
         d, fma = self.d, self.fma
         self.m += 1
         ph = fma(-d * self.h, dU, p)
-        kn = fma(d * self.eps, ph, k)
+        kn = fma(d * self.eps, self.velocity(ph), k)
         loss, grad, bad = self.f(kn[None])
         loss, grad, bad = float(np.asarray(loss)[0]), np.asarray(grad, dtype=np.float64)[0], bool(np.asarray(bad)[0])
         with np.errstate(all="ignore"):
             dk = kn - self.mean
             dUn = fma(self.coef, grad, dk)
             pn = fma(-d * self.h, dUn, ph)
+            vn = self.velocity(pn)
             Un = float(fma(self.c_lik, loss, 0.5 * self.c_pri * self.dot(dk, dk)))
-            dE = (Un + 0.5 * self.dot(pn, pn)) - self.H0
+            dE = (Un + self.kinetic(pn, vn)) - self.H0
         if bad or not np.isfinite(loss) or not np.isfinite(dE) or dE > E_MAX:
             return None
         with np.errstate(over="ignore"):
@@ -124,8 +175,8 @@ class _Transition:
         if u * self.W_sub < w:
             self.sub_cand = (kn, dUn, Un, loss)
         self.rho_sub = self.rho_sub + pn
-        self.walker = (kn, pn, dUn)
-        return pn
+        self.walker = (kn, pn, dUn, vn)
+        return pn, vn
 
     def adopt(self, j):
         """The finished sub-tree joins the tree -> whether the tree has turned."""
@@ -136,7 +187,7 @@ class _Transition:
         self.rho = self.rho + self.rho_sub
         self.edge[self.d] = self.walker
         self.depth = j + 1
-        return self.turning(self.rho, self.edge[-1][1], self.edge[1][1])
+        return self.turning(self.rho, self.edge[-1][3], self.edge[1][3])
 
     def run(self, subtree):
         """subtree(j) -> 0, or the stop reason with which building it ended the transition."""
@@ -162,28 +213,31 @@ def _trailing_ones(i):
     return t
 
 
-def transition_iterative(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None):
+def transition_iterative(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None,
+                         metric=None, dot_metric=None):
     """One transition of ONE chain from the state (k [n], U, dU [n] = grad U / c_pri, loss) with the momentum p0 [n]; the other draws
     are philox.nuts_top / nuts_leaf of (seed, proposal).  value_and_grad(K [1, n]) -> (loss [1], grad [1, n], bad [1]) as run_chains
-    takes it.  The leaves in order, U-turns by checkpoints.  -> a namespace: k, dU, U, loss (the draw), depth, steps, reason, moved,
+    takes it.  The leaves in order, U-turns by checkpoints.  metric: a LowRankMetric (p0 then holds the standard normals: the module's
+    text).  -> a namespace: k, dU, U, loss (the draw), depth, steps, reason, moved,
     tree (those four, int32), accept_stat, margin, directions."""
-    t = _Transition(value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot)
-    ck_p, ck_rho = [None] * max_depth, [None] * max_depth
+    t = _Transition(value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot, metric, dot_metric)
+    ck_p, ck_v, ck_rho = [None] * max_depth, [None] * max_depth, [None] * max_depth
     t.max_span = 0
 
     def subtree(j):
         for i in range(1 << j):
-            p = t.leaf()
-            if p is None:
+            pv = t.leaf()
+            if pv is None:
                 return STOP_DIVERGED
+            p, v = pv
             i_max = bin(i >> 1).count("1")
             if not i & 1:
-                ck_p[i_max], ck_rho[i_max] = p, t.rho_sub
+                ck_p[i_max], ck_v[i_max], ck_rho[i_max] = p, v, t.rho_sub
                 continue
             i_min = i_max - _trailing_ones(i) + 1
             for c in range(i_max, i_min - 1, -1):
                 rho_s = (t.rho_sub - ck_rho[c]) + ck_p[c]
-                if t.turning(rho_s, ck_p[c], p):
+                if t.turning(rho_s, ck_v[c], v):
                     t.max_span = max(t.max_span, i_max - c + 1)      # levels the turning span covers: 1 = two leaves
                     return STOP_SUBTREE_TURNED
         return 0
@@ -192,16 +246,17 @@ def transition_iterative(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, 
     return out
 
 
-def transition_recursive(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None):
+def transition_recursive(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None,
+                         metric=None, dot_metric=None):
     """transition_iterative's transition with the sub-tree built by the textbook recursion: two halves, rho their sum, the criterion on
-    the union's first and last momentum."""
-    t = _Transition(value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot)
+    the union's first and last velocity (momentum, without a metric)."""
+    t = _Transition(value_and_grad, k, U, dU, loss, p0, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma, dot, metric, dot_metric)
 
     def build(depth):
-        """-> (reason, first momentum, last momentum, rho)"""
+        """-> (reason, first velocity, last velocity, rho)"""
         if depth == 0:
-            p = t.leaf()
-            return (STOP_DIVERGED, None, None, None) if p is None else (0, p, p, p)
+            pv = t.leaf()
+            return (STOP_DIVERGED, None, None, None) if pv is None else (0, pv[1], pv[1], pv[0])
         r1, a, _, rho1 = build(depth - 1)
         if r1:
             return r1, None, None, None

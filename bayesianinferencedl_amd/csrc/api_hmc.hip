@@ -450,6 +450,33 @@ int finrom_hmc_end_metric(const finrom_hmc_state* a, finrom_metric_t metric, int
   if (n_steps < 0) { set_error("hmc_end_metric: n_steps < 0"); return FINROM_ERR_ARG; }
   return launch_hmc_end_metric(h, metric->d, a->Kq[n_steps & 1], (hipStream_t)stream);
 }
+// the No-U-turn transition under the metric (hmc_nuts.hip): finrom_hmc_nuts_ml's checks, the metric's, the larger workspace
+int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* a, finrom_metric_t metric, const uint64_t* seeds, int64_t proposal0,
+                              int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
+                              void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h;
+  if (int rc = hmc_dev(a, &h, "hmc_nuts_ml_metric")) return rc;
+  if (max_depth < 1 || max_depth > NUTS_MAX_DEPTH) {
+    set_error("hmc_nuts_ml_metric: max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH));
+    return FINROM_ERR_ARG;
+  }
+  if (proposal0 < 0) { set_error("hmc_nuts_ml_metric: proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (!seeds) { set_error("hmc_nuts_ml_metric: null seeds"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_metric_check(a, metric, "hmc_nuts_ml_metric")) return rc;
+  double* out = nullptr;
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_nuts_ml_metric")) return rc;
+  if (a->C == 0) return 0;
+  const MlpDev& m = mlp->d;
+  const int64_t wsd = hmc_nuts_metric_ws_doubles(a->C, a->n);
+  if (int rc = mlp->nuts_ws.reserve((size_t)(wsd + (2 + NUTS_SCALARS) * a->C) * sizeof(double))) return rc;      // (grown outside a capture only)
+  NutsDev nd;
+  nd.max_depth = max_depth; nd.proposal0 = proposal0; nd.seeds = (const unsigned long long*)seeds;
+  nd.ws = (double*)mlp->nuts_ws.p; nd.wloss = nd.ws + wsd; nd.winfo = (int*)(nd.wloss + a->C); nd.scal = nd.wloss + 2 * a->C; nd.st_loss = a->loss;
+  nd.tree = tree; nd.accept_stat = accept_stat;
+  return launch_hmc_nuts_ml_metric(m, h, nd, metric->d, data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p,
+                                   (float*)mlp->tape.p, out, (hipStream_t)stream);
+}
 int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior,
                                      const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* a,
                                      int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,

@@ -60,5 +60,10 @@ struct NutsDev {
 int64_t hmc_nuts_ws_doubles(int64_t C, int n);
 int launch_hmc_nuts_ml(const MlpDev& m, const HmcDev& h, const NutsDev& a, const double* data, int64_t data_stride, const double* zero,
                        float* tape, double* out, hipStream_t st);
+// finrom_hmc_nuts_ml_metric: the same transition under the metric M (P_block: standard normals).  ws: hmc_nuts_metric_ws_doubles -- the
+// identity launch's arrays and behind them the velocities' (both edges, the walker's two, one per checkpoint)
+int64_t hmc_nuts_metric_ws_doubles(int64_t C, int n);
+int launch_hmc_nuts_ml_metric(const MlpDev& m, const HmcDev& h, const NutsDev& a, const MetricDev& mt, const double* data,
+                              int64_t data_stride, const double* zero, float* tape, double* out, hipStream_t st);
 
 }  // namespace finrom

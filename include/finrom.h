@@ -612,7 +612,8 @@ int finrom_hmc_leapfrog_field(finrom_rom_t rom, finrom_mlp_t mlp, const double* 
  *                                  A = Sop, theta0 NULL; whitened (k = m + U^T v): A = Sop U^T, theta0 = Sop m, mean zeros,
  *                                  c_pri = 1 -- neither n x n triangular product runs in a step, and no field exists.
  * What the model allocates on first use (workspaces that grow with C) it allocates in the first call: run one step with the same C
- * before a capture.  There are no metric forms of these steps. */
+ * before a capture.  There are no metric forms of these steps; of the model="ml" entry points below the No-U-turn transition alone
+ * has one (finrom_hmc_nuts_ml_metric). */
 int finrom_hmc_drift(const finrom_hmc_state* st, int32_t step, const double* A, const double* theta0, int32_t P, double* theta_out,
                      void* stream);
 int finrom_hmc_kick(const finrom_hmc_state* st, int32_t step, const double* grad, const double* g_theta, const double* A, int32_t P,
@@ -710,6 +711,27 @@ int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const d
                                      int32_t step, const double* data, int32_t data_per_sample, double* qoi_r, double* e_nn,
                                      finrom_metric_t metric, double* vel, void* stream);
 int finrom_hmc_end_metric(const finrom_hmc_state* st, finrom_metric_t metric, int32_t n_steps, void* stream);
+/* finrom_hmc_nuts_ml under the metric: the reference's sampler as it is called, pm.NUTS(scaling=G_INV, max_treedepth=7)
+ * (bayesian_inference/inference.py:102-140,165-166); hmc.py nuts=Nuts(max_depth, metric=...), the statement nuts.py's
+ * transition_iterative(metric=).  The same launch, workgroup layout, Philox words, stop reasons, tree row, accept_stat and candidate
+ * rule; with the velocity v(x) = M^-1 x = x + sum_j a_j V_j, a_j = c_inv[j] (V_j . x), c_inv = -lambda / (1 + lambda):
+ *   start      row jt of P_block holds STANDARD normals xi (finrom_hmc_draw's, unchanged): p0 = M^(1/2) xi, v0 = v(p0),
+ *              H0 = U + p0 . v0 / 2, both edges (k, p0, v0, dU), rho = p0;
+ *   leaf       p1/2 = fma(-d h, dU, p), k' = fma(d eps, v(p1/2), k), dU' as there, p' = fma(-d h, dU', p1/2), v' = v(p'),
+ *              dE = U' + p' . v' / 2 - H0; rho_sub += p';
+ *   U-turns    the generalised criterion with p# = M^-1 p (Betancourt 2017, A.4.2): checkpoints hold (p, v, rho_sub),
+ *              rho_s = (rho_sub - rho_ckpt) + p_ckpt, turning when rho_s . v_ckpt <= 0 or rho_s . v' <= 0; the tree when
+ *              rho . v_left <= 0 or rho . v_right <= 0.
+ * Sums of the maps: wave w of the 16 forms V_j . x for j = w, w + 16, w + 32, w + 48 alone (lane l chains fused multiply-adds over
+ * elements l, l + 64, ..., a butterfly inside the wave), then y = x + sum_j a_j V_j with j ascending, one fused multiply-add per term
+ * (finrom_metric_apply's orders for 16 waves); p' . v' and the U-turn products in finrom_hmc_nuts_ml's order.
+ * Refused before any launch: everything finrom_hmc_nuts_ml refuses; a null metric handle, a metric whose n is not st->n
+ * (FINROM_ERR_ARG); an n_in that leaves no LDS for the sums, above finrom_mlp_forward_max_in() - 256 (FINROM_ERR_UNSUPPORTED).
+ * C == 0: returns 0, no launch.  The workspace is finrom_hmc_nuts_ml's with the velocities' arrays behind it, on the same handle: the
+ * first call with a new C is refused with FINROM_ERR_UNSUPPORTED and a message while a stream capture is open. */
+int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* st, finrom_metric_t metric, const uint64_t* seeds,
+                              int64_t proposal0, int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree,
+                              double* accept_stat, void* stream);
 /* The draws of a block of B proposals ON THE DEVICE (hmc.py rng="philox"), in the layout finrom_hmc_begin / _begin_metric read: row
  * j * C + c of P_block [B x C x n] and of lu_block [B x C] belongs to proposal first_proposal + j of the chain with seed seeds[c]
  * (seeds [C]: DEVICE array).  For seed s and global proposal index p, Philox4x32-10 with key (s lo, s hi):
