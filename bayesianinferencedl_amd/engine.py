@@ -521,7 +521,9 @@ class RomEngine:
         self.mirror = False
 
     # ---- the half form of a mirror-symmetric reduced model (DESIGN 4b', finrom_rom_set_mirror) ----------------------------------
-    MIRROR_EPS_GATE = 1e-9       # a hundredth of the rtol (1e-7) at which the tests equate the qoi_r of two projection forms
+    MIRROR_EPS_GATE = 1e-9       # relative, energy norm: what a list may cost as a FORM.  (The tests hold each list to the
+    #                              extended-precision LSPG of its own rows, tests/rom_lspg_cases.py; the lists' own solutions differ
+    #                              from the full model's by 1.5e-14 in qoi_r at the sizes tested, tests/test_rom_lspg_host.py.)
     MIRROR_PROBES = 16
     MIRROR_PROBE_RANGE = (0.1, 10.0)       # the dataset's range: where the probes lie, and where the short list is offered
 

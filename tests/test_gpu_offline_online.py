@@ -4,6 +4,7 @@ the same oracle restatement of rom/averaged_affine_ROM.py:278-310 (which contrac
 import numpy as np
 import pytest
 
+import rom_lspg_cases as Y
 from oracle import fin_oracle as O
 from test_gpu_parity import oracle_basis, rel, TOL
 
@@ -56,11 +57,17 @@ def test_rom_gradient_offline_online(problems, spaces, m, r):
     K = np.exp(0.3 * rng.standard_normal((6, prob.n)))
     res = rom.grad_reduced_batch(K)
     assert (res["info"] == 0).all()
+    # dJ_dk = g_theta S against the 80-bit statement at the theta the device averaged (tests/rom_lspg_cases.py), within the allowance
+    # max(8 d_host, 1e-12), d_host the deviation of the plain fp64 evaluation (host64) in the same quantity
+    c = Y.Case.from_rom(rom, np.asarray(rom.subfin_avg_batch(K)), data=data)
+    Sk = np.asarray(rom.dsigma_dk)
     for s in range(3):
         g_ref, J_ref = ro.grad_reduced(K[s])
-        g = res["g_theta"][s] @ rom.dsigma_dk
         assert abs(res["J"][s] - J_ref) < 1e-10 * abs(J_ref)
-        assert np.linalg.norm(g - g_ref) < 1e-8 * np.linalg.norm(g_ref)
+        ref, h = c.gd(s, False), c.h64(s, "full", False)
+        out = {"J": (Y.dev(res["J"][s], ref["J"]), Y.dev(h["J"], ref["J"])),
+               "dJ_dk": (Y.dev(res["g_theta"][s] @ Sk, ref["g"] @ Sk), Y.dev(h["g"] @ Sk, ref["g"] @ Sk))}
+        assert Y.report(f"offline/online gradient, m = {m}, r = {r}, sample {s}", out)
 
 
 @pytest.mark.parametrize("params,S", [("five", 300), ("field", 40), ("five", 1000)])

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import rom_lspg_cases as Y
 from oracle import fin_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -70,11 +71,18 @@ def cases(problems, spaces):
 
 
 def _close(a, b):
-    return np.allclose(np.asarray(a), np.asarray(b), rtol=1e-7, atol=1e-10)
+    """Two forms on in-range samples: each is held to its allowance of the extended-precision yardstick (tests/test_gpu_rom_lspg.py,
+    test_half_form_matches_full_form_and_oracle below), which the inputs keep at or under 1e-10; hence within 2e-10 of each other,
+    per sample and relative in the 2-norm."""
+    a, b = np.atleast_2d(np.asarray(a)), np.atleast_2d(np.asarray(b))
+    return bool(np.all(np.linalg.norm(a - b, axis=-1) <= 2.0 * Y.CAP * np.linalg.norm(b, axis=-1)))
 
 
 @pytest.mark.parametrize("m,r", CASES)
 def test_half_form_matches_full_form_and_oracle(cases, m, r):
+    """Measured, qoi_r (device / host64): the list that ran against its own 80-bit LSPG on four samples: (4, 16): 9.3e-14 / 9.2e-14,
+    (12, 33): 6.3e-13 / 3.0e-12, (12, 80): 3.3e-13 / 4.8e-13; the full handle against QR on all 301: 5.2e-12 / 5.5e-12,
+    8.0e-12 / 8.4e-12, 1.1e-11 / 8.7e-12."""
     prob, phi, rom, full, TH, res, ref = cases(m, r)
     A, A0 = np.asarray(res["A_r"]), np.asarray(ref["A_r"])
     assert np.array_equal(np.asarray(res["info"]), np.asarray(ref["info"])) and not np.asarray(res["info"]).any()
@@ -82,14 +90,28 @@ def test_half_form_matches_full_form_and_oracle(cases, m, r):
     dq = np.max(np.abs(np.asarray(res["qoi_r"]) / np.asarray(ref["qoi_r"]) - 1.0))
     print(f"m = {m}, r = {r}: eps_probe {rom._rom.mirror_eps:.3e}, half vs full: max|dA_r|/max|A_r| {dA:.3e}, max rel qoi_r {dq:.3e}")
     assert dA < 1e-12
-    assert _close(res["qoi_r"], ref["qoi_r"]) and _close(res["w_r"], ref["w_r"])
     assert not np.array_equal(A, A0)                         # another sum: the half list did run
     ro = O.AffineROMOracle(prob, phi)
     for s in (0, 77, 150, 300):
         w, Ar, Br, _ = ro.forward_nine_param_reduced(TH[s], return_parts=True)
         assert np.linalg.norm(A[s] - Ar) < 1e-12 * np.linalg.norm(Ar), s
-        q = ro.qoi_reduced(w)
-        assert np.linalg.norm(np.asarray(res["qoi_r"])[s] - q) < 1e-7 * np.linalg.norm(q), s
+    # each form against the extended-precision LSPG of ITS OWN list (tests/rom_lspg_cases.py), within max(8 d_host, 1e-12): the
+    # handle with the half list -- whose in-range samples walk the short list where one is installed -- on four samples, the full
+    # handle on the same four and, by the QR yardstick, on all; then the two against each other on every sample, within the two
+    # allowances added (the lists' own LSPGs differ by 1.5e-14 at most, tests/test_rom_lspg_host.py)
+    c = Y.Case.from_rom(full, TH)
+    own = "short" if rom._rom.mirror_dropped else "half"
+    r_own = c.against_ld(res, (0, 77, 150, 300), ("qoi_r", "Phi_w"), form=own)
+    r_full = c.against_ld(ref, (0, 77, 150, 300), ("qoi_r", "Phi_w"))
+    r_all = c.against_qr(ref, S, ("qoi_r", "Phi_w"))
+    assert Y.report(f"m = {m}, r = {r}: {own} list against its own LSPG", r_own)
+    assert Y.report(f"m = {m}, r = {r}: full list, 80-bit", r_full) and Y.report(f"m = {m}, r = {r}: full list, QR on all", r_all)
+    for key, k in (("qoi_r", "qoi_r"), ("w_r", "Phi_w")):
+        a, b = np.asarray(res[key]), np.asarray(ref[key])
+        if key == "w_r":
+            a, b = a @ phi.T, b @ phi.T
+        d = np.max(np.linalg.norm(a - b, axis=1) / np.linalg.norm(b, axis=1))
+        assert d <= Y.allowance(r_own[k][1]) + Y.allowance(r_all[k][1]), (key, d)
 
 
 def _mixed_batch(TH):
@@ -158,8 +180,8 @@ def test_pair_path_with_five_parameters(spaces, cases, m, r):
         assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), key
     assert not np.asarray(a["info"]).any()
     qa, qb = np.asarray(a["qoi_r"]), np.asarray(b["qoi_r"])
-    assert np.allclose(qa, qb, rtol=1e-7, atol=0.0) and not np.array_equal(qa, qb)
-    assert np.allclose(qa[:, ::-1], qa, rtol=1e-7, atol=0.0)
+    assert _close(qa, qb) and not np.array_equal(qa, qb)
+    assert np.allclose(qa[:, ::-1], qa, rtol=1e-7, atol=0.0)      # (the basis' own asymmetry, not rounding: as it was)
 
 
 def test_nine_parameter_basis_installs_nothing(problems, spaces):

@@ -16,8 +16,9 @@ import os
 import numpy as np
 import pytest
 
+import rom_lspg_cases as Y
 from oracle import fin_oracle as O
-from test_gpu_rom_mirror import TWIN, _basis
+from test_gpu_rom_mirror import TWIN, _basis, _close
 
 pytestmark = pytest.mark.gpu
 CASES = [(4, 16, 30), (12, 80, 506)]
@@ -70,9 +71,10 @@ def cases(problems, spaces):
     return get
 
 
-def _compare(res, ref, rom):
-    """info equal; norm(A_r - A_r0) <= 1e-12 norm(A_r0) per sample, not the same bits (see above); qoi_r to rtol 1e-7.
-    -> the two maxima."""
+def _compare(res, ref, rom, in_range=True):
+    """info equal; norm(A_r - A_r0) <= 1e-12 norm(A_r0) per sample, not the same bits (see above); qoi_r of in-range batches within
+    2e-10 per sample (_close: each form is held to its allowance of the yardstick, at most 1e-10), of batches with conductivities
+    outside [0.1, 10] to rtol 1e-7 as before.  -> the two maxima."""
     assert np.array_equal(np.asarray(res["info"]), np.asarray(ref["info"])) and not np.asarray(res["info"]).any()
     A, A0 = np.asarray(res["A_r"]), np.asarray(ref["A_r"])
     dA = np.max(np.linalg.norm(A - A0, axis=(1, 2)) / np.linalg.norm(A0, axis=(1, 2)))
@@ -81,7 +83,10 @@ def _compare(res, ref, rom):
     assert rom._rom.mirror_info()[1] < (rom._rom.mirror_info()[0] + rom._rom.mirror_dropped + 3) // 4      # the short list ran
     if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
         assert not np.array_equal(A, A0)                     # another sum
-    assert np.allclose(np.asarray(res["qoi_r"]), np.asarray(ref["qoi_r"]), rtol=1e-7, atol=0.0), dq
+    if in_range:
+        assert _close(res["qoi_r"], ref["qoi_r"]), dq
+    else:
+        assert np.allclose(np.asarray(res["qoi_r"]), np.asarray(ref["qoi_r"]), rtol=1e-7, atol=0.0), dq
     return dA, dq
 
 
@@ -102,6 +107,8 @@ def test_counts_and_gate_on_the_handle(cases, m, r, ndrop):
 @pytest.mark.parametrize("S", SIZES)
 @pytest.mark.parametrize("m,r,ndrop", CASES)
 def test_short_list_matches_all_rows_and_oracle(cases, m, r, ndrop, S):
+    """Measured, qoi_r against the list's own 80-bit LSPG on three samples (device / host64, largest over the sizes): short list
+    (4, 16): 9e-14 / 9e-14, (12, 80): 3.3e-13 / 4.8e-13; all rows against the half list's: 7.1e-14 / 9.2e-14, 4.5e-13 / 2.4e-13."""
     prob, phi, rom, _, runs = cases(m, r)
     TH, res, ref = runs[S]
     if r >= 49 and S <= 64:                                  # split-K: no half list on either handle
@@ -115,12 +122,19 @@ def test_short_list_matches_all_rows_and_oracle(cases, m, r, ndrop, S):
         dqc = np.max(np.abs(np.asarray(res["qoi_r"])[:32] / np.asarray(ref["qoi_r"])[:32] - 1.0))
         print(f"    the 32 corners of [0.1, 10]: max rel qoi_r {dqc:.3e}")
     ro = O.AffineROMOracle(prob, phi)
-    A, q = np.asarray(res["A_r"]), np.asarray(res["qoi_r"])
+    A = np.asarray(res["A_r"])
     for s in (0, S // 3, S - 1):
-        w, Ar, _, _ = ro.forward_nine_param_reduced(TH[s], return_parts=True)
-        qo = ro.qoi_reduced(w)
+        _, Ar, _, _ = ro.forward_nine_param_reduced(TH[s], return_parts=True)
         assert np.linalg.norm(A[s] - Ar) <= 1e-12 * np.linalg.norm(Ar), s
-        assert np.allclose(q[s], qo, rtol=1e-7, atol=0.0), s
+    # qoi_r and Phi w_r against the extended-precision LSPG of the list that ran (tests/rom_lspg_cases.py: the short list's own rows;
+    # the full list in the split-K cell), within max(8 d_host, 1e-12); the handle with all rows against the half list's
+    c = Y.Case.from_rom(rom, TH)
+    splitk = r >= 49 and S <= 64
+    ss = (0, S // 3, S - 1)
+    assert Y.report(f"m = {m}, r = {r}, S = {S}: short list against its own LSPG",
+                    c.against_ld(res, ss, ("qoi_r", "Phi_w"), form="full" if splitk else "short"))
+    assert Y.report(f"m = {m}, r = {r}, S = {S}: all rows against the half list's LSPG",
+                    c.against_ld(ref, ss, ("qoi_r", "Phi_w"), form="full" if splitk else "half"))
 
 
 @pytest.mark.parametrize("m,r,ndrop", CASES)
@@ -141,7 +155,7 @@ def test_extreme_thetas(cases, m, r, ndrop):
     res = rom.forward_nine_param_reduced_batch(TH, want_state=True)
     ref = allrows.forward_nine_param_reduced_batch(TH, want_state=True)
     assert rom._rom.last_form() == allrows._rom.last_form() == "half"
-    dA, dq = _compare(res, ref, rom)
+    dA, dq = _compare(res, ref, rom, in_range=False)
     print(f"m = {m}, r = {r}, theta in [0.01, 100]: max norm(dA_r)/norm(A_r) {dA:.3e}, max rel qoi_r {dq:.3e}")
     inside = ((TH >= 0.1) & (TH <= 10.0)).all(axis=1)
     assert inside[18:26].all() and not inside[:18].any() and not inside[26] and inside.sum() < 64
@@ -185,7 +199,7 @@ def test_pair_path_with_five_parameters(spaces, cases, m, r, ndrop):
     assert not np.asarray(a["info"]).any()
     qa, qb = np.asarray(a["qoi_r"]), np.asarray(b["qoi_r"])
     print(f"m = {m}, r = {r}: pair path, max rel qoi_r {np.max(np.abs(qa / qb - 1.0)):.3e}")
-    assert np.allclose(qa, qb, rtol=1e-7, atol=0.0)
+    assert _close(qa, qb)
     if rom._rom.mirror_dropped_max ** 2 >= 2.0 ** -53:
         assert not np.array_equal(qa, qb)
 
@@ -206,4 +220,4 @@ def test_all_zero_conductivities_are_flagged_as_before(cases, m, r, ndrop):
     for key in ("A_r", "B_r", "w_r", "qoi_r"):
         assert np.array_equal(np.asarray(a[key])[5], np.asarray(b[key])[5], equal_nan=True), key
     ok = np.delete(np.arange(128), 5)
-    assert np.allclose(np.asarray(a["qoi_r"])[ok], np.asarray(b["qoi_r"])[ok], rtol=1e-7, atol=0.0)
+    assert _close(np.asarray(a["qoi_r"])[ok], np.asarray(b["qoi_r"])[ok])
