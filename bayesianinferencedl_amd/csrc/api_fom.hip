@@ -169,14 +169,19 @@ static int64_t fom_equal_chunk(int64_t S, int64_t limit) {
 }
 // stages: 1 = pack + assembly, 2 = interpreter (+ unpack of w), 3 = both.  finrom_solve_pairs runs stage 1, then
 // launches the ROM half, then stage 2 (only possible when the batch fits one workspace chunk).
+// the bound on a call's workspace, shared by every finrom_fom_* entry point that cuts a batch into pieces: 48 GiB, or
+// FINROM_FOM_WORKSPACE_BYTES=<n>, read per call, so that a test can make a small batch run in pieces
+static int64_t fom_workspace_bound() {
+  const char* env_ws = getenv("FINROM_FOM_WORKSPACE_BYTES");
+  return env_ws != nullptr && atoll(env_ws) > 0 ? (int64_t)atoll(env_ws) : (int64_t)((size_t)48 << 30);
+}
+// samples per piece for a workspace of `per_sample` bytes each: whole blocks of 64 lanes, one block at least
+static int64_t fom_piece_samples(size_t per_sample) {
+  return std::max<int64_t>(64, fom_workspace_bound() / (int64_t)per_sample / 64 * 64);
+}
 int64_t fom_chunk_samples(const FomDev& d, const BandDev* band) {
   // bound the per-call workspace (L values dominate: nnzL * 8 B per sample)
-  const size_t per_sample = ((size_t)(band && band->on ? band->gsize : d.gsize) + d.xdim) * sizeof(double);
-  // (FINROM_FOM_WORKSPACE_BYTES=<n>, read per call: another bound, so that a test can make a small batch run in pieces)
-  const char* env_ws = getenv("FINROM_FOM_WORKSPACE_BYTES");
-  const int64_t bound = env_ws != nullptr && atoll(env_ws) > 0 ? (int64_t)atoll(env_ws) : (int64_t)((size_t)48 << 30);
-  const int64_t chunk = bound / (int64_t)per_sample;
-  return std::max<int64_t>(64, chunk / 64 * 64);
+  return fom_piece_samples(((size_t)(band && band->on ? band->gsize : d.gsize) + d.xdim) * sizeof(double));
 }
 int fom_solve_stages(finrom_fom_t h, const double* x, int64_t S, double* qoi, double* w, int32_t* info, hipStream_t st, int stages,
                      bool records) {
@@ -525,7 +530,7 @@ int finrom_fom_solve_rhs(finrom_fom_t h, const double* x, int64_t S, const doubl
   h->last_path = band_path(b, false);
   const int64_t dr = (int64_t)nrhs * d.n;
   const size_t per_sample = ((size_t)b.gsize + d.xdim + 2 * (size_t)dr) * sizeof(double);
-  const int64_t limit = std::max<int64_t>(64, (int64_t)((size_t)48 << 30) / (int64_t)per_sample / 64 * 64);
+  const int64_t limit = fom_piece_samples(per_sample);
   for (int64_t s0 = 0; s0 < S; s0 += limit) {
     const int64_t Sc = std::min(limit, S - s0), nblk = (Sc + 63) / 64;
     int rc;
@@ -605,8 +610,7 @@ int finrom_fom_gradient(finrom_fom_t h, const double* x, const double* data, int
     const BandDev& b = h->band;
     h->last_path = band_path(b, false);
     const size_t per_sample = ((size_t)b.gsize + 2 * d.xdim) * sizeof(double);
-    const int64_t limit = std::max<int64_t>(64, (int64_t)((size_t)48 << 30) / (int64_t)per_sample / 64 * 64);
-    const int64_t chunk = fom_equal_chunk(S, limit);
+    const int64_t chunk = fom_equal_chunk(S, fom_piece_samples(per_sample));
     for (int64_t s0 = 0; s0 < S; s0 += chunk) {
       const int64_t Sc = std::min(chunk, S - s0), nblk = (Sc + 63) / 64;
       int rc;
@@ -637,8 +641,7 @@ int finrom_fom_gradient(finrom_fom_t h, const double* x, const double* data, int
   }
   h->last_path = FINROM_FOM_PATH_INTERPRETER;
   const size_t per_sample = ((size_t)d.gsize + 2 * d.xdim) * sizeof(double);
-  int64_t chunk = (int64_t)((size_t)48 << 30) / (int64_t)per_sample;
-  chunk = std::max<int64_t>(64, chunk / 64 * 64);
+  const int64_t chunk = fom_piece_samples(per_sample);
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int64_t Sc = std::min(chunk, S - s0);
     const int64_t nblk = (Sc + 63) / 64;

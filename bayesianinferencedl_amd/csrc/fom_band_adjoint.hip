@@ -119,10 +119,14 @@ __global__ __launch_bounds__(64) void fom_band_adjoint_kernel(BandDev p, const i
   for (int f = 0; f < p.nfins; ++f)
     band_bsweep<NSF, false, NXM, RBF>(p, io, wx, T, iface_elim + f * p.nif, f * p.npf, p.npf, p.npf + p.nif, f * p.npf * NSF, p.offV);
   // grad_j = sum dA_ab/dx_j v_a w_b, loads batched by GB pairs (a failed factorisation left NaN in w: it propagates).  16 pairs =
-  // 32 loads in flight: a lone wave (the one-block batches of a scalar caller) is latency-bound on exactly this loop
+  // 32 loads in flight: a lone wave (the one-block batches of a scalar caller) is latency-bound on exactly this loop.
+  // ONE accumulator, in table order: the triples of a parameter come row by row of A, and a row's terms v_a sum_b dA_ab/dx_j w_b
+  // cancel (a stiffness row applied to a smooth w) -- for a fin conductivity by five to six digits over the whole sum.  Summed in
+  // order the partial sums stay small; dealt alternately to two accumulators each half grows to the size of the terms and the
+  // digits go in g0 + g1 (measured: 2.1e-11 against 1.7e-12 for the host's sequential sum at m = 12, five conductivities).
   constexpr int GB = 16;
   for (int j = 0; j < p.xdim; ++j) {
-    double g0 = 0.0, g1 = 0.0;
+    double g = 0.0;
     const int t0 = g_ptr[j], t1 = g_ptr[j + 1];
     for (int t = t0; t < t1; t += GB) {
       double va[GB], wb[GB];
@@ -133,12 +137,9 @@ __global__ __launch_bounds__(64) void fom_band_adjoint_kernel(BandDev p, const i
         wb[u] = io.ld(p.offY + g_b[tt]);
       }
 #pragma unroll
-      for (int u = 0; u < GB; u += 2) {
-        g0 = fma((t + u < t1) ? g_w[t + u] : 0.0, va[u] * wb[u], g0);
-        g1 = fma((t + u + 1 < t1) ? g_w[t + u + 1] : 0.0, va[u + 1] * wb[u + 1], g1);
-      }
+      for (int u = 0; u < GB; ++u) g = fma((t + u < t1) ? g_w[t + u] : 0.0, va[u] * wb[u], g);
     }
-    gradT[(blk * p.xdim + j) * 64 + lane] = g0 + g1;
+    gradT[(blk * p.xdim + j) * 64 + lane] = g;
   }
   if (live) Jout[s] = 0.5 * jl;
 }

@@ -399,9 +399,10 @@ __global__ __launch_bounds__(64) void fom_adjoint_kernel(FomDev p, const int* __
       }
     }
   }
-  // grad_j = sum dA_ab/dx_j v_a w_b, loads batched by 4 pairs
+  // grad_j = sum dA_ab/dx_j v_a w_b, loads batched by 4 pairs; ONE accumulator in table order (a row's terms cancel: see
+  // fom_band_adjoint_kernel)
   for (int j = 0; j < p.xdim; ++j) {
-    double g0 = 0.0, g1 = 0.0;
+    double g = 0.0;
     const int t0 = g_ptr[j], t1 = g_ptr[j + 1];
     for (int t = t0; t < t1; t += 4) {
       double va[4], wb[4];
@@ -412,12 +413,9 @@ __global__ __launch_bounds__(64) void fom_adjoint_kernel(FomDev p, const int* __
         wb[u] = G[(int64_t)(ZV + g_b[tt]) * 64];
       }
 #pragma unroll
-      for (int u = 0; u < 4; u += 2) {
-        g0 = fma((t + u < t1) ? g_w[t + u] : 0.0, va[u] * wb[u], g0);
-        g1 = fma((t + u + 1 < t1) ? g_w[t + u + 1] : 0.0, va[u + 1] * wb[u + 1], g1);
-      }
+      for (int u = 0; u < 4; ++u) g = fma((t + u < t1) ? g_w[t + u] : 0.0, va[u] * wb[u], g);
     }
-    gradT[(blk * p.xdim + j) * 64 + lane] = g0 + g1;      // NaN propagates from a failed factorisation
+    gradT[(blk * p.xdim + j) * 64 + lane] = g;            // NaN propagates from a failed factorisation
   }
   if (live) Jout[s] = 0.5 * jl;
 }

@@ -327,7 +327,13 @@ int finrom_fom_set_band_gradient(finrom_fom_t h, const finrom_fom_band_grad_desc
  * row-major in dof order -- the incremental state and incremental adjoint solves of Fin.hessian_action (fom/forward_solve.py:
  * 344-368: `solve(self._a == rhs)` with a new right-hand side for the same conductivity).  One band sweep factors A(x_s), the
  * columns then stream back once per right-hand side (forward substitution + backward sweep on the stored factor).  Needs
- * finrom_fom_set_band (FINROM_ERR_UNSUPPORTED otherwise); info as for finrom_fom_solve. */
+ * finrom_fom_set_band (FINROM_ERR_UNSUPPORTED otherwise); info as for finrom_fom_solve: non-zero for a sample whose operator is not
+ * positive definite, and that sample's out is NaN in EVERY entry of every right-hand side (the failed pivot's reciprocal square
+ * root is NaN in the stored factor; the forward substitution carries it to the last pivot, the backward sweep from there to every
+ * dof).  Lane = sample: no other sample's bits change.
+ * Batches whose workspace would exceed 48 GiB run in pieces of whole 64-sample blocks, here, in finrom_fom_solve and in
+ * finrom_fom_gradient alike; FINROM_FOM_WORKSPACE_BYTES=<n> (read per call) puts another bound in its place, so that a test can make
+ * a small batch run in pieces (64 samples a piece at the least).  The outputs do not depend on the pieces. */
 int finrom_fom_solve_rhs(finrom_fom_t h, const double* x, int64_t S, const double* rhs, int32_t nrhs, double* out, int32_t* info,
                          void* stream);
 
