@@ -321,6 +321,19 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
   return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy, short_waits);
 }
 
+// the workspace bound of one piece of a batch (the packed A_r and B_r of its samples): 16 GiB; FINROM_ROM_WORKSPACE_BYTES=<n>, read
+// per call, puts another bound in its place so that a test can make a small batch run in pieces (the shape of api_fom.hip's
+// fom_piece_samples).  Pieces are multiples of four samples, four at the least.  rom_solve_impl then makes its pieces equal (a piece
+// chooses its form by its own size); finrom_rom_grad cuts whole pieces and leaves the rest to the last one.
+// NOT for finrom_romml_grad: its one-sample form needs finrom_rom_grad to run the batch in one piece (defer_sum) and says so with an
+// error when the switch cuts a batch of <= 64 samples; include/finrom.h says the switch is not supported there.
+static int64_t rom_piece_samples(size_t per_sample) {
+  const char* env_ws = getenv("FINROM_ROM_WORKSPACE_BYTES");
+  const int64_t env_bound = env_ws != nullptr ? (int64_t)atoll(env_ws) : 0;
+  const int64_t bound = env_bound > 0 ? env_bound : (int64_t)((size_t)16 << 30);
+  return std::max<int64_t>(4, bound / (int64_t)per_sample / 4 * 4);
+}
+
 // roomy: finrom_solve_pairs beside the FOM's half sweep -- QoI-only calls at r <= 80 then take the 256-register one-wave kernel at
 // every batch size (rom_roomy_applies); finrom_rom_solve itself never does.  short_waits: that kernel's form without the fixed waits
 // between accumulate-chained MFMAs (finrom_rom_s::short_waits says where)
@@ -331,7 +344,7 @@ static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double
   hipStream_t st = (hipStream_t)stream;
   const RomDev& d = h->d;
   const size_t per_sample = ((size_t)d.rp * (d.rp + 1) / 2 + d.rp) * sizeof(double);
-  int64_t chunk = std::max<int64_t>(4, (int64_t)(((size_t)16 << 30) / per_sample) / 4 * 4);
+  int64_t chunk = rom_piece_samples(per_sample);
   if (S > chunk) { const int64_t np = (S + chunk - 1) / chunk; chunk = ((S + np - 1) / np + 3) / 4 * 4; }      // equal pieces
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int64_t Sc = std::min(chunk, S - s0);
@@ -403,7 +416,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
   const RomDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
   const size_t per_sample = ((size_t)d.rp * (d.rp + 1) / 2 + d.rp) * sizeof(double);
-  int64_t chunk = std::max<int64_t>(4, (int64_t)(((size_t)16 << 30) / per_sample) / 4 * 4);
+  const int64_t chunk = rom_piece_samples(per_sample);
   for (int64_t s0 = 0; s0 < S; s0 += chunk) {
     const int64_t Sc = std::min(chunk, S - s0);
     int rc;
@@ -416,6 +429,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
     if (h->projection == FINROM_PROJECTION_DIRECT && rom_onesample_applies(d, Sc)) {
       // contraction over several workgroups per sample, MFMA-form factorisation + forward / adjoint solves (rom_onesample.hip),
       // then the gradient contraction dealt over 36 workgroups per sample
+      h->last_form = FINROM_ROM_FORM_FULL; h->last_epilogue = FINROM_ROM_EPILOGUE_STANDARD;      // (this branch's own projection launch)
       RomGradArgs ga;
       ga.data = data + (data_per_sample ? s0 * d.n_obs : 0); ga.data_stride = data_per_sample ? d.n_obs : 0;
       ga.theta = theta + s0 * d.P; ga.J = J + s0; ga.g = g + s0 * d.P;
@@ -437,6 +451,7 @@ int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int
       continue;
     }
     if (h->projection == FINROM_PROJECTION_DIRECT && rom_splitk_applies(d, Sc) && d.n_obs <= 64) {
+      h->last_form = FINROM_ROM_FORM_FULL; h->last_epilogue = FINROM_ROM_EPILOGUE_STANDARD;      // (this branch's own projection launch)
       RomGradArgs ga;
       ga.data = data + (data_per_sample ? s0 * d.n_obs : 0); ga.data_stride = data_per_sample ? d.n_obs : 0;
       ga.theta = theta + s0 * d.P; ga.J = J + s0; ga.g = g + s0 * d.P;

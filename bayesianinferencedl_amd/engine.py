@@ -79,7 +79,9 @@ class _Batch:
 
     def new(self, shape, dtype="f8", zero=True):
         """Allocate an output of the same kind, zero-filled unless the call overwrites all of it (zero=False: one fill kernel
-        less per output on the torch path -- they add up in a one-sample call); returns (handle, device pointer)."""
+        less per output on the torch path -- they add up in a one-sample call); returns (handle, device pointer).
+        info is always zero-filled: every entry point ORs its flags into it (include/finrom.h, Conventions) but finrom_romml_grad,
+        which overwrites it and is the one call that gets zero=False for it."""
         if self.torch:
             import torch
             t = (torch.zeros if zero else torch.empty)(shape, dtype=torch.float64 if dtype == "f8" else torch.int32, device=self.device)
@@ -679,7 +681,8 @@ class RomEngine:
 
     def last_form(self):
         """'half' when the most recent projection launch of solve / solve_pairs offered its samples the half list (each sample
-        whose parameters equal their twins' walked it), 'full' otherwise, 'none' before the first call (finrom_rom_last_form)."""
+        whose parameters equal their twins' walked it), 'full' otherwise -- after every projection launch of grad as well, which never
+        offers the half list --, 'none' before the first call (finrom_rom_last_form)."""
         rc = lib().finrom_rom_last_form(self._h)
         if rc < 0:
             check(rc, "finrom_rom_last_form")

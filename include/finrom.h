@@ -19,8 +19,26 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream); calls are
  *    asynchronous on that stream unless stated; a handle is used by one host thread at
  *    a time (the reference classes are not re-entrant either).
- *  - info[s] != 0 marks a failed sample (bit 0: FOM pivot <= 0 or NaN, bit 1: ROM pivot);
- *    its outputs are NaN.  info must be zero-initialised by the caller (bits are OR-ed in).
+ *  - info[s] != 0 marks a failed sample (bit 0, value 1: FOM pivot <= 0 or NaN; bit 1, value 2: ROM pivot);
+ *    its outputs are NaN, and no other sample of the batch is touched: every output of every other sample has the bits
+ *    the same call returns for the batch without the failed samples (tests/test_gpu_rom_flags.py, tests/test_gpu_fom_flags.py).
+ *    A NaN, an infinity or an overflowing entry in a sample's row of theta / x is ordinary data and ends as a flagged sample;
+ *    a NaN in a sample's row of `data` (gradients) is not a failed sample: info stays 0, the solve's outputs are those of the
+ *    clean data, J and every entry of the gradient are NaN.
+ *    The full-order factorisation has no pivoting and flags by the sign of its pivots: an operator that is positive definite
+ *    in exact arithmetic but singular to rounding can come back flagged.  Measured with one conductivity, or all, at 1e200 (the
+ *    Robin term is then 200 digits below the stiffness): 10 of 26 such samples were flagged with NaN outputs, 16 solved with
+ *    info 0 and finite outputs; never anything in between (tests/test_gpu_fom_flags.py).
+ *  - what a call does with the info it is given, entry point by entry point:
+ *      finrom_fom_solve, finrom_fom_gradient, finrom_fom_solve_rhs     OR bit 0 in; nothing is cleared
+ *      finrom_rom_solve, finrom_rom_grad                               OR bit 1 in; nothing is cleared
+ *      finrom_solve_pairs                                              ORs bit 0 (FOM half) and bit 1 (ROM half) in; nothing is cleared
+ *      finrom_romml_grad                                               OVERWRITES info[s] with 0 or the flag
+ *      the finrom_hmc_* steps                                          clear the state's info in front of the model's launches
+ *    So the caller zero-initialises info for every entry point of the first three rows (a bit that was set on entry is still
+ *    set on return, in a flagged and in a clean row alike), and need not for finrom_romml_grad.  finrom_solve_pairs READS info
+ *    behind its two halves where it ran the roomy projection kernel (finrom_rom_last_epilogue): a row whose info is not 0 there
+ *    -- from this call or from before it -- gets NaN in qoi_r and err.
  */
 #ifndef FINROM_H
 #define FINROM_H
@@ -165,7 +183,12 @@ int finrom_fom_solve(finrom_fom_t h, const double* x, int64_t S,
  *   bt_*     B_obs^T as CSR by dof  (row i: observation indices and weights),
  *   g_*      for every parameter j the list of (row a, column b, weight dA_ab/dx_j) triples.
  * finrom_fom_gradient: x [S x xdim], data [n_obs] (data_per_sample = 0) or [S x n_obs] ->
- * grad [S x xdim], J [S], optional qoi [S x n_obs]; info as for finrom_fom_solve. */
+ * grad [S x xdim], J [S], optional qoi [S x n_obs]; info as for finrom_fom_solve (bit 0 OR-ed in).
+ * A flagged sample (info[s] & 1), on each of the three paths (band adjoint, small-batch kernel, interpreter): every entry of its
+ * grad, J and qoi is NaN; every other sample keeps the bits of the batch without it, and the handle's workspace carries nothing
+ * over into the next call.  A NaN, +inf or negative conductivity in x is flagged.  x = 1e200 is a positive definite operator with
+ * finite entries: such a sample is either solved (info 0, every output finite) or flagged with NaN outputs, never in between --
+ * which of the two, rounding in the Schur complements decides. */
 typedef struct {
   int32_t nops_res;
   const int32_t* res_kind; const int32_t* res_a; const int32_t* res_b; const int32_t* res_d;
@@ -432,7 +455,8 @@ int finrom_rom_mirror_counts(const finrom_rom_desc* desc, const double* row_weig
 int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps);
 /* Which list the most recent projection launch of finrom_rom_solve / finrom_solve_pairs on this handle OFFERED its samples
  * (tests assert on it, like finrom_fom_last_path): FINROM_ROM_FORM_HALF = the launch carried the half list and every sample that
- * passed the per-sample mirror test walked it; FINROM_ROM_FORM_FULL = every sample ran the handle's own tables. */
+ * passed the per-sample mirror test walked it; FINROM_ROM_FORM_FULL = every sample ran the handle's own tables.  finrom_rom_grad
+ * never offers the half list: every projection launch of its sets FINROM_ROM_FORM_FULL and FINROM_ROM_EPILOGUE_STANDARD. */
 #define FINROM_ROM_FORM_NONE 0
 #define FINROM_ROM_FORM_FULL 1
 #define FINROM_ROM_FORM_HALF 2
@@ -451,7 +475,20 @@ int finrom_rom_last_form(finrom_rom_t h);
 int finrom_rom_last_epilogue(finrom_rom_t h);
 /* theta [S x P] -> w_r [S x r] (NULL to skip), qoi_r [S x n_obs], info [S] (NULL ok);
  * optional A_r [S x r x r] and B_r [S x r] (the state the reference keeps in
- * self._A_r / self._B_r for its gradients, :296-297) -- NULL to skip. */
+ * self._A_r / self._B_r for its gradients, :296-297) -- NULL to skip.
+ * info: bit 1 (value 2) is OR-ed in for a sample whose A_r cannot be factored; nothing is cleared (see Conventions).
+ * A flagged sample, in every form the call dispatches to: every entry of its qoi_r is NaN, and its w_r is not all finite (the
+ * guarantee; every form run so far returns no finite entry in it).  What its A_r and B_r hold is not specified.
+ * Every other sample keeps, bit for bit, what the batch without the flagged samples returns, and the handle's
+ * grow-only scratch carries nothing over: a clean call after a poisoned one returns the bits of the clean call before it.
+ * Workspace: the packed A_r and B_r of a piece of the batch stay under 16 GiB; larger batches run in pieces (multiples of four
+ * samples), each offsetting theta and every output.  FINROM_ROM_WORKSPACE_BYTES=<n> (read per call) puts another bound in its
+ * place, so that a test can make a small batch run in pieces (four samples a piece at the least); finrom_rom_grad and
+ * finrom_solve_pairs alike.  The switch is NOT supported by finrom_romml_grad: its one-sample form needs its batch (<= 64 samples)
+ * in one piece and returns FINROM_ERR_UNSUPPORTED ("the one-sample form was announced but not taken") when the switch
+ * cuts it; leave the switch unset around that entry point.  A piece chooses its kernels by its own size, so a sample's bits are those of a call on the piece
+ * alone, not those of the one-piece call.  finrom_rom_solve makes the pieces equal; finrom_rom_grad cuts whole pieces and leaves
+ * the rest to the last one. */
 int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S,
                      double* w_r, double* qoi_r, double* A_r, double* B_r,
                      int32_t* info, void* stream);
@@ -480,7 +517,12 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode);
  * finrom_rom_set_gradient installs the host-precomputed blocks G_pi = (A_p Phi)^T (A_i Phi), one r x r matrix
  * per listed pair (p in 0..P with 0 = constant term, i in 0..P-1), each stored COLUMN by column.
  * finrom_rom_grad: theta [S x P], data [n_obs] (data_per_sample = 0) or [S x n_obs] (1) ->
- * J [S], g [S x P]; optional w_r [S x r], qoi_r [S x n_obs]; info as for finrom_rom_solve.  Any supported r (<= 208). */
+ * J [S], g [S x P]; optional w_r [S x r], qoi_r [S x n_obs]; info as for finrom_rom_solve (bit 1 OR-ed in, nothing cleared; pieces
+ * and FINROM_ROM_WORKSPACE_BYTES as there).  Any supported r (<= 208).
+ * A flagged sample: J and every entry of g and qoi_r are NaN, w_r is not all finite; every other sample keeps its bits -- the
+ * fifteen that share a 16-sample MFMA tile of the batched contraction with it included.  A NaN in a sample's data row
+ * (data_per_sample = 1) leaves info, qoi_r and w_r as for the clean data and makes J and every entry of g NaN, for that sample
+ * alone.  The arrival counters of the small contraction are back at zero behind every call, a poisoned one included. */
 int finrom_rom_set_gradient(finrom_rom_t h, int32_t npairs, const int32_t* pair_p, const int32_t* pair_i,
                             const double* G);
 int finrom_rom_grad(finrom_rom_t h, const double* theta, const double* data, int32_t data_per_sample,
@@ -914,7 +956,8 @@ int finrom_sampler_pullback(finrom_sampler_t h, const double* g, int64_t S, doub
  * so the HBM-bound sparse solve overlaps the MFMA-bound projection.
  * Sop: device [P x xdim] (P = the ROM's parameter count, xdim = the FOM's).  Optional
  * outputs (NULL to skip): w [S x n], w_r [S x r], theta [S x P], err [S x n_obs].
- * info [S] must be zero-initialised by the caller (bits are OR-ed in). */
+ * info [S] must be zero-initialised by the caller: bit 0 (FOM half) and bit 1 (ROM half) are OR-ed in, nothing is cleared, and
+ * behind the roomy projection kernel a row whose info is not 0 -- set by this call or before it -- gets NaN in qoi_r and err. */
 int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop,
                        const double* x, int64_t S,
                        double* qoi, double* qoi_r, double* err,
