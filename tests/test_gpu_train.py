@@ -7,47 +7,10 @@ import copy
 import numpy as np
 import pytest
 
-from bayesianinferencedl_amd.deep_learning.dl_model import ResBnFcModel, TREE_KEYS
+from bayesianinferencedl_amd.deep_learning.dl_model import ResBnFcModel
+from train_cases import ULP32, deviations, leaves, perturbed, probe
 
 pytestmark = pytest.mark.gpu
-ULP32 = float(np.finfo(np.float32).eps)
-
-
-def probe(n_in, S, n_out=9, seed=0):
-    """Seeded synthetic pairs: fields exp(0.3 xi), targets 0.05 tanh(20 log(x) T), T = randn(n_in, n_out) / n_in."""
-    rng = np.random.default_rng(seed)
-    X = np.exp(0.3 * rng.standard_normal((S, n_in)))
-    T = rng.standard_normal((n_in, n_out)) / n_in
-    return X, 0.05 * np.tanh(20 * np.log(X) @ T)
-
-
-def perturbed(n_in, n_w, L, n_out, seed=1):
-    m = ResBnFcModel(n_in, n_out, L, n_w, seed)
-    rng = np.random.default_rng(seed + 100)
-    for u in m.units + [m.head]:
-        u["gamma"] = rng.uniform(0.5, 1.5, u["gamma"].shape).astype(np.float32)
-        u["beta"] = rng.normal(0, 0.3, u["beta"].shape).astype(np.float32)
-        u["b"] = rng.normal(0, 0.1, u["b"].shape).astype(np.float32)
-    m.b0 = rng.normal(0, 0.1, m.b0.shape).astype(np.float32)
-    return m
-
-
-def leaves(tree):
-    """[(name, array, gradient zero in exact arithmetic?)]: gradients and, under mean / var, the batch statistics."""
-    n = len(tree["layers"])
-    out = [("W0", tree["W0"], False), ("b0", tree["b0"], True)]
-    for i, u in enumerate(tree["layers"]):
-        out += [(f"l{i}_{k}", u[k], k == "b" and i < n - 1) for k in TREE_KEYS]
-    return [(nm, np.asarray(a, dtype=np.float64), z) for nm, a, z in out]
-
-
-def deviations(tree, ref):
-    """name -> max |a - ref| over the tensor, relative to the yardstick tensor's largest entry; for the biases whose gradient is
-    zero in exact arithmetic, to the largest gradient of the step."""
-    R = leaves(ref)
-    gmax = max(np.abs(b).max() for nm, b, _ in R if not nm.endswith(("mean", "var")))
-    return {nm: np.abs(a - b).max() / (gmax if z or np.abs(b).max() == 0 else np.abs(b).max())
-            for (nm, a, z), (_, b, _) in zip(leaves(tree), R)}
 
 
 def cuda_rows(rows):
