@@ -13,8 +13,8 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libfinrom_hip.so")
 # the host layer behind the C ABI: what build_asan() instruments
 API_SOURCES = ["api_runtime.hip", "api_fom.hip", "api_rom.hip", "api_infer.hip", "api_hmc.hip", "fom_band_tables.hip", "rom_tables.hip"]
-SOURCES = API_SOURCES + ["fom_kernels.hip", "fom_band.hip", "fom_band_wide.hip", "fom_band_adjoint.hip", "rom_kernels.hip", "rom_proj_wide.hip", "rom_proj_half.hip", "rom_proj_single.hip", "rom_onesample.hip", "rom_gram.hip", "util_kernels.hip", "mlp_kernels.hip", "mlp_surrogate.hip", "mlp_train.hip", "hmc_kernels.hip", "hmc_metric.hip", "hmc_stats.hip", "hmc_model.hip", "hmc_ml.hip", "hmc_nuts.hip", "hmc_da.hip", "lbfgs_kernels.hip", "field_prior.hip", "comm.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("finrom_core.h", "finrom_internal.h", "rom_proj_device.h", "fom_band_device.h", "mlp_device.h", "mlp_surrogate.h", "hmc_ml_device.h", "block_reduce.h", "api_private.h", "rom_tables.h")] + [os.path.join(ROOT, "include", "finrom.h")]
+SOURCES = API_SOURCES + ["fom_kernels.hip", "fom_band.hip", "fom_band_wide.hip", "fom_band_adjoint.hip", "rom_kernels.hip", "rom_proj_wide.hip", "rom_proj_half.hip", "rom_proj_single.hip", "rom_onesample.hip", "rom_gram.hip", "util_kernels.hip", "mlp_kernels.hip", "mlp_surrogate.hip", "mlp_train.hip", "hmc_kernels.hip", "hmc_metric.hip", "hmc_stats.hip", "hmc_model.hip", "hmc_ml.hip", "hmc_nuts.hip", "hmc_nuts_model.hip", "hmc_da.hip", "lbfgs_kernels.hip", "field_prior.hip", "comm.hip"]
+HEADERS = [os.path.join(CSRC, h) for h in ("finrom_core.h", "finrom_internal.h", "rom_proj_device.h", "fom_band_device.h", "mlp_device.h", "mlp_surrogate.h", "hmc_ml_device.h", "hmc_nuts_device.h", "block_reduce.h", "api_private.h", "rom_tables.h")] + [os.path.join(ROOT, "include", "finrom.h")]
 
 
 def _deps(path, seen=None):

@@ -89,6 +89,11 @@ class HmcState(C.Structure):
                 ("accept", C.c_void_p), ("trace", C.c_void_p), ("loss", C.c_void_p), ("info", C.c_void_p)]
 
 
+class HmcNutsTree(C.Structure):
+    _fields_ = [("ws", C.c_void_p), ("seeds", C.c_void_p), ("proposal0", C.c_int64), ("max_depth", C.c_int32),
+                ("state_loss", C.c_void_p), ("tree", C.c_void_p), ("accept_stat", C.c_void_p), ("active", C.c_void_p)]
+
+
 class HmcStats(C.Structure):
     _fields_ = [("C", C.c_int64), ("n", C.c_int32), ("proposal0", C.c_int64), ("burn", C.c_int64), ("batch", C.c_int64),
                 ("pt", C.c_void_p), ("accept", C.c_void_p), ("cand", C.c_void_p), ("cand_loss", C.c_void_p),
@@ -220,6 +225,12 @@ SIGNATURES = {
     "finrom_hmc_trajectory_ml": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "finrom_hmc_nuts_ml": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_ws_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "finrom_hmc_nuts_begin": (C.c_int, [C.POINTER(HmcState), C.POINTER(HmcNutsTree), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p]),
+    "finrom_hmc_nuts_leaf": (C.c_int, [C.POINTER(HmcState), C.POINTER(HmcNutsTree), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_end": (C.c_int, [C.POINTER(HmcState), C.POINTER(HmcNutsTree), C.c_void_p]),
     "finrom_metric_create": (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "finrom_metric_destroy": (None, [C.c_void_p]),
     "finrom_metric_apply": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -74,9 +74,17 @@ the i.i.d. chain of that network with mean 0 and tau 1.  With an ml_form nothing
 max_treedepth=7, target_accept=0.98)`) in the place of the fixed-length trajectory and its Metropolis test: multinomial NUTS with the
 generalised U-turn criterion, identity mass, eps the caller's (no adaptation).  A call makes (n_evals - 1) // n_leapfrog transitions,
 the draws the same call makes without nuts=.  run_chains: nuts.transition_iterative over any callable, chain by chain.  Device
-functions: model="ml" alone -- a transition is ONE finrom_hmc_nuts_ml call (the tree's kernel, one 1024-thread workgroup per chain, and the counters'
-advance behind it: csrc/hmc_nuts.hip);
-it implies the library form (ml_form None or "trajectory").  It needs rng="philox" (momenta as before, the tree's direction bits and
+functions, two library forms (fused=False is refused).  model="ml": a transition is ONE finrom_hmc_nuts_ml call (the tree's kernel, one
+1024-thread workgroup per chain, and the counters' advance behind it: csrc/hmc_nuts.hip); it implies the library form (ml_form None or
+"trajectory").  model="romml" | "rom" | "fom", both priors: ONE LEAF PER ROUND (csrc/hmc_nuts_model.hip; the statement nuts.LeafMachine /
+transition_lockstep) -- a transition is finrom_hmc_nuts_begin, for j = 0, 1, ... the 2^j rounds of doubling j, finrom_hmc_nuts_end; a
+round clears info, runs the model's own launches at Kq[0] (finrom_fom_gradient; finrom_romml_grad's plain launches; finrom_rom_grad at
+theta_out, which begin and leaf write themselves; under a prior finrom_sampler_field / _pullback around the first two, the plain ROM
+whitened through A = Sop U^T) and finrom_hmc_nuts_leaf, which keeps the tree's state in a workspace.  Every chain's doubling j covers
+the same rounds, so the host reads active [C] back once per doubling, at most max_depth small read-backs per transition; a chain that
+has ended sits at its draw.  graph=True captures begin, ONE round and end once each and replays them; the start point's evaluation is
+a round too (_run_nuts_rounds), so a run continued with proposal0= is the uninterrupted one to the byte.  The result gains nuts_rounds
+and nuts_readbacks.  Nuts(metric=) is refused with these three models.  Either form needs rng="philox" (momenta as before, the tree's direction bits and
 uniforms from counter words 3 and 4, philox.nuts_top / nuts_leaf).  The result gains tree [proposals, C, 4] int32 (depth, leapfrog
 steps, stop reason: 0 depth limit, 1 tree turned, 2 sub-tree turned, 3 diverged; moved) and accept_stat [proposals, C], the mean of
 min(1, exp(H0 - H)) over the leaves: what dual averaging would consume.  accept counts the transitions whose draw is not the point
@@ -839,16 +847,23 @@ class _DeviceChains:
         _check_correct(a.correct, a.stats, who, a.model)
         _check_ml_form(a.ml_form, a.model, who, a.fused)
         _check_nuts(a.nuts, a.rng, a.metric, a.correct, a.record, who)
-        if a.nuts is not None:                                       # the device has the transition for one model, in one form
-            if a.model != "ml":
-                raise ValueError(f"{who}: nuts= on the device belongs to model='ml'; model={a.model!r} has the host statement "
-                                 f"(run_chains(..., nuts=))")
+        if a.nuts is not None:                                       # two library forms: one launch per transition ("ml"), one leaf per launch
             if a.fused is not None and not a.fused:
-                raise ValueError(f"{who}: nuts= is a library form (finrom_hmc_nuts_ml); fused=False asks for the torch-op form")
+                raise ValueError(f"{who}: nuts= is a library form (finrom_hmc_nuts_ml; finrom_hmc_nuts_begin / _leaf / _end); fused=False "
+                                 f"asks for the torch-op form")
             if a.ml_form == "steps":
                 raise ValueError(f"{who}: nuts= is one launch per transition; ml_form='steps' asks for three launches per step")
             from .nuts import Nuts
             self.nuts_metric = Nuts.metric_for(a.nuts, np.shape(a.K0)[-1], who)     # (refused here where its n is not the chains')
+            if a.model != "ml":
+                holder, name, need = {"fom": (a.solver, "solver=Fin", "gradient_batch"), "rom": (a.solver_r, "solver_r=AffineROMFin", "grad_reduced_batch"),
+                                      "romml": (a.solver_r, "solver_r=AffineROMFin", "grad_romml_batch")}[a.model]
+                if not hasattr(holder, need):
+                    raise ValueError(f"{who}: nuts= with model={a.model!r} launches the model's own gradient between two leaves and needs "
+                                     f"{name} (the transition in one launch belongs to model='ml' and its surrogate)")
+                if self.nuts_metric is not None:
+                    raise ValueError(f"{who}: Nuts(metric=...) with model={a.model!r}: the leaf kernel (finrom_hmc_nuts_leaf) has no form under "
+                                     f"the Laplace metric; the metric's transition is model='ml' alone (finrom_hmc_nuts_ml_metric)")
 
     def allocate(self):
         import torch
@@ -1125,6 +1140,146 @@ def _fused_form(a):
     return bind
 
 
+def _run_nuts_rounds(a, ch, st, Kq0, loss, info):
+    """run_chains_fused under nuts= for model "fom" | "rom" | "romml": the No-U-turn transition with ONE LEAF PER ROUND of all chains
+    (csrc/hmc_nuts_model.hip; the statement: nuts.LeafMachine / transition_lockstep).  ch: the allocated _DeviceChains, st its
+    finrom_hmc_state, Kq0 the position every round evaluates, loss / info the evaluation's misfit and flags.
+    A transition: finrom_hmc_nuts_begin; for j = 0, 1, ... the 2^j rounds of doubling j; finrom_hmc_nuts_end (finrom_hmc_stats_update
+    behind it under stats=).  A round: info cleared, the model's own launches at Kq[0], finrom_hmc_nuts_leaf:
+      fom    i.i.d.  finrom_fom_gradient at Kq[0] -> grad
+             field   finrom_sampler_field -> finrom_fom_gradient -> finrom_sampler_pullback -> grad (whitened: mean zeros, c_pri = 1)
+      romml  the same two with finrom_romml_grad, its plain launches
+      rom    theta_out = theta0 + A Kq[0] written by begin / leaf themselves; finrom_rom_grad at it -> g_theta; i.i.d. A = Sop, under a
+             prior A = Sop U^T, theta0 = Sop m: no field, no triangular product.
+    Every chain's doubling j covers the same rounds, so the host reads active [C] back ONCE per doubling and stops when no chain is
+    active: at most max_depth small read-backs per transition.  graph=True: begin, ONE round and end are each captured once; the leaf
+    kernel reads j, i, m and d from the workspace, so the round's graph is replayed with no node parameter changed.
+    The start point's evaluation is a round too (finrom_hmc_nuts_leaf with active = 2), before any capture: it warms the model's
+    workspaces up with the same C and leaves the state's U and dU in a leaf's arithmetic, so a run continued with proposal0= from a
+    draw (K, or V under a prior; an explicit mean=) is the uninterrupted run to the byte."""
+    import ctypes as C
+    import torch
+    from .. import _ffi
+    L, check = _ffi.lib(), _ffi.check
+    model, prior, solver_r, depth = a.model, a.prior, a.solver_r, a.nuts.max_depth
+    K = ch.K
+    Cn, n = K.shape
+    f64, i32 = dict(dtype=torch.float64, device=K.device), dict(dtype=torch.int32, device=K.device)
+    data_p, per = ch.data_t.data_ptr(), ch.per_sample
+
+    def stream():
+        return torch.cuda.current_stream().cuda_stream
+
+    ws = torch.zeros(L.finrom_hmc_nuts_ws_bytes(Cn, n, depth) // 8, **f64)
+    seeds_t = torch.as_tensor(ch.seeds64.view(np.int64), dtype=torch.int64, device=K.device)
+    tree, accept_stat = torch.zeros(ch.n_prop, Cn, 4, **i32), torch.zeros(ch.n_prop, Cn, **f64)
+    active, state_loss = torch.zeros(Cn, **i32), torch.zeros(Cn, **f64)
+    tr = _ffi.HmcNutsTree(ws=ws.data_ptr(), seeds=seeds_t.data_ptr(), proposal0=a.proposal0, max_depth=depth, state_loss=state_loss.data_ptr(),
+                          tree=tree.data_ptr(), accept_stat=accept_stat.data_ptr(), active=active.data_ptr())
+    grad = gth = A_t = th0 = theta = None                            # (a round holds, by name, every tensor it passes by address)
+    P = 0
+    if prior is not None:
+        F, gF, fs_h, fmean_p = torch.zeros_like(K), torch.zeros_like(K), ch.fs._h, ch.fmean.data_ptr()
+    if model == "rom":
+        rom = solver_r._rom
+        solver_r._ensure_gradient()
+        S_np = np.ascontiguousarray(solver_r.dsigma_dk, dtype=np.float64)
+        P = S_np.shape[0]
+        A_t = torch.as_tensor(np.ascontiguousarray(S_np @ prior.U.T) if prior is not None else S_np, **f64)
+        th0 = torch.as_tensor(S_np @ prior.mean, **f64) if prior is not None else None
+        theta, gth = torch.zeros(Cn, P, **f64), torch.zeros(Cn, P, **f64)
+
+        def evaluate():
+            check(L.finrom_rom_grad(rom._h, theta.data_ptr(), data_p, per, Cn, loss.data_ptr(), gth.data_ptr(), None, None, info.data_ptr(),
+                                    stream()), "finrom_rom_grad")
+    else:
+        grad = torch.zeros_like(K)
+        if model == "fom":
+            fom = a.solver._engine("field")
+            fom._enable_gradient()
+
+            def at(X, g):
+                check(L.finrom_fom_gradient(fom._h, X.data_ptr(), data_p, per, Cn, g.data_ptr(), loss.data_ptr(), None, info.data_ptr(),
+                                            stream()), "finrom_fom_gradient")
+        else:
+            rom, mlp, Sop = solver_r._rom, solver_r._dev_model, solver_r._avg._S
+            solver_r._ensure_gradient()
+
+            def at(X, g):
+                check(L.finrom_romml_grad(rom._h, mlp._h, Sop.ptr, X.data_ptr(), data_p, per, Cn, g.data_ptr(), loss.data_ptr(), None, None,
+                                          info.data_ptr(), stream()), "finrom_romml_grad")
+                Sop.used_on(stream())
+        if prior is None:
+            def evaluate():
+                at(Kq0, grad)
+        else:
+            def evaluate():
+                check(L.finrom_sampler_field(fs_h, fmean_p, Kq0.data_ptr(), Cn, F.data_ptr(), stream()), "finrom_sampler_field")
+                at(F, gF)
+                check(L.finrom_sampler_pullback(fs_h, gF.data_ptr(), Cn, grad.data_ptr(), stream()), "finrom_sampler_pullback")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    map_args = (ptr(A_t), ptr(th0), P, ptr(theta))
+
+    def begin(state=st):
+        check(L.finrom_hmc_nuts_begin(C.byref(state), C.byref(tr), *map_args, stream()), "finrom_hmc_nuts_begin")
+
+    def round_():
+        info.zero_()
+        evaluate()
+        check(L.finrom_hmc_nuts_leaf(C.byref(st), C.byref(tr), ptr(grad), ptr(gth), *map_args, stream()), "finrom_hmc_nuts_leaf")
+
+    def end():
+        check(L.finrom_hmc_nuts_end(C.byref(st), C.byref(tr), stream()), "finrom_hmc_nuts_end")
+        if ch.ds is not None:                                        # (Kq[0] holds the draw: where it moved, the sums take it)
+            ch.ds.update(field_of_draw(), state_loss)
+
+    def field_of_draw():
+        if prior is None:
+            return Kq0
+        check(L.finrom_sampler_field(fs_h, fmean_p, Kq0.data_ptr(), Cn, F.data_ptr(), stream()), "finrom_sampler_field")
+        return F
+
+    # evaluation 0, a round: Kq[0] = K (and theta_out) by a begin with eps = 0, the model, the leaf call that writes the state
+    st0 = _ffi.HmcState.from_buffer_copy(st)
+    st0.eps = 0.0
+    begin(st0)
+    active.fill_(2)
+    round_()
+    ch.evals += 1
+    ch.start(ch.U.clone(), ch.dU.clone())
+    ch.start_stats(field_of_draw().clone() if a.stats is not None else None, state_loss)
+    counts = dict(rounds=0, readbacks=0)
+    graphs = None
+    if a.graph and ch.n_prop > 0:
+        def captured(fn):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn()
+            return g
+        torch.cuda.synchronize()
+        graphs = tuple(captured(fn) for fn in (begin, round_, end))
+
+    def transition(rec=False):
+        g_begin, g_round, g_end = graphs if graphs is not None else (None, None, None)
+        g_begin.replay() if graphs else begin()
+        for j in range(depth):
+            for _ in range(1 << j):
+                g_round.replay() if graphs else round_()
+            counts["rounds"] += 1 << j
+            counts["readbacks"] += 1
+            if not bool(active.any()):                               # ONE small read-back per doubling
+                break
+        g_end.replay() if graphs else end()
+
+    res = ch.run(transition, SimpleNamespace(replay=transition) if graphs else None, fused=True, nuts=depth, metric_rho=0)
+    res["nuts_rounds"], res["nuts_readbacks"] = counts["rounds"], counts["readbacks"]
+    res["tree"], res["accept_stat"] = tree.cpu().numpy(), accept_stat.cpu().numpy()
+    if np.any(res["tree"][:, :, 2] < 0):
+        raise _ffi.FinromError(f"run_chains_fused: a chain was still active after 2^{depth} - 1 rounds (tree rows with reason -1)")
+    res["n_evals"] = 1 + (int(res["tree"][:, :, 1].sum(axis=0).max()) if ch.n_prop else 0)
+    return res
+
+
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
                      keep_trace=False, graph=True, data=None, block=32, prior=None, metric=None, rng="numpy", proposal0=0,
                      stats=None, model="romml", solver=None, correct=None, surrogate=None, ml_form=None, nuts=None):
@@ -1141,6 +1296,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     statement nuts.transition_iterative -- in the place of begin, steps and end; the momenta are finrom_hmc_draw's, finrom_sampler_field
     and finrom_hmc_stats_update follow where prior= / stats= ask for them, under a prior the chain runs on surrogate.whitened(prior).
     The result gains tree and accept_stat as run_chains has them.
+    nuts=Nuts(max_depth) (model="romml" | "rom" | "fom"): one leaf per round, finrom_hmc_nuts_begin / _leaf / _end around the model's
+    own launches (_run_nuts_rounds); the same result fields, and nuts_rounds, nuts_readbacks.
     Raises _ffi.FinromError (FINROM_ERR_UNSUPPORTED) where the library has no such step (_fused_form) before anything is allocated:
     run_chains_device(fused=None) then takes the torch-op form.
     Same random numbers, same order of evaluations and the same chains as run_chains up to the rounding of fused multiply-adds; the
@@ -1168,6 +1325,8 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                        loss=loss.data_ptr(), info=info.data_ptr())
     st0 = _ffi.HmcState.from_buffer_copy(st)                         # evaluation 0: a "step" of length zero from K itself
     st0.eps = 0.0
+    if nuts is not None and model != "ml":
+        return _run_nuts_rounds(a, ch, st, Kq[0], loss, info)
     form = bind(ch, Kq, loss)
     step, mh = form.step, form.mh
 

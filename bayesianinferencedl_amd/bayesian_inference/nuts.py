@@ -25,6 +25,12 @@ Two forms that are given the same draws and return the same tree: transition_rec
 the form the kernel executes.  Both report `margin`: the smallest relative gap between the two sides of any comparison made (a U-turn
 product relative to |rho| |p|, a selection test relative to its larger side), so that a test can require its inputs to decide clearly.
 
+LeafMachine is transition_iterative cut at the model call -- begin() returns the first point to evaluate, leaf(loss, grad, bad) takes
+its evaluation and returns the next, result() the same namespace --, with all of its state named: the statement of finrom_hmc_nuts_begin /
+_leaf / _end (csrc/hmc_nuts_model.hip), which make one leaf per launch so that any model's launches can sit between two leaves.
+transition_lockstep advances C machines together with one batched call per round: the statement of hmc.py's device form for "fom",
+"rom" and "romml".
+
 `fma(a, x, y)` and `dot(x, y)` may be given: the defaults are the plain NumPy expressions; tests/hmc_cases.fma and the emulated
 block_sum_1024 make the iterative form the kernel's arithmetic bit for bit.
 
@@ -148,15 +154,19 @@ class _Transition:
         self.walker = self.edge[self.d]
         self.W_sub, self.rho_sub, self.sub_cand = 0.0, np.zeros_like(self.rho), None
 
-    def leaf(self):
-        """One leapfrog step of the walker -> its (momentum, velocity), or None: diverged."""
+    def drift(self):
+        """The walker's first half kick and its drift -> the point to evaluate (leaf m of the transition)."""
         k, p, dU, _ = self.walker
         d, fma = self.d, self.fma
         self.m += 1
-        ph = fma(-d * self.h, dU, p)
-        kn = fma(d * self.eps, self.velocity(ph), k)
-        loss, grad, bad = self.f(kn[None])
-        loss, grad, bad = float(np.asarray(loss)[0]), np.asarray(grad, dtype=np.float64)[0], bool(np.asarray(bad)[0])
+        self.ph = fma(-d * self.h, dU, p)
+        self.kn = fma(d * self.eps, self.velocity(self.ph), k)
+        return self.kn
+
+    def arrive(self, loss, grad, bad):
+        """The evaluation of drift()'s point: the second half kick, the energy, the streamed selection -> the leaf's (momentum,
+        velocity), or None: diverged."""
+        kn, ph, d, fma = self.kn, self.ph, self.d, self.fma
         with np.errstate(all="ignore"):
             dk = kn - self.mean
             dUn = fma(self.coef, grad, dk)
@@ -177,6 +187,13 @@ class _Transition:
         self.rho_sub = self.rho_sub + pn
         self.walker = (kn, pn, dUn, vn)
         return pn, vn
+
+    def leaf(self):
+        """One leapfrog step of the walker -> its (momentum, velocity), or None: diverged."""
+        kn = self.drift()
+        loss, grad, bad = self.f(kn[None])
+        loss, grad, bad = float(np.asarray(loss)[0]), np.asarray(grad, dtype=np.float64)[0], bool(np.asarray(bad)[0])
+        return self.arrive(loss, grad, bad)
 
     def adopt(self, j):
         """The finished sub-tree joins the tree -> whether the tree has turned."""
@@ -199,6 +216,9 @@ class _Transition:
             if self.adopt(j):
                 self.reason = STOP_TREE_TURNED
                 break
+        return self.result()
+
+    def result(self):
         k, dU, U, loss = self.cand
         return SimpleNamespace(k=k, dU=dU, U=U, loss=loss, depth=self.depth, steps=self.m, reason=self.reason, moved=self.moved,
                                accept_stat=self.sum_acc / self.m, margin=self.margin, directions=self.directions,
@@ -243,6 +263,109 @@ def transition_iterative(value_and_grad, k, U, dU, loss, p0, *, seed, proposal, 
         return 0
     out = t.run(subtree)
     out.turn_levels = t.max_span
+    return out
+
+
+class LeafMachine:
+    """transition_iterative cut at the model call (identity mass): the statement of finrom_hmc_nuts_begin / _leaf / _end
+    (csrc/hmc_nuts_model.hip), where any model's launches sit between two leaves.
+        begin(k, U, dU, loss, p0)  START, begin_subtree(0) and the first drift -> the point to evaluate;
+        leaf(loss, grad, bad)      the evaluation of that point -> the next point, or None: the transition has ended;
+        result()                   the namespace transition_iterative returns.
+    Every operation of transition_iterative in its order (fma=, dot= passed through): driven over a callable, the same bits.  ALL of its
+    state is named here -- what the kernel keeps in memory between two launches: j the doubling, i the leaf inside the sub-tree, the
+    leaf count m, the direction d and u_top, the walker (k, p, dU) with the half-kicked p1/2 and the drifted k', both edges, rho and
+    rho_sub, the checkpoints (p, rho_sub) per level, H0, W, W_sub, the sum of min(1, w), the sub-tree's candidate and the tree's (the
+    chain's state itself), depth, moved, reason, active.  `position`: the point of the next evaluation while active, then the draw."""
+
+    def __init__(self, *, seed, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None):
+        self.kw = dict(seed=seed, proposal=proposal, eps=eps, c_lik=c_lik, c_pri=c_pri, mean=mean, max_depth=max_depth, fma=fma, dot=dot)
+        self.max_depth, self.active, self.t = max_depth, False, None
+
+    def begin(self, k, U, dU, loss, p0):
+        kw = self.kw
+        t = self.t = _Transition(None, k, U, dU, loss, p0, kw["seed"], kw["proposal"], kw["eps"], kw["c_lik"], kw["c_pri"], kw["mean"],
+                                 self.max_depth, kw["fma"], kw["dot"])
+        t.max_span = 0
+        self.ck_p, self.ck_rho = [None] * self.max_depth, [None] * self.max_depth
+        self.j, self.i, self.active = 0, 0, True
+        t.begin_subtree(0)
+        self.position = t.drift()
+        return self.position
+
+    # the explicit state, by the names of the text above
+    m = property(lambda self: self.t.m)
+    d = property(lambda self: self.t.d)
+    depth = property(lambda self: self.t.depth)
+    moved = property(lambda self: self.t.moved)
+    reason = property(lambda self: self.t.reason)
+
+    def _end(self, reason):
+        self.t.reason, self.active = reason, False
+        self.position = self.t.cand[0]
+        return None
+
+    def leaf(self, loss, grad, bad):
+        if not self.active:
+            raise ValueError("LeafMachine.leaf: the transition has ended (or has not begun)")
+        t, i = self.t, self.i
+        pv = t.arrive(float(loss), np.asarray(grad, dtype=np.float64), bool(bad))
+        if pv is None:
+            return self._end(STOP_DIVERGED)
+        p, v = pv
+        i_max = bin(i >> 1).count("1")
+        if not i & 1:
+            self.ck_p[i_max], self.ck_rho[i_max] = p, t.rho_sub
+        else:
+            i_min = i_max - _trailing_ones(i) + 1
+            for c in range(i_max, i_min - 1, -1):
+                rho_s = (t.rho_sub - self.ck_rho[c]) + self.ck_p[c]
+                if t.turning(rho_s, self.ck_p[c], v):
+                    t.max_span = max(t.max_span, i_max - c + 1)
+                    return self._end(STOP_SUBTREE_TURNED)
+        self.i += 1
+        if self.i == 1 << self.j:                                    # the sub-tree is finished: adoption, the tree's test, the next draw
+            if t.adopt(self.j):
+                return self._end(STOP_TREE_TURNED)
+            if self.j + 1 == self.max_depth:
+                return self._end(STOP_DEPTH)
+            self.j, self.i = self.j + 1, 0
+            t.begin_subtree(self.j)
+        self.position = t.drift()
+        return self.position
+
+    def result(self):
+        if self.active or self.t is None:
+            raise ValueError("LeafMachine.result: the transition has not ended")
+        out = self.t.result()
+        out.turn_levels = self.t.max_span
+        return out
+
+
+def transition_lockstep(value_and_grad, K, U, dU, loss, P0, *, seeds, proposal, eps, c_lik, c_pri, mean, max_depth, fma=None, dot=None):
+    """One transition of C chains TOGETHER, the statement of the device form for models whose bits depend on the batch: C LeafMachines,
+    ONE call value_and_grad(X [C, n]) -> (loss [C], grad [C, n], bad [C]) per round.  A chain that has ended sits at its draw: its row
+    of X is the draw's position and its evaluation is ignored.  K, dU, P0 [C, n], U, loss [C], seeds [C], mean [C, n] (or what
+    broadcasts to it).  -> the list of the C namespaces transition_iterative returns, each with `rounds`: the rounds the batch made
+    (at most 2^max_depth - 1)."""
+    K = np.asarray(K, dtype=np.float64)
+    C = len(K)
+    mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), K.shape)
+    ms = [LeafMachine(seed=seeds[c], proposal=proposal, eps=eps, c_lik=c_lik, c_pri=c_pri, mean=mean[c], max_depth=max_depth, fma=fma,
+                      dot=dot) for c in range(C)]
+    for c, mc in enumerate(ms):
+        mc.begin(K[c], U[c], dU[c], loss[c], P0[c])
+    rounds = 0
+    while any(mc.active for mc in ms):
+        ls, gr, bad = value_and_grad(np.stack([mc.position for mc in ms]))
+        ls, gr, bad = np.asarray(ls, dtype=np.float64), np.asarray(gr, dtype=np.float64), np.asarray(bad, dtype=bool)
+        rounds += 1
+        for c, mc in enumerate(ms):
+            if mc.active:
+                mc.leaf(ls[c], gr[c], bad[c])
+    out = [mc.result() for mc in ms]
+    for r in out:
+        r.rounds = rounds
     return out
 
 

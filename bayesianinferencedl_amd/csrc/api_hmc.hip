@@ -374,6 +374,69 @@ int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, const uint64
   return launch_hmc_nuts_ml(m, h, nd, data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p, (float*)mlp->tape.p, out,
                             (hipStream_t)stream);
 }
+}  // extern "C"
+// ---- the No-U-turn transition under any model, one leaf per launch (hmc_nuts_model.hip; hmc.py model="fom" | "rom" | "romml", nuts=) ----
+// everything the three entry points refuse before any device call; the workspace is the caller's, cut here into its three parts
+static int hmc_nuts_tree_dev(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, HmcDev* h, NutsTreeDev* d, const char* who) {
+  if (int rc = hmc_dev(a, h, who)) return rc;
+  if (!tr || !tr->ws || !tr->seeds || !tr->state_loss || !tr->active) {
+    set_error(std::string(who) + ": null descriptor or null field in finrom_hmc_nuts_tree (only tree and accept_stat may be NULL)");
+    return FINROM_ERR_ARG;
+  }
+  if (a->c_pri == 0.0) { set_error(std::string(who) + ": c_pri = 0"); return FINROM_ERR_ARG; }
+  if (tr->max_depth < 1 || tr->max_depth > NUTS_MAX_DEPTH) {
+    set_error(std::string(who) + ": max_depth = " + std::to_string(tr->max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH));
+    return FINROM_ERR_ARG;
+  }
+  if (tr->proposal0 < 0) { set_error(std::string(who) + ": proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (((uintptr_t)tr->ws & 7u) != 0) { set_error(std::string(who) + ": ws is not aligned to 8 bytes"); return FINROM_ERR_ARG; }
+  if (a->C > 65535) { set_error(std::string(who) + ": C > 65535 (one grid row per chain)"); return FINROM_ERR_UNSUPPORTED; }
+  d->max_depth = tr->max_depth; d->proposal0 = tr->proposal0; d->seeds = (const unsigned long long*)tr->seeds;
+  d->ws = (double*)tr->ws;
+  d->scal = d->ws + (int64_t)(NUTS_TREE_FIXED_ARRAYS + 2 * tr->max_depth) * a->C * a->n;
+  d->ints = (int*)(d->scal + a->C * NUTS_TREE_SCALARS);
+  d->st_loss = tr->state_loss; d->tree = tr->tree; d->accept_stat = tr->accept_stat; d->active = tr->active;
+  return 0;
+}
+static int hmc_nuts_map(const char* who, const double* A, const double* theta0, int32_t P, double* theta_out, NutsMap* tm) {
+  if (int rc = hmc_model_map_check(who, A, P)) return rc;
+  if (A != nullptr && !theta_out) { set_error(std::string(who) + ": A without theta_out"); return FINROM_ERR_ARG; }
+  tm->A = A; tm->theta0 = A != nullptr ? theta0 : nullptr; tm->P = A != nullptr ? P : 0; tm->theta_out = A != nullptr ? theta_out : nullptr;
+  return 0;
+}
+extern "C" {
+int64_t finrom_hmc_nuts_ws_bytes(int64_t C, int32_t n, int32_t max_depth) {
+  if (C < 0 || n < 1 || max_depth < 1 || max_depth > NUTS_MAX_DEPTH) {
+    set_error("hmc_nuts_ws_bytes: C < 0, n < 1 or max_depth outside 1 .. " + std::to_string(NUTS_MAX_DEPTH)); return FINROM_ERR_ARG;
+  }
+  return hmc_nuts_tree_ws_bytes(C, n, max_depth);
+}
+int finrom_hmc_nuts_begin(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* A, const double* theta0, int32_t P,
+                          double* theta_out, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h; NutsTreeDev d; NutsMap tm;
+  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, "hmc_nuts_begin")) return rc;
+  if (int rc = hmc_nuts_map("hmc_nuts_begin", A, theta0, P, theta_out, &tm)) return rc;
+  return launch_hmc_nuts_begin(h, d, tm, (hipStream_t)stream);
+}
+int finrom_hmc_nuts_leaf(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* grad, const double* g_theta,
+                         const double* A, const double* theta0, int32_t P, double* theta_out, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h; NutsTreeDev d; NutsMap tm;
+  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, "hmc_nuts_leaf")) return rc;
+  if ((grad != nullptr) == (g_theta != nullptr)) {
+    set_error("hmc_nuts_leaf: exactly one of grad and g_theta must be given"); return FINROM_ERR_ARG;
+  }
+  if (g_theta != nullptr && !A) { set_error("hmc_nuts_leaf: g_theta without A"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_nuts_map("hmc_nuts_leaf", A, theta0, P, theta_out, &tm)) return rc;
+  return launch_hmc_nuts_leaf(h, d, grad, g_theta, tm, (hipStream_t)stream);
+}
+int finrom_hmc_nuts_end(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, void* stream) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h; NutsTreeDev d;
+  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, "hmc_nuts_end")) return rc;
+  return launch_hmc_nuts_end(h, d, (hipStream_t)stream);
+}
 
 // ---- low-rank metric (hmc_metric.hip) --------------------------------------------------------------------------------------------
 int finrom_metric_create(const double* Vt, const double* lam, int32_t n, int32_t rho, finrom_metric_t* out) {

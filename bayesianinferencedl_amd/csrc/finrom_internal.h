@@ -108,6 +108,25 @@ int launch_hmc_drift(const HmcDev& h, const double* k, double* k_out, const doub
 int launch_hmc_kick(const HmcDev& h, const double* kq, const double* grad, const double* g_theta, const double* A, int P,
                     double* grad_out, hipStream_t st);
 
+// hmc_nuts_model.hip (finrom_hmc_nuts_begin / _leaf / _end): the No-U-turn transition one leaf per launch, the tree's state in the
+// caller's workspace.  ws: NUTS_TREE_FIXED_ARRAYS + 2 max_depth arrays [C x n]; behind them scal [C x NUTS_TREE_SCALARS] doubles and
+// ints [C x NUTS_TREE_INTS] (hmc_nuts_tree_ws_bytes); st_loss [C]: the state's misfit; active [C]; tree, accept_stat: optional.
+// NutsMap: the optional map of finrom_hmc_drift (A NULL: none; P <= HMC_MODEL_MAXP).
+constexpr int NUTS_TREE_FIXED_ARRAYS = 13;
+constexpr int NUTS_TREE_SCALARS = 8;
+constexpr int NUTS_TREE_INTS = 8;
+struct NutsTreeDev {
+  int max_depth; long long proposal0;
+  const unsigned long long* seeds;
+  double* ws; double* scal; int* ints;
+  double* st_loss; int* tree; double* accept_stat; int* active;
+};
+struct NutsMap { const double* A; const double* theta0; int P; double* theta_out; };
+int64_t hmc_nuts_tree_ws_bytes(int64_t C, int n, int max_depth);
+int launch_hmc_nuts_begin(const HmcDev& h, const NutsTreeDev& a, const NutsMap& tm, hipStream_t st);
+int launch_hmc_nuts_leaf(const HmcDev& h, const NutsTreeDev& a, const double* grad, const double* g_theta, const NutsMap& tm, hipStream_t st);
+int launch_hmc_nuts_end(const HmcDev& h, const NutsTreeDev& a, hipStream_t st);
+
 // ---- low-rank metric M = I + V diag(lambda) V^T (hmc_metric.hip, finrom_metric_*, finrom_hmc_*_metric) -----------------------
 constexpr int METRIC_MAX_RHO = 64;
 // rows of MetricDev::coef: the c_j of y = x + sum_j c_j V_j (V_j . x) for the four maps (finrom.h's FINROM_METRIC_* codes), then

@@ -25,28 +25,16 @@
 // checkpoints and the edges.  Its maps run outside the forward pass, between the leaf's row pass and the leaf's sums.
 #include "hmc_ml_device.h"
 #include "block_reduce.h"
+#include "hmc_nuts_device.h"
 
 namespace finrom {
 
 namespace {
 
-__device__ __forceinline__ void nuts_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {                                      // Philox4x32-10, as util_kernels.hip has it
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 // element e of a per-chain array: the array's address stays a scalar and the element's byte offset one 32-bit register shared by all
 // arrays (a 64-bit address per array held across the forward pass does not fit beside it)
 __device__ __forceinline__ double& at(double* base, int e) { return *(double*)((char*)base + (unsigned)e * 8u); }
 __device__ __forceinline__ const double& at(const double* base, int e) { return *(const double*)((const char*)base + (unsigned)e * 8u); }
-__device__ __forceinline__ double nuts_uniform(const unsigned (&o)[4]) {      // [0, 1)
-  return (double)((((unsigned long long)o[1] << 32) | o[0]) >> 11) * 0x1.0p-53;
-}
 
 // the per-chain arrays of the workspace, [NUTS_ARRAYS][C][n]: the two edges (k, p, dU), the walker (its position ping-pongs as the
 // trajectory's does; beside its momentum p the half-kicked p1/2 the next leaf's drift takes), the sub-tree's candidate (k, dU), rho

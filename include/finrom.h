@@ -725,6 +725,79 @@ int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, int32
  * the first call with that C: that call is refused with FINROM_ERR_UNSUPPORTED and a message while a stream capture is open. */
 int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* st, const uint64_t* seeds, int64_t proposal0, int32_t max_depth,
                        const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream);
+/* The same transition under ANY model (hmc.py model="fom" | "rom" | "romml" with nuts=; the statement: nuts.py LeafMachine, which is
+ * transition_iterative cut at the model call): the reference samples with pm.NUTS under the FULL-ORDER operator (bayesian_inference/
+ * inference.py:21-57,165-166), whose gradient is many launches of many workgroups, so the tree cannot live in one launch.  Here it is
+ * ONE LEAF PER LAUNCH with the tree's bookkeeping in memory, and any model's launches sit between two leaves:
+ *   transition = finrom_hmc_nuts_begin;  rounds { clear info; the model's value and gradient at Kq[0] -> st->loss, st->info, grad or
+ *                g_theta;  finrom_hmc_nuts_leaf } until no chain is active (at most 2^max_depth - 1 rounds);  finrom_hmc_nuts_end.
+ * Layout of all three: one 1024-thread workgroup per chain (finrom_hmc_nuts_end: one thread per (chain, node)); element i of every
+ * per-chain array belongs to thread i % 1024; every sum in finrom_hmc_nuts_ml's order (thread t chains fused multiply-adds over
+ * i = t, t + 1024, ..., a butterfly inside each of the 16 waves, the wave sums pairwise in index order); every fused multiply-add is
+ * written fma(a, b, c) below and nothing else contracts; thread 0 decides and the workgroup follows; no workgroup waits on another.
+ * The Philox counters, both uniforms, the stop reasons, the tree row and accept_stat are finrom_hmc_nuts_ml's, word for word; with
+ * h = 0.5 eps c_pri, d = +-1 the sub-tree's direction, p = proposal0 + *pt:
+ *   finrom_hmc_nuts_begin  p0 = row *jt of P_block; H0 = U + |p0|^2 / 2; both edges (k, p, dU) = (K, p0, dU); rho = p0; W = 1; the sum
+ *                          of min(1, w) = 0; j = 0, i = 0, m = 0, depth = 0, moved = 0, reason = 0.  Sub-tree 0's draw: counter
+ *                          (p lo, p hi, 0, 3): d from o2 & 1, u_top; W_sub = 0.  The walker stands at d's edge with its first half
+ *                          kick made: p1/2 = fma(-d h, dU_edge, p_edge), rho_sub = 0; the first drift k' = fma(d eps, p1/2, k_edge) goes
+ *                          to Kq[0]; active[c] = 1.
+ *   finrom_hmc_nuts_leaf   for a chain with active[c] == 1 (one with active[c] == 0 is left as it is, to the byte), k' = Kq[0], m += 1:
+ *                          g[i] = grad[c][i], or (grad NULL) fma-chained from 0 over q = 0 .. P - 1: g = fma(g_theta[c][q], A[q][i], g);
+ *                          info[c] == 0:  dk = k' - mean;  dU' = fma(c_lik / c_pri, g, dk);  p' = fma(-d h, dU', p1/2);
+ *                          rho_sub += p';  an even i stores the checkpoint (p', rho_sub) at level popcount(i >> 1);
+ *                          U' = fma(c_lik, loss[c], 0.5 c_pri |dk|^2);  dE = (U' + 0.5 |p'|^2) - H0.
+ *                          info[c] != 0, dE not finite (a NaN or infinite loss makes it so) or dE > 1000: the transition ends, reason 3.
+ *                          Else w = exp(-dE); W_sub += w; the sum of min(1, w) += min(1, w); u_m from counter (p lo, p hi, m, 4); when
+ *                          u_m W_sub < w the sub-tree's candidate becomes (k', dU', U', loss[c]).  An odd i tests the checkpoints
+ *                          q = popcount(i >> 1) down to that minus (trailing one bits of i) plus 1: rho_s = (rho_sub - rho_q) + p_q,
+ *                          turning when rho_s . p_q <= 0 or rho_s . p' <= 0: the transition ends, reason 2.  i += 1.
+ *                          At the sub-tree's end (i == 2^j): when u_top W < W_sub the candidate is written into K, dU, U and state_loss
+ *                          (the candidate IS the state) and moved = 1; W += W_sub; rho += rho_sub; d's edge = (k', p', dU');
+ *                          depth = j + 1; rho . p_left <= 0 or rho . p_right <= 0: ends, reason 1; depth == max_depth: ends, reason 0;
+ *                          else j += 1, i = 0, the next sub-tree's draw and walker as in finrom_hmc_nuts_begin.
+ *                          Then either the next leaf's p1/2 = fma(-d h, dU', p') and drift k'' = fma(d eps, p1/2, k') into Kq[0], or,
+ *                          the transition over, active[c] = 0 and Kq[0] = K: every later round evaluates a point known to be good, and
+ *                          finrom_hmc_stats_update finds its cand there (with st->loss of the last round as cand_loss).
+ *                          THE START POINT'S EVALUATION is a round too: with Kq[0] = K (finrom_hmc_nuts_begin on a copy of the state
+ *                          with eps = 0 leaves k' = fma(0, p1/2, K) = K there, and theta_out with it), the model's launches, and the
+ *                          caller's active[c] = 2, the leaf call writes the STATE: dU = fma(c_lik / c_pri, g, K - mean) (0 where
+ *                          info[c] != 0), U = fma(c_lik, loss[c], 0.5 c_pri |K - mean|^2) (+inf where info[c] != 0 or not finite),
+ *                          state_loss[c] = loss[c], active[c] = 0 -- a leaf's arithmetic, so a chain continued from a draw starts
+ *                          from the bits the draw had.  Nothing else is touched.
+ *   finrom_hmc_nuts_end    accept[c] += moved; trace row *pt + 1 = K; tree [rows x C x 4] row *pt = (depth, m, reason, moved) and
+ *                          accept_stat [rows x C] row *pt = (the sum of min(1, w)) / m.  A chain still active cannot exist after
+ *                          2^max_depth - 1 rounds; one that is gets reason -1 and the call still returns 0.  Then *jt += 1, *pt += 1.
+ * With A [P x n] (1 <= P <= 16; DEVICE) begin and leaf also write theta_out[c][q] = theta0[q] + s_q (theta0 [P] or NULL = 0; ONE
+ * rounded addition), s_q = sum_i A[q][i] Kq[0][c][i] in the order above: finrom_hmc_drift's contract with 1024 threads.  The plain
+ * reduced model takes it as its input and returns g_theta; i.i.d. prior: A = Sop; whitened: A = Sop U^T, theta0 = Sop m.
+ * The workspace is the CALLER's: finrom_hmc_nuts_ws_bytes(C, n, max_depth) bytes at ws, 8-byte aligned -- 13 + 2 max_depth arrays
+ * [C x n] (both edges' k, p, dU; the walker's p', p1/2, dU'; the sub-tree candidate's k, dU; rho; rho_sub; a checkpoint (p, rho_sub)
+ * per level), then 8 doubles and 8 int32 per chain.  Nothing allocates: all three are legal while the stream is capturing.  The leaf
+ * kernel reads j, i, m and d from the workspace, so a captured round is replayed with no node parameter changed.  P, dUq, H0,
+ * lu_block and Kq[1] of the state are not used; st->loss and st->info are the last evaluation's, state_loss [C] is the STATE's misfit
+ * (it must hold the start point's before the first transition).
+ * Refused before any device call, with a message: a null state, descriptor or field of either (tree and accept_stat may be NULL),
+ * c_pri == 0, max_depth outside 1 .. 10, proposal0 < 0, a ws not aligned to 8 bytes, both or neither of grad and g_theta, g_theta
+ * without A, P outside 1 .. 16 where A is given, A without theta_out (FINROM_ERR_ARG); C > 65535 (FINROM_ERR_UNSUPPORTED).
+ * C == 0: returns 0, no launch, no counter moved.  finrom_hmc_nuts_ws_bytes: FINROM_ERR_ARG (negative) for C < 0, n < 1 or a
+ * max_depth outside 1 .. 10. */
+typedef struct {
+  void* ws;                             /* finrom_hmc_nuts_ws_bytes(C, n, max_depth) bytes, DEVICE */
+  const uint64_t* seeds;                /* [C], DEVICE */
+  int64_t proposal0;                    /* global index of the proposal *pt == 0 stands for */
+  int32_t max_depth;                    /* 1 .. 10 */
+  double* state_loss;                   /* [C] the state's misfit */
+  int32_t* tree;                        /* [rows x C x 4] or NULL */
+  double* accept_stat;                  /* [rows x C] or NULL */
+  int32_t* active;                      /* [C] 1 while the chain's transition runs */
+} finrom_hmc_nuts_tree;
+int64_t finrom_hmc_nuts_ws_bytes(int64_t C, int32_t n, int32_t max_depth);
+int finrom_hmc_nuts_begin(const finrom_hmc_state* st, const finrom_hmc_nuts_tree* tr, const double* A, const double* theta0, int32_t P,
+                          double* theta_out, void* stream);
+int finrom_hmc_nuts_leaf(const finrom_hmc_state* st, const finrom_hmc_nuts_tree* tr, const double* grad, const double* g_theta,
+                         const double* A, const double* theta0, int32_t P, double* theta_out, void* stream);
+int finrom_hmc_nuts_end(const finrom_hmc_state* st, const finrom_hmc_nuts_tree* tr, void* stream);
 
 /* ---- Laplace-preconditioned HMC: a low-rank metric at the MAP point ------------------------------------------------------------- *
  * The reference's working sampler builds a low-rank Gauss-Newton Hessian of the misfit at the MAP point in prior-whitened
