@@ -277,7 +277,7 @@ FOM_PATHS = {0: "none", 1: "small_lds", 2: "small_global", 3: "interpreter", 4: 
 # finrom_rom_last_form codes (include/finrom.h)
 ROM_FORMS = {0: "none", 1: "full", 2: "half"}
 # finrom_rom_last_epilogue codes (include/finrom.h)
-ROM_EPILOGUES = {0: "none", 1: "standard", 2: "roomy", 3: "roomy-short-waits"}
+ROM_EPILOGUES = {0: "none", 1: "standard", 2: "roomy", 3: "roomy-short-waits", 4: "roomy-block-row"}
 
 _lib = None
 

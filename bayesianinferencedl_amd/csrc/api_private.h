@@ -48,6 +48,14 @@ struct finrom_rom_s {
   // stream.  Read at creation: FINROM_PROJ_FIXED_WAITS=1 never (A/B), FINROM_PROJ_SHORT_WAITS=1 at every batch size (tests)
   bool fixed_waits = getenv("FINROM_PROJ_FIXED_WAITS") != nullptr, short_waits_always = getenv("FINROM_PROJ_SHORT_WAITS") != nullptr;
   bool short_waits(bool sweep_masked) const { return !fixed_waits && (short_waits_always || sweep_masked); }
+  // the short-waits epilogue that eliminates each block row in place instead of forming U_kk^-T: where the
+  // default takes the short waits, at the basis widths (d.NB) where it measured faster -- a handle under either switch above keeps
+  // its form.  Read at creation: FINROM_PROJ_BLOCK_ROW=1 at every batch size and width (tests), FINROM_PROJ_NO_BLOCK_ROW=1 never (A/B)
+  bool block_row_always = getenv("FINROM_PROJ_BLOCK_ROW") != nullptr, no_block_row = getenv("FINROM_PROJ_NO_BLOCK_ROW") != nullptr;
+  bool block_row(bool masked_by_default) const {      // (the batches finrom_solve_pairs masks the sweep for unless told otherwise)
+    if (no_block_row) return false;
+    return block_row_always || (!fixed_waits && !short_waits_always && masked_by_default && ((ROM_BLOCK_ROW_NB_MASK >> d.NB) & 1));
+  }
   hipStream_t side = nullptr;          // library-owned stream for the ROM half of finrom_solve_pairs / the error model of finrom_romml_grad
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // the FOM half of finrom_solve_pairs on a stream restricted to a SUBSET of the CUs (hipExtStreamCreateWithCUMask): the sweep's

@@ -303,11 +303,14 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
 // A_r, B_r (or, with factor > 0, the factor / the solution) by the form of the reduced operator the handle is set to
 // (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
-                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false, bool short_waits = false) {
+                       double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false, bool short_waits = false,
+                       bool block_row = false) {
   h->last_form = FINROM_ROM_FORM_FULL;
   roomy = roomy && h->projection == FINROM_PROJECTION_DIRECT && rom_roomy_applies(h->d, factor, w_r, qoi_r);
-  short_waits = roomy && short_waits;
-  h->last_epilogue = !roomy ? FINROM_ROM_EPILOGUE_STANDARD : short_waits ? FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS : FINROM_ROM_EPILOGUE_ROOMY;
+  block_row = roomy && block_row;
+  short_waits = roomy && (short_waits || block_row);      // (the block-row elimination is a form of the short-waits epilogue)
+  h->last_epilogue = !roomy ? FINROM_ROM_EPILOGUE_STANDARD : block_row ? FINROM_ROM_EPILOGUE_ROOMY_BLOCK_ROW :
+                     short_waits ? FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS : FINROM_ROM_EPILOGUE_ROOMY;
   if (h->projection == FINROM_PROJECTION_GRAM)
     return launch_rom_gram(h->d, h->gram, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r);
   RomDev d = h->d;
@@ -318,7 +321,7 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
     d.ext = (double*)h->ext.p;
     if (d.nkg_m > 0) h->last_form = FINROM_ROM_FORM_HALF;
   }
-  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy, short_waits);
+  return launch_rom_proj(d, theta, S, (double*)h->Ar.p, (double*)h->Br.p, factor, info, st, w_r, qoi_r, roomy, short_waits, block_row);
 }
 
 // the workspace bound of one piece of a batch (the packed A_r and B_r of its samples): 16 GiB; FINROM_ROM_WORKSPACE_BYTES=<n>, read
@@ -336,9 +339,10 @@ static int64_t rom_piece_samples(size_t per_sample) {
 
 // roomy: finrom_solve_pairs beside the FOM's half sweep -- QoI-only calls at r <= 80 then take the 256-register one-wave kernel at
 // every batch size (rom_roomy_applies); finrom_rom_solve itself never does.  short_waits: that kernel's form without the fixed waits
-// between accumulate-chained MFMAs (finrom_rom_s::short_waits says where)
+// between accumulate-chained MFMAs (finrom_rom_s::short_waits says where).  block_row: the short-waits form that eliminates each block
+// row in place instead of forming U_kk^-T (finrom_rom_s::block_row says where)
 static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
-                          double* B_r, int32_t* info, void* stream, bool roomy, bool short_waits = false) {
+                          double* B_r, int32_t* info, void* stream, bool roomy, bool short_waits = false, bool block_row = false) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!theta || (!qoi_r && h->d.n_obs > 0)))) { set_error("rom_solve: bad argument"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
@@ -375,7 +379,7 @@ static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
         qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
-                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm, short_waits))) return rc;
+                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm, short_waits, block_row))) return rc;
     if (factor >= 2) continue;
     int factored = factor;
     if (want_factor && d.NB > 6) {                                     // wider bases: blocked MFMA Cholesky kernel
@@ -577,9 +581,11 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // projection's time, and the projection loses least.  Headline, step in ms: unmasked 19.48, one CU per engine 19.06, two 19.20,
   // three 19.32 (the full plan with three: 20.11-20.15).
   const bool half_plan = &fband == &fom->band_m;
-  if (fom_cus < 0)
-    fom_cus = (rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !no_band &&
-               w == nullptr && S >= 16384) ? (half_plan ? -1 : -3) : 0;
+  // (what the default is, whatever FINROM_FOM_CUS, the caller's stream or the overlap switch then make of it: the block-row epilogue
+  // below follows THIS, because it returns other bits than the kernels beside it and a call's bits must not depend on the mask)
+  const bool mask_by_default = rom->projection == FINROM_PROJECTION_DIRECT && rom->d.NB <= 5 && fom->band.on && fom->band.NSP <= 14 && !no_band &&
+                               w == nullptr && S >= 16384;
+  if (fom_cus < 0) fom_cus = mask_by_default ? (half_plan ? -1 : -3) : 0;
   hipStream_t fst = st;
   if (overlap && fom_cus != 0) {
     if ((rc = rom->ensure_fom_side(fom_cus))) return rc;
@@ -621,8 +627,11 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // WHICH of its two forms runs does depend on the mask: the epilogue drops the fixed waits between accumulate-chained MFMAs (same
   // bits) only beside a sweep on its masked stream, for the reason the pivot records below have: a batch too small for
   // the mask is bounded from BELOW by the benchmark's contract (0.662 ms at 4096 samples; with the short waits the step measured
-  // 0.660 and 0.678 ms there, with the fixed ones 0.69).
-  if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy, rom->short_waits(fst != st))))
+  // 0.660 and 0.678 ms there, with the fixed ones 0.69).  The batches whose sweep is masked BY DEFAULT eliminate their block rows in
+  // place (round 15: no U_kk^-T; qoi_r differs at rounding level) at the basis widths where that measured faster -- also where
+  // FINROM_FOM_CUS, a blocking stream or the overlap switch then keep the mask away: same bits wherever the kernels run.
+  if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy, rom->short_waits(fst != st),
+                           rom->block_row(mask_by_default))))
     return fail(rc);
   // With a masked FOM stream only the SWEEP runs on it: pack + assembly go to an unmasked stream (they take 0.1 ms there against
   // 2.0 ms on 96 CUs beside the projection's start, and since the grouped projection loop the FOM half is the one that ends
@@ -640,7 +649,8 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   join();
   // a roomy call returns a sample that either half flagged as NaN in qoi_r and err (launch_sub_flagged); every other call keeps
   // what its kernels wrote
-  if ((rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY || rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS) && info != nullptr) {
+  if ((rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY || rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS ||
+       rom->last_epilogue == FINROM_ROM_EPILOGUE_ROOMY_BLOCK_ROW) && info != nullptr) {
     if ((rc = launch_sub_flagged(qoi, qoi_r, info, fom->d.n_obs, S * (int64_t)fom->d.n_obs, err, st))) return rc;
   } else if (err && (rc = launch_sub(qoi, qoi_r, S * (int64_t)fom->d.n_obs, err, st))) return rc;
   if (tracing) {

@@ -241,7 +241,8 @@ int launch_rom_grad(const RomDev& p, const double* Ar, const double* Br, int64_t
 int launch_rom_grad_contract(const RomDev& p, int64_t S, const RomGradArgs& ga, hipStream_t st);
 int launch_rom_chol_blocked(const RomDev& p, double* Ar, int64_t S, int* info, hipStream_t st);
 int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info, hipStream_t st,
-                    double* w_r = nullptr, double* qoi_r = nullptr, bool roomy = false, bool short_waits = false);
+                    double* w_r = nullptr, double* qoi_r = nullptr, bool roomy = false, bool short_waits = false, bool block_row = false);
+constexpr unsigned ROM_BLOCK_ROW_NB_MASK = 1u << 5;      // basis widths in 16-column blocks at which the block-row epilogue is the pair path's default
 bool rom_roomy_applies(const RomDev& p, int factor, const double* w_r, const double* qoi_r);
 constexpr int ROM_SPLITK_MAX_S = 64;      // batches up to this size take the split-K projection kernel (r = 49..96)
 // (r mod 16 in 1..8, NB >= 7: the HalfCover form of the multi-wave kernels, rom_proj_half.hip)
@@ -260,7 +261,7 @@ int launch_rom_grad_contract_small(const RomDev& p, int64_t S, const RomGradArgs
 int launch_rom_proj_splitk(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
                            hipStream_t st, double* w_r, double* qoi_r, const RomGradArgs& ga);
 int launch_rom_proj_single(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                           hipStream_t st, double* w_r, double* qoi_r, bool roomy = false, bool short_waits = false);
+                           hipStream_t st, double* w_r, double* qoi_r, bool roomy = false, bool short_waits = false, bool block_row = false);
 int launch_rom_solve(const RomDev& p, const double* Ar, const double* Br, int64_t S, double* w_r,
                      double* qoi_r, double* Ar_out, double* Br_out, int* info, int factored, hipStream_t st);
 

@@ -145,7 +145,7 @@ bool rom_roomy_applies(const RomDev& p, int factor, const double* w_r, const dou
 }
 
 int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                    hipStream_t st, double* w_r, double* qoi_r, bool roomy, bool short_waits) {
+                    hipStream_t st, double* w_r, double* qoi_r, bool roomy, bool short_waits, bool block_row) {
   // factor: 0 = write A_r, 1 = write its Cholesky factor (NB <= 6), 2 = also solve and write only w_r / qoi_r (NB <= 5)
   if (S == 0) return 0;
   ScopedKernelTimer t(K_ROM_PROJ, st);
@@ -162,7 +162,7 @@ int launch_rom_proj(const RomDev& p, const double* theta, int64_t S, double* Ar,
   if (p.NB >= 7 && p.r <= 16 * p.NB - 8 && !no_half) return launch_rom_proj_half(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r);
   switch (p.NB) {
     case 1: case 2: case 3: case 4: case 5:      // own translation unit (-O2)
-      return launch_rom_proj_single(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r, roomy, short_waits);
+      return launch_rom_proj_single(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r, roomy, short_waits, block_row);
     FR_CASE(6, 1)      // (r = 81..96 through the four-wave kernel with the fused solve: 28.6 vs 27.2 ms per 100k -- 21 tiles do not split evenly)
     FR_CASE(7, 4) FR_CASE(8, 4) FR_CASE(9, 4)
     case 10: case 11: case 12: case 13: return launch_rom_proj_wide(p, theta, S, Ar, Br, factor, info, st, w_r, qoi_r);

@@ -767,6 +767,43 @@ __device__ __forceinline__ d4 diag_tile_inverse(d4& D, int q, int c, int lane, i
 }
 
 // ---------------------------------------------------------------------------------------
+// The scalar step of diag_tile_inverse<true> on its own (round 15, fused_solve_sw<NB, true, true, true>): Db = register b of the
+// diagonal tile as it stands after the eliminations of blocks 0 .. b - 1.  The 4 x 4 block S = Db[:, 4 b .. 4 b + 3] goes through the
+// wave's LDS area sl[0 .. 32) exactly as there -- same exchange, same arithmetic, same pivot tests -- and the routine returns the
+// A operand AI (lane (q, c < 4) = Ib[q][c], Ib = R^-1, S = R^T R).  What the caller does with AI is the difference: it scales and
+// eliminates the WHOLE block row with it, so M = U^-T is never formed.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ double block4_inverse_operand(double Db, int b, int q, int c, int& bad, double* __restrict__ sl) {
+  if ((c >> 2) == b) sl[4 * q + (c & 3)] = Db;      // lane (q, 4 b + j): S[q][j]
+  lds_wave_order();
+  const double s00 = sl[0], s01 = sl[1], s02 = sl[2], s03 = sl[3], s11 = sl[5], s12 = sl[6], s13 = sl[7], s22 = sl[10], s23 = sl[11], s33 = sl[15];
+  auto rsqrt2 = [&](double p_) {                    // (diag_tile_inverse: the estimate and one third-order step)
+    bad |= !(p_ > 0.0);
+    const double r0 = __builtin_amdgcn_rsq(p_);
+    const double e = fma(-p_ * r0, r0, 1.0);
+    return fma(r0 * e, fma(0.375, e, 0.5), r0);
+  };
+  const double i00 = rsqrt2(s00);
+  const double r01 = s01 * i00, r02 = s02 * i00, r03 = s03 * i00;
+  const double i11 = rsqrt2(fma(-r01, r01, s11));
+  const double r12 = fma(-r01, r02, s12) * i11, r13 = fma(-r01, r03, s13) * i11;
+  const double i22 = rsqrt2(fma(-r12, r12, fma(-r02, r02, s22)));
+  const double r23 = fma(-r12, r13, fma(-r02, r03, s23)) * i22;
+  const double i33 = rsqrt2(fma(-r23, r23, fma(-r13, r13, fma(-r03, r03, s33))));
+  const double i01 = -(r01 * i11) * i00, i12 = -(r12 * i22) * i11, i23 = -(r23 * i33) * i22;
+  const double i02 = -fma(r01, i12, r02 * i22) * i00, i13 = -fma(r12, i23, r13 * i33) * i11;
+  const double i03 = -fma(r01, i13, fma(r02, i23, r03 * i33)) * i00;
+  double* __restrict__ tb = sl + 16;                // (every lane stores the same value; the entries below the diagonal are never read)
+  tb[0] = i00; tb[1] = i01; tb[2] = i02; tb[3] = i03; tb[5] = i11; tb[6] = i12; tb[7] = i13; tb[10] = i22; tb[11] = i23; tb[15] = i33;
+  lds_wave_order();
+  const bool mine = c < 4 && q <= c;
+  const double t_ = tb[mine ? 4 * q + c : 0];
+  const double AI = mine ? t_ : 0.0;
+  lds_wave_order();                                 // (the next block's writes stay behind these reads)
+  return AI;
+}
+
+// ---------------------------------------------------------------------------------------
 // Factorisation + reduced QoI for the multi-wave kernels WITHOUT leaving the registers (factor == 3: only qoi_r is wanted).
 // The block triangle of A_r stays where the main loop accumulated it -- tile idx in wave idx % NW -- and LDS only carries what
 // one block row hands to the others.  Right-looking by block rows kb:
@@ -940,7 +977,13 @@ constexpr int ROM_SW_MFMA_DIAG_TILES = 6;      // block rows with at most this m
 // touches an in-flight accumulator before the next wait is the next MFMA, taking it whole as C.  Nothing in the source enforces
 // that, and a passing test is no evidence for an inline-asm hazard: after a compiler upgrade, or a change that moves the register
 // pressure of this function, read the epilogue in the .s of rom_proj_roomy_sw_kernel<1..5> again (and check: no scratch).
-template <int NB, bool RM = false, bool SW = false>
+// BR (round 15, with RM and SW): steps (a) and (b) as ONE elimination of the block row [A_kk | A(kb, kb + 1 ..) | G_kb] in place.  For
+// each 4 x 4 block b of the diagonal tile the scalar step gives Ib = R^-1 (block4_inverse_operand), then one MFMA per tile scales
+// block row b -- X = Ib^T T[b], which is final -- and, for b < 3, one MFMA per tile eliminates the rows below it, T -= A^T X with the
+// diagonal tile's own A operand (-U[b, :] masked to the columns behind the block).  Seven MFMAs per tile and no M = U_kk^-T: the
+// block forward substitutions, the products with Ib and the four-MFMA transpose of diag_tile_inverse have no counterpart.  Every
+// result here is read as an operand by the next round, so every round keeps the fixed wait behind it.
+template <int NB, bool RM = false, bool SW = false, bool BR = false>
 __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (NB + 1) / 2], const double (&bacc)[NB], int q, int c,
                                               double* __restrict__ mt, double& qout) {
   // The extra column is formed LEFT-looking -- G_kb -= sum_{j < kb} U(j, kb)^T Z_j when block row kb is reached -- so that at most
@@ -961,6 +1004,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       if (q + 4 * g == c && 16 * t + c >= p.r) acc[tidx<NB>(t, t)][g] = 1.0;
   int bad = 0;
   static_assert(!SW || RM, "the short waits belong to the roomy variant");
+  static_assert(!BR || (SW && ROM_ROOMY_LDS_DIAG), "the block-row elimination belongs to the short-waits variant and factors through LDS");
   sfor<0, NB>([&](auto kc) {
     constexpr int kb = decltype(kc)::value;
     // G_kb = [B_r | (B_obs Phi)^T | 0] rows of this block: column 0 = B_r, columns 1 .. n_obs = rows of B_obs Phi
@@ -998,7 +1042,48 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
     // (RM, the roomy variant beside the FOM's half sweep: 256 registers, every block row factors its diagonal tile this way and
     //  the shuffle steps are not instantiated)
     constexpr bool kMfmaDiag = RM || (NB - kb) * (NB - kb + 1) / 2 <= ROM_SW_MFMA_DIAG_TILES;
-    if constexpr (kMfmaDiag) {
+    if constexpr (BR) {
+      // (a) and (b) in one: the block row eliminated in place, 4 x 4 block by 4 x 4 block.  Tile 0 of a round is the diagonal one, so
+      // that its result is the first to be complete; tiles 1 .. NP are the row's other tiles, the extra column last.
+      constexpr int NP = NB - kb;
+      double* __restrict__ sl = mt + ROM_SW_LDS;
+      d4 D[1] = {acc[tidx<NB>(kb, kb)]};
+      sfor<0, 4>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        const double AI = block4_inverse_operand(D[0][b], b, q, c, bad, sl);
+        if constexpr (kb > 0 && b == 0) mfma_drain(e);      // (the extra column's chain: its one wait, behind the first scalar step)
+        // scaling: X = Ib^T T[b] onto a zero accumulator; register 0 of X is block row b of the finished tile
+        d4 X[NP + 1];
+        asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, 0" : "=&v"(X[0]) : "v"(AI), "v"((double)D[0][b]));
+#pragma unroll
+        for (int t = 0; t < NP; ++t) {
+          const double tb = t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)][b] : e[0][b];
+          asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, 0" : "=&v"(X[1 + t]) : "v"(AI), "v"(tb));
+        }
+        mfma_drain(X);
+        const double Ub = c >= 4 * b ? X[0][0] : 0.0;         // block row b of U_kk (columns left of the block are not part of U)
+#pragma unroll
+        for (int t = 0; t < NP; ++t) (t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)] : e[0])[b] = X[1 + t][0];
+        if constexpr (b < 3) {
+          // elimination: rows behind the block, T -= U[b, rows]^T X, the diagonal tile's A operand for every tile (rows up to 4 b + 3
+          // meet zeros and keep their values); the operand X stays in its own register, outside the tuple the MFMA writes
+          const double A = c >= 4 * (b + 1) ? -Ub : 0.0;
+          asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(D[0]) : "v"(A), "v"(Ub));
+#pragma unroll
+          for (int t = 0; t < NP; ++t) {
+            const double xb = X[1 + t][0];
+            asm volatile("s_nop 3\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0"
+                         : "+v"(t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)] : e[0]) : "v"(A), "v"(xb));
+          }
+          // (one wait for the round; only the tiles it wrote are named)
+          asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(D[0]));
+#pragma unroll
+          for (int t = 0; t < NP; ++t) asm volatile("" : "+v"(t + 1 < NP ? acc[tidx<NB>(kb, t + 1 < NP ? kb + 1 + t : kb)] : e[0]));
+        }
+      });
+      asm volatile("" : "+v"(bad));                          // (the pivot tests are settled here, as below)
+      z[kb] = e[0];
+    } else if constexpr (kMfmaDiag) {
       // Round 4: the diagonal tile 4 x 4-blocked on the matrix cores (diag_tile_inverse, as the other two epilogues since round 3)
       // instead of the 16 shuffle steps below.  It returns M in the C/D layout; the A operand of M T is M^T in that layout --
       // and a tile in the C/D layout IS a valid A operand holding its own transpose (A[i = c][k = q] <- X[q + 4 g][c]), so
@@ -1045,7 +1130,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
           }
         }
     }
-    if constexpr (kb > 0) mfma_drain(e);
+    if constexpr (kb > 0 && !BR) mfma_drain(e);
     // (b) one tile at a time (the standard variant): four dependent MFMAs with a fixed wait behind each
     auto solve_tile = [&](d4& T) {
       double b[4];
@@ -1059,7 +1144,9 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
       }
       T = n[0];
     };
-    if constexpr (RM) {
+    if constexpr (BR) {
+      // (done above)
+    } else if constexpr (RM) {
       // the roomy variant has the registers for all results of the block row at once: the four-MFMA chains of its NB - kb
       // independent tiles (the extra column last) run interleaved, ONE wait per round instead of one per MFMA; every product and
       // every sum keeps its place in its own chain, so the bits are those of solve_tile.  (SW: the rounds follow each other
@@ -1123,7 +1210,7 @@ __device__ __forceinline__ int fused_solve_sw(const RomDev& p, d4 (&acc)[NB * (N
   return bad;
 }
 
-template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false, bool RM = false, bool SW = false>
+template <int NB, int NW, int W, bool SK = false, bool GR = false, bool HF = false, bool RM = false, bool SW = false, bool BR = false>
 __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw, int64_t s, int lane,
                                               double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                               int* __restrict__ info, double* __restrict__ w_r = nullptr,
@@ -1251,7 +1338,7 @@ __device__ __forceinline__ void rom_proj_body(const RomDev& p, const double* thw
     if constexpr (NW == 1 && NB <= 5 && !SK) {
       if (qoi_only) {
         double qv;
-        bad = fused_solve_sw<NB, RM, SW>(p, acc, bacc, q, c, mt_lds, qv);
+        bad = fused_solve_sw<NB, RM, SW, BR>(p, acc, bacc, q, c, mt_lds, qv);
         if (bad && info != nullptr && lane == 0) atomicOr(&info[s], 2);
         if (lane >= 1 && lane <= p.n_obs) qoi_r[s * p.n_obs + lane - 1] = bad ? __builtin_nan("") : qv;
         return;
@@ -1361,7 +1448,7 @@ __device__ __forceinline__ void rom_proj_entry_splitk(RomDev p, const double* __
 
 // NW waves share one sample (each owns every NW-th tile of the upper block triangle); a
 // workgroup is max(4, NW) waves = max(4, NW)/NW samples.
-template <int NB, int NW, bool GR = false, bool HF = false, bool RM = false, bool SW = false>
+template <int NB, int NW, bool GR = false, bool HF = false, bool RM = false, bool SW = false, bool BR = false>
 __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restrict__ theta, int64_t S,
                                                        double* __restrict__ Ar, double* __restrict__ Br, int factor,
                                                        int* __restrict__ info, double* __restrict__ w_r, double* __restrict__ qoi_r,
@@ -1407,7 +1494,7 @@ __device__ __forceinline__ void rom_proj_entry(RomDev p, const double* __restric
         }
       }
     }
-    rom_proj_body<NB, 1, 0, false, GR, false, RM, SW>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
+    rom_proj_body<NB, 1, 0, false, GR, false, RM, SW, BR>(p, thw, s, lane, Ar, Br, factor, info, w_r, qoi_r, nullptr, theta_s,
                                        half ? kpat + __builtin_amdgcn_readfirstlane(half == 2 ? p.kmg_s : p.kmg_m) : kpat, 0, 1, nullptr,
                                        NB <= 5 ? mt_sw + wave * rom_sw_lds<RM>() : nullptr, ext_s, half);
   } else if constexpr (NW == 4) {

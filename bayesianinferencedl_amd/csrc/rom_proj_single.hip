@@ -40,6 +40,17 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(128))) void 
   rom_proj_entry<NB, 1, true, false, true, true>(p, theta, S, nullptr, nullptr, 2, info, nullptr, qoi_r, kpat);
 }
 
+// The short-waits variant with the block-row elimination (round 15; fused_solve_sw<NB, true, true, true>): each block row
+// [A_kk | A(kb, kb + 1 ..) | G_kb] is scaled and eliminated in place by the 4 x 4 block steps that factor its diagonal tile, so
+// U_kk^-T is never formed.  Rounding-level differences in qoi_r against the two kernels above; finrom_rom_s::block_row says where
+// finrom_solve_pairs launches it.
+template <int NB>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(128))) void rom_proj_roomy_br_kernel(RomDev p, const double* __restrict__ theta, int64_t S,
+                                                                 int* __restrict__ info, double* __restrict__ qoi_r,
+                                                                 const int* __restrict__ kpat) {
+  rom_proj_entry<NB, 1, true, false, true, true, true>(p, theta, S, nullptr, nullptr, 2, info, nullptr, qoi_r, kpat);
+}
+
 // the samples' scalars for the grouped main loop (RomDev::ext_def): ext[s][l] = (theta'[a_l] / theta'[b_l]) ^ (1 + (f_l & 1)), theta'[0] = 1,
 // times an exact 2 where f_l & 2 (the half list of a mirror-symmetric ROM: the left rows count twice)
 __global__ __launch_bounds__(256) void rom_ext_kernel(const double* __restrict__ theta, int P, int64_t S, const int* __restrict__ def,
@@ -94,13 +105,19 @@ int launch_rom_proj_splitk(const RomDev& p, const double* theta, int64_t S, doub
 }
 
 int launch_rom_proj_single(const RomDev& p, const double* theta, int64_t S, double* Ar, double* Br, int factor, int* info,
-                           hipStream_t st, double* w_r, double* qoi_r, bool roomy, bool short_waits) {
+                           hipStream_t st, double* w_r, double* qoi_r, bool roomy, bool short_waits, bool block_row) {
   const dim3 grid((unsigned)((S + 3) / 4)), block(256);
   if (roomy && !(factor == 2 && w_r == nullptr && qoi_r != nullptr && p.n_obs <= 15)) { set_error("rom_proj_single: the roomy kernel is QoI-only"); return FINROM_ERR_ARG; }
   if (p.ext != nullptr)
     hipLaunchKernelGGL(rom_ext_kernel, dim3((unsigned)((S * p.n_ext + 255) / 256)), dim3(256), 0, st, theta, p.P, S, p.ext_def, p.n_ext, p.ext);
   const int* kp = p.ext != nullptr ? p.kmg : p.kmeta;
-  if (roomy && short_waits) switch (p.NB) {
+  if (roomy && short_waits && block_row) switch (p.NB) {
+#define FR_ONE(N) case N: hipLaunchKernelGGL(rom_proj_roomy_br_kernel<N>, grid, block, 0, st, p, theta, S, info, qoi_r, kp); break;
+    FR_ONE(1) FR_ONE(2) FR_ONE(3) FR_ONE(4) FR_ONE(5)
+#undef FR_ONE
+    default: set_error("rom_proj_single: basis size > 80"); return FINROM_ERR_UNSUPPORTED;
+  }
+  else if (roomy && short_waits) switch (p.NB) {
 #define FR_ONE(N) case N: hipLaunchKernelGGL(rom_proj_roomy_sw_kernel<N>, grid, block, 0, st, p, theta, S, info, qoi_r, kp); break;
     FR_ONE(1) FR_ONE(2) FR_ONE(3) FR_ONE(4) FR_ONE(5)
 #undef FR_ONE

@@ -692,7 +692,9 @@ class RomEngine:
         """'roomy' when the most recent projection launch ran the 256-register one-wave kernel (the pair path beside the FOM's half
         sweep, QoI-only, r <= 80) with a fixed wait behind every round of its epilogue's dependent MFMAs, 'roomy-short-waits' when
         it ran that kernel's form without the waits between accumulate-chained MFMAs (same bits; the pair path beside a sweep on
-        its CU-masked stream, batches of 16 384 and more), 'standard' for every other kernel, 'none' before the first call
+        its CU-masked stream, batches of 16 384 and more), 'roomy-block-row' when it ran the short-waits form that eliminates each
+        block row in place instead of forming its diagonal tile's inverse (qoi_r differs at rounding level; there, at r = 65 .. 80),
+        'standard' for every other kernel, 'none' before the first call
         (finrom_rom_last_epilogue)."""
         rc = lib().finrom_rom_last_epilogue(self._h)
         if rc < 0:

@@ -467,11 +467,17 @@ int finrom_rom_last_form(finrom_rom_t h);
  * FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS = the roomy kernel whose epilogue waits only where an MFMA's result is read by something
  * other than the next MFMA's accumulator input -- same bits as FINROM_ROM_EPILOGUE_ROOMY, which keeps a fixed wait behind every
  * round of dependent MFMAs.  finrom_solve_pairs launches it where the FOM's sweep runs on its CU-masked stream (large batches);
- * when the handle is created, FINROM_PROJ_FIXED_WAITS=1 says never and FINROM_PROJ_SHORT_WAITS=1 at every batch size. */
+ * when the handle is created, FINROM_PROJ_FIXED_WAITS=1 says never and FINROM_PROJ_SHORT_WAITS=1 at every batch size.
+ * FINROM_ROM_EPILOGUE_ROOMY_BLOCK_ROW = the short-waits kernel that scales and eliminates each block row in place with the 4 x 4
+ * block steps of its diagonal tile instead of forming that tile's inverse: qoi_r differs from the other two at rounding level, no
+ * less accurate.  finrom_solve_pairs launches it for the batches whose sweep it masks by default (whatever then overrides the mask:
+ * a call's bits do not depend on where its kernels run), at r in 65 .. 80, on a handle created under neither switch above; FINROM_PROJ_BLOCK_ROW=1 at creation says at every batch size and r <= 80,
+ * FINROM_PROJ_NO_BLOCK_ROW=1 never. */
 #define FINROM_ROM_EPILOGUE_NONE 0
 #define FINROM_ROM_EPILOGUE_STANDARD 1
 #define FINROM_ROM_EPILOGUE_ROOMY 2
 #define FINROM_ROM_EPILOGUE_ROOMY_SHORT_WAITS 3
+#define FINROM_ROM_EPILOGUE_ROOMY_BLOCK_ROW 4
 int finrom_rom_last_epilogue(finrom_rom_t h);
 /* theta [S x P] -> w_r [S x r] (NULL to skip), qoi_r [S x n_obs], info [S] (NULL ok);
  * optional A_r [S x r x r] and B_r [S x r] (the state the reference keeps in
