@@ -94,6 +94,11 @@ class HmcNutsTree(C.Structure):
                 ("state_loss", C.c_void_p), ("tree", C.c_void_p), ("accept_stat", C.c_void_p), ("active", C.c_void_p)]
 
 
+class HmcStepAdapt(C.Structure):
+    _fields_ = [("eps", C.c_void_p), ("hbar", C.c_void_p), ("xbar", C.c_void_p), ("mu", C.c_double), ("target", C.c_double),
+                ("gamma", C.c_double), ("t0", C.c_double), ("tune", C.c_int64)]
+
+
 class HmcStats(C.Structure):
     _fields_ = [("C", C.c_int64), ("n", C.c_int32), ("proposal0", C.c_int64), ("burn", C.c_int64), ("batch", C.c_int64),
                 ("pt", C.c_void_p), ("accept", C.c_void_p), ("cand", C.c_void_p), ("cand_loss", C.c_void_p),
@@ -241,6 +246,16 @@ SIGNATURES = {
     "finrom_hmc_end_metric": (C.c_int, [C.POINTER(HmcState), C.c_void_p, C.c_int32, C.c_void_p]),
     "finrom_hmc_nuts_ml_metric": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_ml_adapt": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_ml_metric_adapt": (C.c_int, [C.c_void_p, C.POINTER(HmcState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_begin_adapt": (C.c_int, [C.POINTER(HmcState), C.POINTER(HmcNutsTree), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_nuts_leaf_adapt": (C.c_int, [C.POINTER(HmcState), C.POINTER(HmcNutsTree), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "finrom_hmc_step_adapt_update": (C.c_int, [C.POINTER(HmcStepAdapt), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     "finrom_hmc_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "finrom_hmc_stats_update": (C.c_int, [C.POINTER(HmcStats), C.c_void_p]),
     "finrom_hmc_end_stage1": (C.c_int, [C.POINTER(HmcState), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -72,7 +72,7 @@ the i.i.d. chain of that network with mean 0 and tau 1.  With an ml_form nothing
 
 `nuts=Nuts(max_depth)` (nuts.py): the No-U-turn sampler the reference runs (bayesian_inference/inference.py:165-166 `pm.NUTS(scaling=G_INV,
 max_treedepth=7, target_accept=0.98)`) in the place of the fixed-length trajectory and its Metropolis test: multinomial NUTS with the
-generalised U-turn criterion, identity mass, eps the caller's (no adaptation).  A call makes (n_evals - 1) // n_leapfrog transitions,
+generalised U-turn criterion, identity mass, eps the caller's (or adapted: `adapt=` below).  A call makes (n_evals - 1) // n_leapfrog transitions,
 the draws the same call makes without nuts=.  run_chains: nuts.transition_iterative over any callable, chain by chain.  Device
 functions, two library forms (fused=False is refused).  model="ml": a transition is ONE finrom_hmc_nuts_ml call (the tree's kernel, one
 1024-thread workgroup per chain, and the counters' advance behind it: csrc/hmc_nuts.hip); it implies the library form (ml_form None or
@@ -87,7 +87,7 @@ a round too (_run_nuts_rounds), so a run continued with proposal0= is the uninte
 and nuts_readbacks.  Nuts(metric=) is refused with these three models.  Either form needs rng="philox" (momenta as before, the tree's direction bits and
 uniforms from counter words 3 and 4, philox.nuts_top / nuts_leaf).  The result gains tree [proposals, C, 4] int32 (depth, leapfrog
 steps, stop reason: 0 depth limit, 1 tree turned, 2 sub-tree turned, 3 diverged; moved) and accept_stat [proposals, C], the mean of
-min(1, exp(H0 - H)) over the leaves: what dual averaging would consume.  accept counts the transitions whose draw is not the point
+min(1, exp(H0 - H)) over the leaves: what dual averaging consumes.  accept counts the transitions whose draw is not the point
 they started from.  Not with metric=, correct= or record=.
 `Nuts(max_depth, metric=LowRankMetric)`: the transition under the Laplace metric -- the reference's `scaling`, on the sampler object as
 it is there (the metric= keyword beside nuts= stays refused) -- in the chain's own coordinates: under prior= the whitened ones
@@ -95,6 +95,16 @@ it is there (the metric= keyword beside nuts= stays refused) -- in the chain's o
 normals, the position moves by eps M^-1 p, the kinetic energy is p . M^-1 p / 2 and the U-turn criterion takes M^-1 p (nuts.py).  On the
 device a transition is ONE finrom_hmc_nuts_ml_metric call with metric.device(); a metric of rank zero or None is the call above, bit
 for bit.  A metric whose n is not the chains' is refused with both numbers.  The result gains metric_rho.
+`Nuts(max_depth, adapt=StepAdapt(target_accept, tune))`: the dual-averaging warm-up of the step size (nuts.StepAdapt; Hoffman & Gelman
+2014, Algorithm 5), the reference's `tune=100, target_accept=0.98`.  Every chain adapts its OWN step on its own accept_stat: the
+transitions with global index < tune adapt, the later ones take exp(xbar); eps= is the starting point, mu = log(10 eps).  run_chains:
+StepAdapt.update behind each transition.  Device functions, all four models, both priors, with or without Nuts(metric=), graph and stream
+order: the transition's kernels read their chain's step from eps [C] on the device (finrom_hmc_nuts_ml_adapt / _ml_metric_adapt;
+finrom_hmc_nuts_begin_adapt / _leaf_adapt) and ONE finrom_hmc_step_adapt_update launch follows the transition (inside the captured
+transition; in the leaf-per-round form inside the `end` graph), which reads its row from the device's counter.  The result gains
+step_size [proposals, C], the step each transition took, and adapt, the started StepAdapt at the end; StepAdapt(resume=res.adapt) with
+proposal0=res.adapt.next continues the recursion.  stats= with a burn < tune is refused: the tuning draws are not draws of the target.
+adapt=None: every path, launch and byte as before.
 
 `correct=`: delayed acceptance (two-stage Metropolis, Christen & Fox 2005).  The trajectory runs under a surrogate -- model "romml",
 "rom" or "ml" -- and the full-order model decides: stage 1 is the Metropolis test the chains make anyway, under the surrogate's
@@ -353,6 +363,43 @@ class _DeviceStats:
         return h
 
 
+class _DeviceStepAdapt:
+    """Nuts(adapt=) on the device: the three [C] arrays of finrom_hmc_step_adapt and step_size [proposals, C] as torch tensors, started
+    from the host statement's state (nuts.StepAdapt.begin: the caller's eps, or resume's); pt: the chain state's counter,
+    accept_stat [proposals, C]: what the transitions write."""
+
+    def __init__(self, spec, eps0, Cn, proposal0, n_prop, pt, accept_stat):
+        import torch
+        from .. import _ffi
+        self._ffi, self._L, self.C, self.proposal0, self.n_prop, self.pt, self.accept_stat = _ffi, _ffi.lib(), Cn, proposal0, n_prop, pt, accept_stat
+        h = self.host = spec.begin(eps0, Cn, proposal0)
+        f64 = dict(dtype=torch.float64, device=pt.device)
+        self.eps, self.hbar, self.xbar = (torch.as_tensor(x, **f64).contiguous() for x in (h.eps, h.hbar, h.xbar))
+        self.step_size = torch.zeros(n_prop, Cn, **f64)
+        self.desc = _ffi.HmcStepAdapt(eps=self.eps.data_ptr(), hbar=self.hbar.data_ptr(), xbar=self.xbar.data_ptr(), mu=h.mu,
+                                      target=h.target_accept, gamma=h.GAMMA, t0=h.T0, tune=h.tune)
+
+    def buffers(self):
+        """Everything the launch writes: saved before a warm-up transition and restored after the capture, with the chain state."""
+        return [self.eps, self.hbar, self.xbar, self.step_size]
+
+    def update(self):
+        """One launch on torch's current stream, behind a transition and its counters' advance."""
+        import ctypes as C
+        import torch
+        self._ffi.check(self._L.finrom_hmc_step_adapt_update(C.byref(self.desc), self.C, self.proposal0, self.pt.data_ptr(),
+                                                             self.accept_stat.data_ptr(), self.step_size.data_ptr(),
+                                                             torch.cuda.current_stream().cuda_stream), "finrom_hmc_step_adapt_update")
+
+    def result(self, res):
+        """res gains step_size and adapt, the started host StepAdapt with the device's end state (synchronises)."""
+        h = self.host
+        h.eps, h.hbar, h.xbar = self.eps.cpu().numpy(), self.hbar.cpu().numpy(), self.xbar.cpu().numpy()
+        h.next = self.proposal0 + self.n_prop
+        res["step_size"], res["adapt"] = self.step_size.cpu().numpy(), h
+        return res
+
+
 class _DeviceDA:
     """The buffers of delayed acceptance (finrom_hmc_end_stage1 / _stage2, finrom_hmc_draw_stage2) as torch tensors on `dev`, and the
     full-order solve between the two stages: `fin`'s "field" engine, QoI only."""
@@ -528,7 +575,7 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
     ChainStats of this run or None; with a prior also V [C, n], the whitened final states; under correct= also accept1, correction,
     n_fom and stage [proposals, C] (0: stopped at stage 1, 1: stopped at stage 2, 2: accepted)); under nuts= also tree, accept_stat
     and margin (_run_chains_nuts)."""
-    _check_nuts(nuts, rng, metric, correct, record, "run_chains")
+    _check_nuts(nuts, rng, metric, correct, record, "run_chains", stats)
     seeds64 = _check_rng(rng, seeds, proposal0, "run_chains")
     if nuts is not None:
         _check_prior(prior, mean, "run_chains")
@@ -635,7 +682,7 @@ def run_chains(value_and_grad, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
                      trace=np.stack(trace) if keep_trace else None, stats=cs, **da)
 
 
-def _check_nuts(nuts, rng, metric, correct, record, who):
+def _check_nuts(nuts, rng, metric, correct, record, who, stats=None):
     """nuts=Nuts(max_depth): what the No-U-turn transition is refused beside, each with its reason."""
     if nuts is None:
         return
@@ -652,6 +699,11 @@ def _check_nuts(nuts, rng, metric, correct, record, who):
         raise ValueError(f"{who}: nuts= with correct=: delayed acceptance is a Metropolis test, the No-U-turn transition has none")
     if record is not None:
         raise ValueError(f"{who}: nuts= with record=: a tree's evaluations have no fixed indices to list")
+    adapt = getattr(nuts, "adapt", None)
+    if adapt is not None:                                            # (StepAdapt and Nuts refuse everything else where they are built)
+        if stats is not None and stats.burn < adapt.tune:
+            raise ValueError(f"{who}: Nuts(adapt=StepAdapt(tune={adapt.tune})) with ChainStats(burn={stats.burn}): the tuning draws are "
+                             f"not draws of the target (the step size still moves): pass a burn >= tune")
 
 
 def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigma, tau, mean, keep_trace, prior, proposal0, stats, nuts):
@@ -691,19 +743,26 @@ def _run_chains_nuts(value_and_grad, K0, n_evals, seeds64, eps, n_leapfrog, sigm
     accept = np.zeros(C, np.int64)
     tree, accept_stat, margin = np.zeros((n_prop, C, 4), np.int32), np.zeros((n_prop, C)), np.inf
     cs = None if stats is None else stats.begin(field(K), loss, proposal0, n_prop)
+    ad = None if getattr(nuts, "adapt", None) is None else nuts.adapt.begin(eps, C, proposal0)
+    step_size = np.zeros((n_prop, C))
     for q in range(n_prop):
         P = philox.draw_block(seeds64, proposal0 + q, 1, n)[0][0]
         for c in range(C):
-            r = N.transition_iterative(f, K[c], U[c], dU[c], loss[c], P[c], seed=seeds64[c], proposal=proposal0 + q, eps=eps, c_lik=c_lik,
+            eps_c = eps if ad is None else float(ad.eps[c])
+            r = N.transition_iterative(f, K[c], U[c], dU[c], loss[c], P[c], seed=seeds64[c], proposal=proposal0 + q, eps=eps_c, c_lik=c_lik,
                                        c_pri=c_pri, mean=mean[c], max_depth=nuts.max_depth, metric=metric)
             K[c], U[c], dU[c], loss[c] = r.k, r.U, r.dU, r.loss
-            tree[q, c], accept_stat[q, c], margin = r.tree, r.accept_stat, min(margin, r.margin)
+            tree[q, c], accept_stat[q, c], margin, step_size[q, c] = r.tree, r.accept_stat, min(margin, r.margin), eps_c
+        if ad is not None:
+            ad.update(accept_stat[q], proposal0 + q)
         accept += tree[q, :, 3]
         if cs is not None:
             cs.update(field(K), loss.copy(), tree[q, :, 3] != 0, proposal0 + q)
         if keep_trace:
             trace.append(np.array(field(K)))
     more = dict(tree=tree, accept_stat=accept_stat, margin=margin, nuts=nuts.max_depth, metric_rho=0 if metric is None else metric.rho)
+    if ad is not None:
+        more.update(step_size=step_size, adapt=ad)
     evals = 1 + (int(tree[:, :, 1].sum(axis=0).max()) if n_prop else 0)
     return HmcResult(K=field(K).copy(), **({} if prior is None else {"V": K}), accept=accept, proposals=n_prop, n_evals=evals, recorded=[],
                      trace=np.stack(trace) if keep_trace else None, stats=cs, **more)
@@ -846,7 +905,7 @@ class _DeviceChains:
         _check_model(a.model, a.solver_r, a.solver, a.data, who, a.surrogate)
         _check_correct(a.correct, a.stats, who, a.model)
         _check_ml_form(a.ml_form, a.model, who, a.fused)
-        _check_nuts(a.nuts, a.rng, a.metric, a.correct, a.record, who)
+        _check_nuts(a.nuts, a.rng, a.metric, a.correct, a.record, who, a.stats)
         if a.nuts is not None:                                       # two library forms: one launch per transition ("ml"), one leaf per launch
             if a.fused is not None and not a.fused:
                 raise ValueError(f"{who}: nuts= is a library form (finrom_hmc_nuts_ml; finrom_hmc_nuts_begin / _leaf / _end); fused=False "
@@ -1176,6 +1235,9 @@ def _run_nuts_rounds(a, ch, st, Kq0, loss, info):
     active, state_loss = torch.zeros(Cn, **i32), torch.zeros(Cn, **f64)
     tr = _ffi.HmcNutsTree(ws=ws.data_ptr(), seeds=seeds_t.data_ptr(), proposal0=a.proposal0, max_depth=depth, state_loss=state_loss.data_ptr(),
                           tree=tree.data_ptr(), accept_stat=accept_stat.data_ptr(), active=active.data_ptr())
+    ad = None                                                        # Nuts(adapt=): each chain's own step, the update behind `end`
+    if a.nuts.adapt is not None:
+        ad = _DeviceStepAdapt(a.nuts.adapt, a.eps, Cn, a.proposal0, ch.n_prop, ch.pt, accept_stat)
     grad = gth = A_t = th0 = theta = None                            # (a round holds, by name, every tensor it passes by address)
     P = 0
     if prior is not None:
@@ -1221,15 +1283,25 @@ def _run_nuts_rounds(a, ch, st, Kq0, loss, info):
     map_args = (ptr(A_t), ptr(th0), P, ptr(theta))
 
     def begin(state=st):
-        check(L.finrom_hmc_nuts_begin(C.byref(state), C.byref(tr), *map_args, stream()), "finrom_hmc_nuts_begin")
+        if ad is not None and state is st:                           # (the start point's round: the plain begin with eps = 0)
+            check(L.finrom_hmc_nuts_begin_adapt(C.byref(state), C.byref(tr), ad.eps.data_ptr(), *map_args, stream()),
+                  "finrom_hmc_nuts_begin_adapt")
+        else:
+            check(L.finrom_hmc_nuts_begin(C.byref(state), C.byref(tr), *map_args, stream()), "finrom_hmc_nuts_begin")
 
     def round_():
         info.zero_()
         evaluate()
-        check(L.finrom_hmc_nuts_leaf(C.byref(st), C.byref(tr), ptr(grad), ptr(gth), *map_args, stream()), "finrom_hmc_nuts_leaf")
+        if ad is not None:
+            check(L.finrom_hmc_nuts_leaf_adapt(C.byref(st), C.byref(tr), ad.eps.data_ptr(), ptr(grad), ptr(gth), *map_args, stream()),
+                  "finrom_hmc_nuts_leaf_adapt")
+        else:
+            check(L.finrom_hmc_nuts_leaf(C.byref(st), C.byref(tr), ptr(grad), ptr(gth), *map_args, stream()), "finrom_hmc_nuts_leaf")
 
     def end():
         check(L.finrom_hmc_nuts_end(C.byref(st), C.byref(tr), stream()), "finrom_hmc_nuts_end")
+        if ad is not None:
+            ad.update()
         if ch.ds is not None:                                        # (Kq[0] holds the draw: where it moved, the sums take it)
             ch.ds.update(field_of_draw(), state_loss)
 
@@ -1277,7 +1349,7 @@ def _run_nuts_rounds(a, ch, st, Kq0, loss, info):
     if np.any(res["tree"][:, :, 2] < 0):
         raise _ffi.FinromError(f"run_chains_fused: a chain was still active after 2^{depth} - 1 rounds (tree rows with reason -1)")
     res["n_evals"] = 1 + (int(res["tree"][:, :, 1].sum(axis=0).max()) if ch.n_prop else 0)
-    return res
+    return res if ad is None else ad.result(res)
 
 
 def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, sigma=0.05, tau=0.5, mean=None, record=None,
@@ -1347,9 +1419,21 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         tree = torch.zeros(ch.n_prop, Cn, 4, dtype=torch.int32, device=K.device)
         accept_stat = torch.zeros(ch.n_prop, Cn, **f64)
         nmh = ch.nuts_metric.device() if ch.nuts_metric is not None else None      # (a rank-zero or absent metric: the plain tree)
+        ad = None                                                    # Nuts(adapt=): each chain's own step, the update behind the tree
+        if nuts.adapt is not None:
+            ad = _DeviceStepAdapt(nuts.adapt, eps, Cn, proposal0, ch.n_prop, ch.pt, accept_stat)
 
     def transition(rec=False):
-        if nmh is not None:
+        if ad is not None:
+            tail = (seeds_t.data_ptr(), proposal0, nuts.max_depth, ch.data_t.data_ptr(), ch.per_sample, tree.data_ptr(),
+                    accept_stat.data_ptr(), stream())
+            if nmh is not None:
+                check(L.finrom_hmc_nuts_ml_metric_adapt(form.mlp._h, C.byref(st), nmh._h, ad.eps.data_ptr(), *tail),
+                      "finrom_hmc_nuts_ml_metric_adapt")
+            else:
+                check(L.finrom_hmc_nuts_ml_adapt(form.mlp._h, C.byref(st), ad.eps.data_ptr(), *tail), "finrom_hmc_nuts_ml_adapt")
+            ad.update()
+        elif nmh is not None:
             check(L.finrom_hmc_nuts_ml_metric(form.mlp._h, C.byref(st), nmh._h, seeds_t.data_ptr(), proposal0, nuts.max_depth,
                                               ch.data_t.data_ptr(), ch.per_sample, tree.data_ptr(), accept_stat.data_ptr(), stream()),
                   "finrom_hmc_nuts_ml_metric")
@@ -1397,14 +1481,14 @@ def run_chains_fused(solver_r, K0, n_evals, *, seeds, eps=2e-3, n_leapfrog=10, s
         da.start(F0, loss, ch.c_lik)
     ch.start_stats(F0, loss if da is None else da.loss_f)
     if nuts is not None:                                             # (loss is the state's misfit here: the warm-up moves it too)
-        g = ch.capture(transition, extra=[loss, Kq[0], tree, accept_stat])
+        g = ch.capture(transition, extra=[loss, Kq[0], tree, accept_stat] + (ad.buffers() if ad is not None else []))
         if g is not None and ch.trace is not None:
             ch.trace[1].zero_()
         res = ch.run(transition, g, fused=True, nuts=nuts.max_depth, metric_rho=0 if ch.nuts_metric is None else ch.nuts_metric.rho,
                      **({} if ml_form is None else {"ml_form": ml_form}))
         res["tree"], res["accept_stat"] = tree.cpu().numpy(), accept_stat.cpu().numpy()
         res["n_evals"] = 1 + (int(res["tree"][:, :, 1].sum(axis=0).max()) if ch.n_prop else 0)
-        return res
+        return res if ad is None else ad.result(res)
     g = ch.capture(proposal)
     if g is not None and ch.trace is not None:                       # (the warm-up's row; proposal 0 writes it again)
         ch.trace[1].zero_()

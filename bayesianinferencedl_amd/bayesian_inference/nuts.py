@@ -45,7 +45,11 @@ dE = (U' + dot(p', v') / 2) - H0; divergence, weight, streamed selection and rho
 U-TURNS, the generalised criterion with p# = M^-1 p (Betancourt 2017, A.4.2): a checkpoint stores (p, v, rho_sub), rho_s = (rho_sub -
 rho_ckpt) + p_ckpt; a sub-tree is turning when dot(rho_s, v_ckpt) <= 0 or dot(rho_s, v') <= 0, the tree when dot(rho, v_left) <= 0 or
 dot(rho, v_right) <= 0; `margin` takes these products relative to |rho| |v|.
-`dot_metric(V_j, x)` may be given like `dot`: the default is np.dot; the kernel's is one wave's (tests/nuts_metric_cases.py)."""
+`dot_metric(V_j, x)` may be given like `dot`: the default is np.dot; the kernel's is one wave's (tests/nuts_metric_cases.py).
+
+THE STEP SIZE (Nuts(max_depth, adapt=StepAdapt(target_accept, tune)), the reference's `tune` and `target_accept`): dual averaging on the
+accept_stat a transition reports, per chain, behind each of the first `tune` transitions: StepAdapt below, the statement
+finrom_hmc_step_adapt_update is tested against.  The transition itself is the one above with that chain's eps."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -59,17 +63,97 @@ MAX_DEPTH_LIMIT = 10
 STOP_DEPTH, STOP_TREE_TURNED, STOP_SUBTREE_TURNED, STOP_DIVERGED = 0, 1, 2, 3
 
 
-class Nuts:
-    """nuts=Nuts(max_depth, metric=None): at most 2^max_depth - 1 leapfrog steps per transition (the reference: 7); metric: a
-    laplace.LowRankMetric in the chain's own coordinates (whitened ones under prior=), the reference's `scaling`."""
+class StepAdapt:
+    """Nuts(adapt=StepAdapt(target_accept, tune)): the dual-averaging warm-up of the step size (Hoffman & Gelman 2014, Algorithm 5;
+    the reference's `tune=100, target_accept=0.98`, bayesian_inference/inference.py:145,165-166), per chain as PyMC3 has it.  The
+    specification handed to a chain function and, started, the result `res.adapt`; the statement of finrom_hmc_step_adapt_update
+    (csrc/hmc_nuts_model.hip).
 
-    def __init__(self, max_depth=7, metric=None):
+    A started StepAdapt holds per chain [C] eps (the step the next transition takes), hbar and xbar (the log-domain state), and mu =
+    log(10 eps0) of the caller's eps=, formed once; `next`: the global index of the next transition.  It starts at (eps0, 0, 0).
+    update(a, p) behind the transition with global index p, a [C] its accept_stat, t = p + 1, ONLY WHILE t <= tune:
+        w    = 1 / (t + t0)
+        hbar = (1 - w) * hbar + w * (target - a)
+        s    = sqrt(t)
+        x    = mu - hbar * s / gamma
+        eta  = 1 / (s * sqrt(s))                    (t^-kappa, kappa = 0.75, without pow)
+        xbar = eta * x + (1 - eta) * xbar
+        eps  = exp(x) if t < tune, exp(xbar) if t == tune: the step every later transition takes
+    every operation as written, nothing contracted: +, -, *, / and sqrt are correctly rounded here and on the device, so hbar and xbar
+    are the device's bits and only exp can differ.  tune = 0 never moves eps.
+    target_accept, tune: None stands for 0.8 and 100.  resume: the `adapt` of the run this one continues (its target_accept and tune
+    are taken over, and values given beside it that differ from them are refused; the run must start at proposal0 = resume.next, the
+    continuation rule of ChainStats(resume=))."""
+    GAMMA, T0, KAPPA = 0.05, 10.0, 0.75
+
+    def __init__(self, target_accept=None, tune=None, resume=None):
+        if resume is not None:
+            if not isinstance(resume, StepAdapt) or not resume.started:
+                raise ValueError("StepAdapt: resume= takes the adapt a run returned")
+            if target_accept not in (None, resume.target_accept) or tune not in (None, resume.tune):
+                raise ValueError(f"StepAdapt: target_accept = {target_accept}, tune = {tune} differ from the resumed run's "
+                                 f"{resume.target_accept}, {resume.tune}")
+            target_accept, tune = resume.target_accept, resume.tune
+        target_accept, tune = 0.8 if target_accept is None else target_accept, 100 if tune is None else tune
+        if not 0.0 < target_accept < 1.0:
+            raise ValueError(f"StepAdapt: target_accept = {target_accept} is outside (0, 1)")
+        if int(tune) != tune or tune < 0:
+            raise ValueError(f"StepAdapt: tune = {tune} is not a number of transitions >= 0")
+        self.target_accept, self.tune, self.resume = float(target_accept), int(tune), resume
+        self.next = None
+
+    started = property(lambda self: self.next is not None)
+
+    def begin(self, eps0, C, proposal0):
+        """-> a started StepAdapt for C chains whose first transition has global index proposal0: (eps0, 0, 0) with mu = log(10
+        eps0), or a copy of resume's state."""
+        s, r = StepAdapt(self.target_accept, self.tune), self.resume
+        if r is None:
+            if not eps0 > 0.0:
+                raise ValueError(f"StepAdapt: eps = {eps0} is not a step size > 0")
+            s.mu = float(np.log(10.0 * eps0))
+            s.eps, s.hbar, s.xbar = np.full(C, float(eps0)), np.zeros(C), np.zeros(C)
+        else:
+            if proposal0 != r.next:
+                raise ValueError(f"StepAdapt: the resumed run ended before transition {r.next}; this one starts at proposal0 = {proposal0}")
+            if len(r.eps) != C:
+                raise ValueError(f"StepAdapt: the resumed run had {len(r.eps)} chains, this one {C}")
+            s.mu, s.eps, s.hbar, s.xbar = r.mu, r.eps.copy(), r.hbar.copy(), r.xbar.copy()
+        s.next = int(proposal0)
+        return s
+
+    def update(self, a, p):
+        """Behind the transition with global index p: a [C] its accept_stat."""
+        if p != self.next:
+            raise ValueError(f"StepAdapt.update: transition {p} after transition {self.next - 1}")
+        self.next = p + 1
+        if p + 1 > self.tune:
+            return
+        t = float(p + 1)
+        w = 1.0 / (t + self.T0)
+        self.hbar = (1.0 - w) * self.hbar + w * (self.target_accept - np.asarray(a, dtype=np.float64))
+        s = np.sqrt(t)
+        x = self.mu - self.hbar * s / self.GAMMA
+        eta = 1.0 / (s * np.sqrt(s))
+        self.xbar = eta * x + (1.0 - eta) * self.xbar
+        self.eps = np.exp(x if p + 1 < self.tune else self.xbar)
+
+
+class Nuts:
+    """nuts=Nuts(max_depth, metric=None, adapt=None): at most 2^max_depth - 1 leapfrog steps per transition (the reference: 7);
+    metric: a laplace.LowRankMetric in the chain's own coordinates (whitened ones under prior=), the reference's `scaling`; adapt: a
+    StepAdapt, the reference's `tune` and `target_accept` (None: the caller's eps throughout)."""
+
+    def __init__(self, max_depth=7, metric=None, adapt=None):
         if int(max_depth) != max_depth or not 1 <= max_depth <= MAX_DEPTH_LIMIT:
             raise ValueError(f"Nuts: max_depth = {max_depth} is outside 1 .. {MAX_DEPTH_LIMIT}")
         if metric is not None and not all(hasattr(metric, a) for a in ("rho", "n", "Vt", "lam")):
             raise ValueError("Nuts: metric= takes a laplace.LowRankMetric (Vt [rho, n], lam [rho])")
+        if adapt is not None and not isinstance(adapt, StepAdapt):
+            raise ValueError("Nuts: adapt= takes a StepAdapt(target_accept, tune)")
         self.max_depth = int(max_depth)
         self.metric = metric
+        self.adapt = adapt
 
     def metric_for(self, n, who="Nuts"):
         """The metric of chains with n coordinates, where n is first known: None for no metric or one of rank zero (the identity:

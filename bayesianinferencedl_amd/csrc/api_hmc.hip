@@ -351,18 +351,21 @@ int finrom_hmc_trajectory_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, int32_
   return launch_hmc_ml_trajectory(m, h, n_steps, a->Kq[0], a->Kq[1], data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p,
                                   (float*)mlp->tape.p, out, a->loss, a->info, (hipStream_t)stream);
 }
-int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, const uint64_t* seeds, int64_t proposal0, int32_t max_depth,
-                       const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream) {
+}  // extern "C"
+// finrom_hmc_nuts_ml (eps_c NULL: the state's step) and finrom_hmc_nuts_ml_adapt (eps_c [C]: each chain's own)
+static int hmc_nuts_ml_impl(finrom_mlp_t mlp, const finrom_hmc_state* a, const double* eps_c, const uint64_t* seeds, int64_t proposal0,
+                            int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
+                            void* stream, const std::string& who) {
   CallGuard cg((hipStream_t)stream);
   HmcDev h;
-  if (int rc = hmc_dev(a, &h, "hmc_nuts_ml")) return rc;
+  if (int rc = hmc_dev(a, &h, who.c_str())) return rc;
   if (max_depth < 1 || max_depth > NUTS_MAX_DEPTH) {
-    set_error("hmc_nuts_ml: max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH)); return FINROM_ERR_ARG;
+    set_error(who + ": max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH)); return FINROM_ERR_ARG;
   }
-  if (proposal0 < 0) { set_error("hmc_nuts_ml: proposal0 < 0"); return FINROM_ERR_ARG; }
-  if (!seeds) { set_error("hmc_nuts_ml: null seeds"); return FINROM_ERR_ARG; }
+  if (proposal0 < 0) { set_error(who + ": proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (!seeds) { set_error(who + ": null seeds"); return FINROM_ERR_ARG; }
   double* out = nullptr;
-  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_nuts_ml")) return rc;
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, who.c_str())) return rc;
   if (a->C == 0) return 0;
   const MlpDev& m = mlp->d;
   const int64_t wsd = hmc_nuts_ws_doubles(a->C, a->n);
@@ -370,9 +373,20 @@ int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, const uint64
   NutsDev nd;
   nd.max_depth = max_depth; nd.proposal0 = proposal0; nd.seeds = (const unsigned long long*)seeds;
   nd.ws = (double*)mlp->nuts_ws.p; nd.wloss = nd.ws + wsd; nd.winfo = (int*)(nd.wloss + a->C); nd.scal = nd.wloss + 2 * a->C; nd.st_loss = a->loss;
-  nd.tree = tree; nd.accept_stat = accept_stat;
+  nd.tree = tree; nd.accept_stat = accept_stat; nd.eps_c = eps_c;
   return launch_hmc_nuts_ml(m, h, nd, data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p, (float*)mlp->tape.p, out,
                             (hipStream_t)stream);
+}
+extern "C" {
+int finrom_hmc_nuts_ml(finrom_mlp_t mlp, const finrom_hmc_state* a, const uint64_t* seeds, int64_t proposal0, int32_t max_depth,
+                       const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream) {
+  return hmc_nuts_ml_impl(mlp, a, nullptr, seeds, proposal0, max_depth, data, data_per_sample, tree, accept_stat, stream, "hmc_nuts_ml");
+}
+int finrom_hmc_nuts_ml_adapt(finrom_mlp_t mlp, const finrom_hmc_state* a, const double* eps, const uint64_t* seeds, int64_t proposal0,
+                             int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
+                             void* stream) {
+  if (!eps) { set_error("hmc_nuts_ml_adapt: null eps"); return FINROM_ERR_ARG; }
+  return hmc_nuts_ml_impl(mlp, a, eps, seeds, proposal0, max_depth, data, data_per_sample, tree, accept_stat, stream, "hmc_nuts_ml_adapt");
 }
 }  // extern "C"
 // ---- the No-U-turn transition under any model, one leaf per launch (hmc_nuts_model.hip; hmc.py model="fom" | "rom" | "romml", nuts=) ----
@@ -411,25 +425,74 @@ int64_t finrom_hmc_nuts_ws_bytes(int64_t C, int32_t n, int32_t max_depth) {
   }
   return hmc_nuts_tree_ws_bytes(C, n, max_depth);
 }
-int finrom_hmc_nuts_begin(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* A, const double* theta0, int32_t P,
-                          double* theta_out, void* stream) {
+}  // extern "C"
+// begin and leaf (eps_c NULL: the state's step) and their _adapt forms (eps_c [C]: each chain's own)
+static int hmc_nuts_begin_impl(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* eps_c, const double* A,
+                               const double* theta0, int32_t P, double* theta_out, void* stream, const char* who) {
   CallGuard cg((hipStream_t)stream);
   HmcDev h; NutsTreeDev d; NutsMap tm;
-  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, "hmc_nuts_begin")) return rc;
-  if (int rc = hmc_nuts_map("hmc_nuts_begin", A, theta0, P, theta_out, &tm)) return rc;
+  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, who)) return rc;
+  if (int rc = hmc_nuts_map(who, A, theta0, P, theta_out, &tm)) return rc;
+  d.eps_c = eps_c;
   return launch_hmc_nuts_begin(h, d, tm, (hipStream_t)stream);
+}
+static int hmc_nuts_leaf_impl(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* eps_c, const double* grad,
+                              const double* g_theta, const double* A, const double* theta0, int32_t P, double* theta_out, void* stream,
+                              const std::string& who) {
+  CallGuard cg((hipStream_t)stream);
+  HmcDev h; NutsTreeDev d; NutsMap tm;
+  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, who.c_str())) return rc;
+  if ((grad != nullptr) == (g_theta != nullptr)) {
+    set_error(who + ": exactly one of grad and g_theta must be given"); return FINROM_ERR_ARG;
+  }
+  if (g_theta != nullptr && !A) { set_error(who + ": g_theta without A"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_nuts_map(who.c_str(), A, theta0, P, theta_out, &tm)) return rc;
+  d.eps_c = eps_c;
+  return launch_hmc_nuts_leaf(h, d, grad, g_theta, tm, (hipStream_t)stream);
+}
+extern "C" {
+int finrom_hmc_nuts_begin(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* A, const double* theta0, int32_t P,
+                          double* theta_out, void* stream) {
+  return hmc_nuts_begin_impl(a, tr, nullptr, A, theta0, P, theta_out, stream, "hmc_nuts_begin");
 }
 int finrom_hmc_nuts_leaf(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* grad, const double* g_theta,
                          const double* A, const double* theta0, int32_t P, double* theta_out, void* stream) {
+  return hmc_nuts_leaf_impl(a, tr, nullptr, grad, g_theta, A, theta0, P, theta_out, stream, "hmc_nuts_leaf");
+}
+int finrom_hmc_nuts_begin_adapt(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* eps, const double* A,
+                                const double* theta0, int32_t P, double* theta_out, void* stream) {
+  if (!eps) { set_error("hmc_nuts_begin_adapt: null eps"); return FINROM_ERR_ARG; }
+  return hmc_nuts_begin_impl(a, tr, eps, A, theta0, P, theta_out, stream, "hmc_nuts_begin_adapt");
+}
+int finrom_hmc_nuts_leaf_adapt(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, const double* eps, const double* grad,
+                               const double* g_theta, const double* A, const double* theta0, int32_t P, double* theta_out,
+                               void* stream) {
+  if (!eps) { set_error("hmc_nuts_leaf_adapt: null eps"); return FINROM_ERR_ARG; }
+  return hmc_nuts_leaf_impl(a, tr, eps, grad, g_theta, A, theta0, P, theta_out, stream, "hmc_nuts_leaf_adapt");
+}
+// the dual-averaging update of every chain's step (hmc_nuts_model.hip): everything refused here, before any device call
+int finrom_hmc_step_adapt_update(const finrom_hmc_step_adapt* ad, int64_t C, int64_t proposal0, const int64_t* pt,
+                                 const double* accept_stat, double* step_size, void* stream) {
   CallGuard cg((hipStream_t)stream);
-  HmcDev h; NutsTreeDev d; NutsMap tm;
-  if (int rc = hmc_nuts_tree_dev(a, tr, &h, &d, "hmc_nuts_leaf")) return rc;
-  if ((grad != nullptr) == (g_theta != nullptr)) {
-    set_error("hmc_nuts_leaf: exactly one of grad and g_theta must be given"); return FINROM_ERR_ARG;
+  if (!ad || !ad->eps || !ad->hbar || !ad->xbar) {
+    set_error("hmc_step_adapt_update: null descriptor or null eps, hbar or xbar in finrom_hmc_step_adapt"); return FINROM_ERR_ARG;
   }
-  if (g_theta != nullptr && !A) { set_error("hmc_nuts_leaf: g_theta without A"); return FINROM_ERR_ARG; }
-  if (int rc = hmc_nuts_map("hmc_nuts_leaf", A, theta0, P, theta_out, &tm)) return rc;
-  return launch_hmc_nuts_leaf(h, d, grad, g_theta, tm, (hipStream_t)stream);
+  if (ad->tune < 0) { set_error("hmc_step_adapt_update: tune < 0"); return FINROM_ERR_ARG; }
+  if (!(ad->target > 0.0 && ad->target < 1.0)) {
+    set_error("hmc_step_adapt_update: target = " + std::to_string(ad->target) + " is outside (0, 1)"); return FINROM_ERR_ARG;
+  }
+  if (!(ad->gamma > 0.0) || !(ad->t0 > 0.0) || !std::isfinite(ad->mu)) {
+    set_error("hmc_step_adapt_update: gamma or t0 is not > 0, or mu is not finite"); return FINROM_ERR_ARG;
+  }
+  if (C < 0) { set_error("hmc_step_adapt_update: C < 0"); return FINROM_ERR_ARG; }
+  if (proposal0 < 0) { set_error("hmc_step_adapt_update: proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (C == 0) return 0;
+  if (!pt) { set_error("hmc_step_adapt_update: null pt"); return FINROM_ERR_ARG; }
+  if (!accept_stat) { set_error("hmc_step_adapt_update: null accept_stat"); return FINROM_ERR_ARG; }
+  StepAdaptDev d;
+  d.eps = ad->eps; d.hbar = ad->hbar; d.xbar = ad->xbar; d.mu = ad->mu; d.target = ad->target; d.gamma = ad->gamma; d.t0 = ad->t0;
+  d.tune = ad->tune; d.C = C; d.proposal0 = proposal0; d.pt = (const long long*)pt; d.accept_stat = accept_stat; d.step_size = step_size;
+  return launch_hmc_step_adapt(d, (hipStream_t)stream);
 }
 int finrom_hmc_nuts_end(const finrom_hmc_state* a, const finrom_hmc_nuts_tree* tr, void* stream) {
   CallGuard cg((hipStream_t)stream);
@@ -513,22 +576,24 @@ int finrom_hmc_end_metric(const finrom_hmc_state* a, finrom_metric_t metric, int
   if (n_steps < 0) { set_error("hmc_end_metric: n_steps < 0"); return FINROM_ERR_ARG; }
   return launch_hmc_end_metric(h, metric->d, a->Kq[n_steps & 1], (hipStream_t)stream);
 }
+}  // extern "C"
 // the No-U-turn transition under the metric (hmc_nuts.hip): finrom_hmc_nuts_ml's checks, the metric's, the larger workspace
-int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* a, finrom_metric_t metric, const uint64_t* seeds, int64_t proposal0,
-                              int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
-                              void* stream) {
+// (eps_c NULL: the state's step; finrom_hmc_nuts_ml_metric_adapt: each chain's own)
+static int hmc_nuts_ml_metric_impl(finrom_mlp_t mlp, const finrom_hmc_state* a, finrom_metric_t metric, const double* eps_c,
+                                   const uint64_t* seeds, int64_t proposal0, int32_t max_depth, const double* data,
+                                   int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream, const std::string& who) {
   CallGuard cg((hipStream_t)stream);
   HmcDev h;
-  if (int rc = hmc_dev(a, &h, "hmc_nuts_ml_metric")) return rc;
+  if (int rc = hmc_dev(a, &h, who.c_str())) return rc;
   if (max_depth < 1 || max_depth > NUTS_MAX_DEPTH) {
-    set_error("hmc_nuts_ml_metric: max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH));
+    set_error(who + ": max_depth = " + std::to_string(max_depth) + " is outside 1 .. " + std::to_string(NUTS_MAX_DEPTH));
     return FINROM_ERR_ARG;
   }
-  if (proposal0 < 0) { set_error("hmc_nuts_ml_metric: proposal0 < 0"); return FINROM_ERR_ARG; }
-  if (!seeds) { set_error("hmc_nuts_ml_metric: null seeds"); return FINROM_ERR_ARG; }
-  if (int rc = hmc_metric_check(a, metric, "hmc_nuts_ml_metric")) return rc;
+  if (proposal0 < 0) { set_error(who + ": proposal0 < 0"); return FINROM_ERR_ARG; }
+  if (!seeds) { set_error(who + ": null seeds"); return FINROM_ERR_ARG; }
+  if (int rc = hmc_metric_check(a, metric, who.c_str())) return rc;
   double* out = nullptr;
-  if (int rc = hmc_ml_prepare(mlp, a, data, &out, "hmc_nuts_ml_metric")) return rc;
+  if (int rc = hmc_ml_prepare(mlp, a, data, &out, who.c_str())) return rc;
   if (a->C == 0) return 0;
   const MlpDev& m = mlp->d;
   const int64_t wsd = hmc_nuts_metric_ws_doubles(a->C, a->n);
@@ -536,9 +601,23 @@ int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* a, finro
   NutsDev nd;
   nd.max_depth = max_depth; nd.proposal0 = proposal0; nd.seeds = (const unsigned long long*)seeds;
   nd.ws = (double*)mlp->nuts_ws.p; nd.wloss = nd.ws + wsd; nd.winfo = (int*)(nd.wloss + a->C); nd.scal = nd.wloss + 2 * a->C; nd.st_loss = a->loss;
-  nd.tree = tree; nd.accept_stat = accept_stat;
+  nd.tree = tree; nd.accept_stat = accept_stat; nd.eps_c = eps_c;
   return launch_hmc_nuts_ml_metric(m, h, nd, metric->d, data, data_per_sample ? m.n_out : 0, (const double*)mlp->sur_zero.p,
                                    (float*)mlp->tape.p, out, (hipStream_t)stream);
+}
+extern "C" {
+int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* a, finrom_metric_t metric, const uint64_t* seeds, int64_t proposal0,
+                              int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
+                              void* stream) {
+  return hmc_nuts_ml_metric_impl(mlp, a, metric, nullptr, seeds, proposal0, max_depth, data, data_per_sample, tree, accept_stat, stream,
+                                 "hmc_nuts_ml_metric");
+}
+int finrom_hmc_nuts_ml_metric_adapt(finrom_mlp_t mlp, const finrom_hmc_state* a, finrom_metric_t metric, const double* eps,
+                                    const uint64_t* seeds, int64_t proposal0, int32_t max_depth, const double* data,
+                                    int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream) {
+  if (!eps) { set_error("hmc_nuts_ml_metric_adapt: null eps"); return FINROM_ERR_ARG; }
+  return hmc_nuts_ml_metric_impl(mlp, a, metric, eps, seeds, proposal0, max_depth, data, data_per_sample, tree, accept_stat, stream,
+                                 "hmc_nuts_ml_metric_adapt");
 }
 int finrom_hmc_leapfrog_field_metric(finrom_rom_t rom, finrom_mlp_t mlp, const double* Sop, finrom_sampler_t prior,
                                      const double* field_mean, double* field, double* grad_field, const finrom_hmc_state* a,

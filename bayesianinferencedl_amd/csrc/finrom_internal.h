@@ -120,7 +120,15 @@ struct NutsTreeDev {
   const unsigned long long* seeds;
   double* ws; double* scal; int* ints;
   double* st_loss; int* tree; double* accept_stat; int* active;
+  const double* eps_c = nullptr;         // [C], optional: each chain's own step in the place of HmcDev::eps (begin and leaf)
 };
+// finrom_hmc_step_adapt_update: finrom_hmc_step_adapt with the call's own arguments beside it
+struct StepAdaptDev {
+  double* eps; double* hbar; double* xbar;
+  double mu, target, gamma, t0; long long tune;
+  int64_t C; long long proposal0; const long long* pt; const double* accept_stat; double* step_size;
+};
+int launch_hmc_step_adapt(const StepAdaptDev& ad, hipStream_t st);
 struct NutsMap { const double* A; const double* theta0; int P; double* theta_out; };
 int64_t hmc_nuts_tree_ws_bytes(int64_t C, int n, int max_depth);
 int launch_hmc_nuts_begin(const HmcDev& h, const NutsTreeDev& a, const NutsMap& tm, hipStream_t st);

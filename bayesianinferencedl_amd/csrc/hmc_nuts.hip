@@ -149,7 +149,8 @@ __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_nuts_ml_kernel(MlpDev m, H
   const double* __restrict__ p0 = h.P_block + (*h.jt * C + c) * n;
   const unsigned long long seed = a.seeds[c], gp = (unsigned long long)(a.proposal0 + row);
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), g0 = (unsigned)gp, g1 = (unsigned)(gp >> 32);
-  const double hh = 0.5 * h.eps * h.c_pri, coef = h.c_lik / h.c_pri;
+  const double eps = a.eps_c != nullptr ? a.eps_c[c] : h.eps;          // (uniform over the workgroup: a scalar load)
+  const double hh = 0.5 * eps * h.c_pri, coef = h.c_lik / h.c_pri;
 
   // under a metric: the velocities' arrays, the two sets of sums in LDS, the maps' coefficients
   double *Lv = nullptr, *Rv = nullptr, *wv = nullptr, *wvh = nullptr, *dA = nullptr, *dB = nullptr;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(HMC_ML_THREADS) void hmc_nuts_ml_kernel(MlpDev m, H
     }
     __syncthreads();
     const bool fwd = __builtin_amdgcn_readfirstlane(bc[0]) != 0;              // (uniform, and the compiler knows it)
-    const double dsgn = fwd ? 1.0 : -1.0, dh = -dsgn * hh, deps = dsgn * h.eps;
+    const double dsgn = fwd ? 1.0 : -1.0, dh = -dsgn * hh, deps = dsgn * eps;
     double* const Ek = w + (fwd ? A_RK : A_LK) * plane;
     double* const Ep = fwd ? Rp : Lp;
     double* const EdU = w + (fwd ? A_RDU : A_LDU) * plane;

@@ -131,7 +131,8 @@ __global__ __launch_bounds__(NT) void hmc_nuts_begin_kernel(HmcDev h, NutsTreeDe
   __syncthreads();
   ThetaSums ts;
   ts.clear();
-  start_walker(ch, bc[0] != 0, 0.5 * h.eps * h.c_pri, h.eps, n, h.Kq0 + o, tm, ts);
+  const double eps = a.eps_c != nullptr ? a.eps_c[c] : h.eps;          // (uniform over the workgroup)
+  start_walker(ch, bc[0] != 0, 0.5 * eps * h.c_pri, eps, n, h.Kq0 + o, tm, ts);
   if (tm.A != nullptr) ts.store(tm, c, redt);
 }
 
@@ -179,8 +180,9 @@ __global__ __launch_bounds__(NT) void hmc_nuts_leaf_kernel(HmcDev h, NutsTreeDev
   const bool flagged = h.info[c] != 0;
   const unsigned long long seed = a.seeds[c], gp = (unsigned long long)(a.proposal0 + *h.pt);
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), g0 = (unsigned)gp, g1 = (unsigned)(gp >> 32);
-  const double hh = 0.5 * h.eps * h.c_pri, coef = h.c_lik / h.c_pri;
-  const double dsgn = fwd ? 1.0 : -1.0, dh = -dsgn * hh, deps = dsgn * h.eps;
+  const double eps = a.eps_c != nullptr ? a.eps_c[c] : h.eps;          // (uniform over the workgroup)
+  const double hh = 0.5 * eps * h.c_pri, coef = h.c_lik / h.c_pri;
+  const double dsgn = fwd ? 1.0 : -1.0, dh = -dsgn * hh, deps = dsgn * eps;
   double* const kn = h.Kq0 + o;                                       // the leaf's position k'
   const double* __restrict__ mean = h.mean + o;
   const int i_max = __popc((unsigned)i >> 1);
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(NT) void hmc_nuts_leaf_kernel(HmcDev h, NutsTreeDev
       if (tid == 0) bc[3] = draw_subtree(sc, g0, g1, j_next, k0, k1);
       __syncthreads();
       fwd_next = bc[3];
-      start_walker(ch, fwd_next != 0, hh, h.eps, n, kn, tm, ts);
+      start_walker(ch, fwd_next != 0, hh, eps, n, kn, tm, ts);
     }
   } else if (!ended) {                                                // the next leaf of this sub-tree: its half kick and drift
     for (int e = tid; e < n; e += NT) {
@@ -328,6 +330,29 @@ __global__ __launch_bounds__(256) void hmc_nuts_end_kernel(HmcDev h, NutsTreeDev
 
 __global__ void hmc_nuts_tree_advance_kernel(long long* jt, long long* pt) { *jt += 1; *pt += 1; }
 
+// The dual-averaging update of every chain's step (nuts.py StepAdapt.update, Hoffman & Gelman 2014, Algorithm 5): one thread per chain,
+// behind a transition of either form and its counters' advance.  The transition is row *pt - 1 with global index p = proposal0 + row;
+// the step it took goes to step_size first, then, while t = p + 1 <= tune, the recursion in the statement's operations, one rounding
+// each (this file contracts nothing).  Everything is read from device memory, so a captured launch is replayed as it is.
+__global__ __launch_bounds__(256) void hmc_step_adapt_kernel(StepAdaptDev ad) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const long long row = *ad.pt - 1;
+  if (c >= ad.C || row < 0) return;
+  const double e = ad.eps[c];
+  if (ad.step_size != nullptr) ad.step_size[row * ad.C + c] = e;
+  const long long ti = ad.proposal0 + row + 1;
+  if (ti > ad.tune) return;
+  const double t = (double)ti, acc = ad.accept_stat[row * ad.C + c];
+  const double w = 1.0 / (t + ad.t0);
+  const double hbar = (1.0 - w) * ad.hbar[c] + w * (ad.target - acc);
+  const double s = sqrt(t);
+  const double x = ad.mu - hbar * s / ad.gamma;
+  const double eta = 1.0 / (s * sqrt(s));
+  const double xbar = eta * x + (1.0 - eta) * ad.xbar[c];
+  ad.hbar[c] = hbar; ad.xbar[c] = xbar;
+  ad.eps[c] = exp(ti < ad.tune ? x : xbar);
+}
+
 }  // namespace
 
 int64_t hmc_nuts_tree_ws_bytes(int64_t C, int n, int max_depth) {
@@ -348,6 +373,14 @@ int launch_hmc_nuts_leaf(const HmcDev& h, const NutsTreeDev& a, const double* gr
   if (h.C == 0) return 0;
   ScopedKernelTimer t(K_MISC, st);
   hipLaunchKernelGGL(hmc_nuts_leaf_kernel, dim3((unsigned)h.C), dim3(NT), 0, st, h, a, grad, g_theta, tm);
+  FR_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_hmc_step_adapt(const StepAdaptDev& ad, hipStream_t st) {
+  if (ad.C == 0) return 0;
+  ScopedKernelTimer t(K_MISC, st);
+  hipLaunchKernelGGL(hmc_step_adapt_kernel, dim3((unsigned)((ad.C + 255) / 256)), dim3(256), 0, st, ad);
   FR_HIP(hipGetLastError());
   return 0;
 }

@@ -47,7 +47,8 @@ int launch_hmc_ml_trajectory(const MlpDev& m, const HmcDev& h, int n_steps, doub
 
 // hmc_nuts.hip (finrom_hmc_nuts_ml): one No-U-turn transition of every chain in one launch, one 1024-thread workgroup per chain, then
 // the counters' advance.  ws: NUTS_ARRAYS arrays [C x n] (hmc_nuts_ws_doubles), wloss [C] / winfo [C]: a leaf's misfit and flag; scal [C x NUTS_SCALARS];
-// st_loss [C]: the state's misfit (written where a candidate is adopted); tree [rows x C x 4], accept_stat [rows x C]: optional
+// st_loss [C]: the state's misfit (written where a candidate is adopted); tree [rows x C x 4], accept_stat [rows x C]: optional;
+// eps_c [C]: optional, each chain's own step in the place of HmcDev::eps (finrom_hmc_nuts_ml_adapt; NULL: the state's step)
 constexpr int NUTS_MAX_DEPTH = 10;
 constexpr int NUTS_ARRAYS = 15 + 2 * NUTS_MAX_DEPTH;
 constexpr int NUTS_SCALARS = 8;      // per chain, thread 0's: H0, W, W_sub, the sum of min(1, w), the sub-tree candidate's U and misfit, u_top
@@ -56,6 +57,7 @@ struct NutsDev {
   const unsigned long long* seeds;
   double* ws; double* wloss; int* winfo; double* scal; double* st_loss;
   int* tree; double* accept_stat;
+  const double* eps_c = nullptr;
 };
 int64_t hmc_nuts_ws_doubles(int64_t C, int n);
 int launch_hmc_nuts_ml(const MlpDev& m, const HmcDev& h, const NutsDev& a, const double* data, int64_t data_stride, const double* zero,

@@ -859,6 +859,45 @@ int finrom_hmc_end_metric(const finrom_hmc_state* st, finrom_metric_t metric, in
 int finrom_hmc_nuts_ml_metric(finrom_mlp_t mlp, const finrom_hmc_state* st, finrom_metric_t metric, const uint64_t* seeds,
                               int64_t proposal0, int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree,
                               double* accept_stat, void* stream);
+/* The step-size warm-up of the No-U-turn chains (hmc.py nuts=Nuts(max_depth, adapt=StepAdapt(target_accept, tune)); the statement
+ * nuts.py StepAdapt): dual averaging (Hoffman & Gelman 2014, Algorithm 5) on the accept_stat every transition writes, the reference's
+ * `tune=100, target_accept=0.98` (bayesian_inference/inference.py:145,165-166).  Every chain adapts its OWN step, eps [C] on the device.
+ *   finrom_hmc_nuts_ml_adapt, finrom_hmc_nuts_ml_metric_adapt, finrom_hmc_nuts_begin_adapt, finrom_hmc_nuts_leaf_adapt
+ *       the entry point without _adapt with chain c's step read from eps[c] (DEVICE) in the place of st->eps: one uniform load at
+ *       the top of the kernel, h = 0.5 eps[c] c_pri formed where it is formed from st->eps.  With eps[c] == st->eps for every c they
+ *       leave the bytes of their counterparts; a chain's bits depend on its own step alone.  (The start point's round of the
+ *       leaf-per-round form is finrom_hmc_nuts_begin on a state with eps = 0, and finrom_hmc_nuts_end serves both.)  They refuse
+ *       what their counterparts refuse, and a null eps (FINROM_ERR_ARG).
+ *   finrom_hmc_step_adapt_update
+ *       ONE launch, one thread per chain, behind a transition of either form (after the counters' advance): the transition is row
+ *       r = *pt - 1 of accept_stat [rows x C] with global index p = proposal0 + r.  step_size [rows x C] (or NULL) row r = eps, the
+ *       step that transition took; then with t = p + 1, a = accept_stat[r][c], ONLY WHILE t <= tune:
+ *         w = 1 / (t + t0);  hbar = (1 - w) hbar + w (target - a);  s = sqrt(t);  x = mu - hbar s / gamma;  eta = 1 / (s sqrt(s));
+ *         xbar = eta x + (1 - eta) xbar;  eps = exp(x) if t < tune, exp(xbar) if t == tune
+ *       every operation as written, one rounding each, nothing contracted: hbar and xbar are the statement's bits, eps is within
+ *       the two exponentials' error bounds.  t > tune (tune = 0 included): nothing but step_size is written.  p and a are read from
+ *       the device, so a captured launch is replayed with no node parameter changed; nothing allocates: legal while a capture is
+ *       open.  The entry point knows no row count: the CALLER sizes accept_stat and step_size to at least *pt rows (the rows the
+ *       transitions' own tree and accept_stat arrays need), and a *pt of 0 -- no transition yet -- writes nothing.  Refused before any device call, with a message (FINROM_ERR_ARG): a null descriptor or eps, hbar, xbar; tune < 0; a
+ *       target outside (0, 1); gamma or t0 not > 0; C < 0; proposal0 < 0; a null pt or accept_stat.  C == 0: returns 0, no launch. */
+typedef struct {
+  double* eps; double* hbar; double* xbar;      /* [C] DEVICE: the step of the next transition; the log-domain state */
+  double mu, target, gamma, t0;                 /* log(10 eps0); target_accept; 0.05; 10 */
+  int64_t tune;                                 /* transitions that adapt: those with global index < tune */
+} finrom_hmc_step_adapt;
+int finrom_hmc_nuts_ml_adapt(finrom_mlp_t mlp, const finrom_hmc_state* st, const double* eps, const uint64_t* seeds, int64_t proposal0,
+                             int32_t max_depth, const double* data, int32_t data_per_sample, int32_t* tree, double* accept_stat,
+                             void* stream);
+int finrom_hmc_nuts_ml_metric_adapt(finrom_mlp_t mlp, const finrom_hmc_state* st, finrom_metric_t metric, const double* eps,
+                                    const uint64_t* seeds, int64_t proposal0, int32_t max_depth, const double* data,
+                                    int32_t data_per_sample, int32_t* tree, double* accept_stat, void* stream);
+int finrom_hmc_nuts_begin_adapt(const finrom_hmc_state* st, const finrom_hmc_nuts_tree* tr, const double* eps, const double* A,
+                                const double* theta0, int32_t P, double* theta_out, void* stream);
+int finrom_hmc_nuts_leaf_adapt(const finrom_hmc_state* st, const finrom_hmc_nuts_tree* tr, const double* eps, const double* grad,
+                               const double* g_theta, const double* A, const double* theta0, int32_t P, double* theta_out,
+                               void* stream);
+int finrom_hmc_step_adapt_update(const finrom_hmc_step_adapt* ad, int64_t C, int64_t proposal0, const int64_t* pt,
+                                 const double* accept_stat, double* step_size, void* stream);
 /* The draws of a block of B proposals ON THE DEVICE (hmc.py rng="philox"), in the layout finrom_hmc_begin / _begin_metric read: row
  * j * C + c of P_block [B x C x n] and of lu_block [B x C] belongs to proposal first_proposal + j of the chain with seed seeds[c]
  * (seeds [C]: DEVICE array).  For seed s and global proposal index p, Philox4x32-10 with key (s lo, s hi):
