@@ -184,6 +184,9 @@ SIGNATURES = {
     "finrom_rom_mirror_validate": (C.c_int, [C.POINTER(RomDesc), C.c_int32, c_i32p, c_f64p, c_i32p]),
     "finrom_rom_mirror_tables": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, c_f64p, c_i32p]),
     "finrom_rom_set_mirror_short": (C.c_int, [C.c_void_p, C.POINTER(RomDesc), c_f64p, C.c_double, C.c_double]),
+    "finrom_rom_set_mirror_compact": (C.c_int, [C.c_void_p, C.POINTER(RomDesc), c_f64p]),
+    "finrom_rom_compact_rows": (C.c_int, [C.POINTER(RomDesc), c_f64p, C.c_double, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, c_f64p,
+                                          C.c_int32, c_f64p]),
     "finrom_rom_mirror_counts": (C.c_int, [C.POINTER(RomDesc), c_f64p, c_i32p, c_i32p, c_i32p]),
     "finrom_rom_mirror_info": (C.c_int, [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]),
     "finrom_rom_last_form": (C.c_int, [C.c_void_p]),

@@ -39,7 +39,14 @@ struct finrom_rom_s {
   int projection = FINROM_PROJECTION_DIRECT;
   std::vector<double> tvg_host; std::vector<int> kmg_host, def_host;      // the grouped tables as uploaded (finrom_rom_set_mirror appends to them)
   int mirror_n = 0;                    // rows of the installed half descriptor
-  int mirror_counts[2][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / the short list
+  int mirror_counts[3][3] = {};        // finrom_rom_mirror_info: {rows with terms, k-steps, k-steps with arithmetic} of the half / short / compact list
+  // the COMPACT list (finrom_rom_set_mirror_compact, DESIGN 4b''): where its records start in RomDev::kmg, its padded k-step count (0:
+  // none), its final factor.  Kept here, not in RomDev: a launch that offers it gets them in the short list's fields (rom_project).
+  // Offered where finrom_solve_pairs masks the sweep by default (the batches of the block-row epilogue); read at creation:
+  // FINROM_ROM_COMPACT=1 wherever the short list is offered (tests), FINROM_ROM_NO_COMPACT=1 never (A/B)
+  int kmg_c = 0, nkg_c = 0, ext_final_c = 0;
+  bool compact_always = getenv("FINROM_ROM_COMPACT") != nullptr, no_compact = getenv("FINROM_ROM_NO_COMPACT") != nullptr;
+  bool compact(bool masked_by_default) const { return !no_compact && (compact_always || masked_by_default); }
   int last_form = FINROM_ROM_FORM_NONE;  // finrom_rom_last_form
   int last_epilogue = FINROM_ROM_EPILOGUE_NONE;      // finrom_rom_last_epilogue
   bool short_grouped = env_rom_short_grouped();      // (A/B, read at creation: the short half list keeps a group per leading parameter, as before group_pays)

@@ -216,8 +216,31 @@ int finrom_rom_set_mirror_short(finrom_rom_t h, const finrom_rom_desc* a, const 
   return 0;
 }
 
+// the compact list (DESIGN 4b''): a fourth list behind the short one, from the short descriptor's rows rotated per pattern class
+// (finrom_rom_compact_rows) with the rows below the caller's threshold left out.  No kernel knows it: a launch that offers it
+// (rom_project) hands the kernel its records in the short list's place, so the samples that pass the short list's tests walk it.
+int finrom_rom_set_mirror_compact(finrom_rom_t h, const finrom_rom_desc* a, const double* row_weight) {
+  if (!h || !a || !row_weight) { set_error("rom_set_mirror_compact: null argument"); return FINROM_ERR_ARG; }
+  RomDev& d = h->d;
+  if (d.nkg_s == 0) { set_error("rom_set_mirror_compact: finrom_rom_set_mirror_short comes first"); return FINROM_ERR_ARG; }
+  if (h->nkg_c > 0) { set_error("rom_set_mirror_compact: already installed"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  if (a->r != d.r || a->P != d.P || a->n != h->mirror_n) { set_error("rom_set_mirror_compact: sizes differ from the half descriptor's"); return FINROM_ERR_ARG; }
+  if (int rc = validate_row_weights(a, row_weight)) return rc;
+  GroupedTables g;
+  int kmg0 = 0;
+  RomDev nd = d;
+  HostTables next;
+  if (int rc = append_half_list(h, a, row_weight, nd, g, kmg0, next, "rom_set_mirror_compact")) return rc;
+  d = nd;
+  h->kmg_c = kmg0; h->nkg_c = g.nkg; h->ext_final_c = g.ext_final;
+  h->tvg_host.swap(next.tvg); h->kmg_host.swap(next.kmg); h->def_host.swap(next.def);
+  h->mirror_counts[2][0] = (int)rows_by_term_count(a).size(); h->mirror_counts[2][1] = g.live; h->mirror_counts[2][2] = g.fma_ksteps;
+  return 0;
+}
+
 int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps) {
-  if (!h || !live_rows || !ksteps || !fma_ksteps || which < 0 || which > 1) { set_error("rom_mirror_info: bad argument"); return FINROM_ERR_ARG; }
+  if (!h || !live_rows || !ksteps || !fma_ksteps || which < 0 || which > 2) { set_error("rom_mirror_info: bad argument"); return FINROM_ERR_ARG; }
   *live_rows = h->mirror_counts[which][0]; *ksteps = h->mirror_counts[which][1]; *fma_ksteps = h->mirror_counts[which][2];      // (zeros: not installed)
   return 0;
 }
@@ -304,7 +327,7 @@ int finrom_rom_set_projection(finrom_rom_t h, int32_t mode) {
 // (mirror: the call may offer the half list of finrom_rom_set_mirror to its samples -- finrom_rom_solve only)
 static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int factor, int* info, hipStream_t st,
                        double* w_r = nullptr, double* qoi_r = nullptr, bool mirror = false, bool roomy = false, bool short_waits = false,
-                       bool block_row = false) {
+                       bool block_row = false, bool compact = false) {
   h->last_form = FINROM_ROM_FORM_FULL;
   roomy = roomy && h->projection == FINROM_PROJECTION_DIRECT && rom_roomy_applies(h->d, factor, w_r, qoi_r);
   block_row = roomy && block_row;
@@ -316,6 +339,8 @@ static int rom_project(finrom_rom_t h, const double* theta, int64_t S, int facto
   RomDev d = h->d;
   d.ext = nullptr;
   if (!mirror) d.nkg_m = d.nkg_s = 0;
+  // (compact: the call offers the compact list -- the samples that would walk the short list walk it instead, same tests, same kernel)
+  if (compact && d.nkg_s > 0 && h->nkg_c > 0) { d.kmg_s = h->kmg_c; d.nkg_s = h->nkg_c; d.ext_final_s = h->ext_final_c; }
   if (d.nkg > 0 && S > 0 && (roomy || !rom_splitk_applies(d, S))) {      // the grouped main loop: room for the samples' scalars
     if (int rc = h->ext.reserve((size_t)S * d.n_ext * sizeof(double))) return rc;
     d.ext = (double*)h->ext.p;
@@ -342,7 +367,8 @@ static int64_t rom_piece_samples(size_t per_sample) {
 // between accumulate-chained MFMAs (finrom_rom_s::short_waits says where).  block_row: the short-waits form that eliminates each block
 // row in place instead of forming U_kk^-T (finrom_rom_s::block_row says where)
 static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
-                          double* B_r, int32_t* info, void* stream, bool roomy, bool short_waits = false, bool block_row = false) {
+                          double* B_r, int32_t* info, void* stream, bool roomy, bool short_waits = false, bool block_row = false,
+                          bool compact = false) {
   CallGuard cg((hipStream_t)stream);
   if (!h || S < 0 || (S > 0 && (!theta || (!qoi_r && h->d.n_obs > 0)))) { set_error("rom_solve: bad argument"); return FINROM_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
@@ -379,7 +405,7 @@ static int rom_solve_impl(finrom_rom_t h, const double* theta, int64_t S, double
     if (d.NB > 6 && want_factor && h->projection == FINROM_PROJECTION_DIRECT && A_r == nullptr && B_r == nullptr && w_r == nullptr &&
         qoi_r != nullptr && d.n_obs + 1 <= 16 * 3) factor = 3;
     if ((rc = rom_project(h, theta + s0 * d.P, Sc, factor, info ? info + s0 : nullptr, st,
-                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm, short_waits, block_row))) return rc;
+                          w_r ? w_r + s0 * d.r : nullptr, qoi_r ? qoi_r + s0 * d.n_obs : nullptr, true, rm, short_waits, block_row, compact))) return rc;
     if (factor >= 2) continue;
     int factored = factor;
     if (want_factor && d.NB > 6) {                                     // wider bases: blocked MFMA Cholesky kernel
@@ -396,7 +422,7 @@ extern "C" {
 
 int finrom_rom_solve(finrom_rom_t h, const double* theta, int64_t S, double* w_r, double* qoi_r, double* A_r,
                      double* B_r, int32_t* info, void* stream) {
-  return rom_solve_impl(h, theta, S, w_r, qoi_r, A_r, B_r, info, stream, false);
+  return rom_solve_impl(h, theta, S, w_r, qoi_r, A_r, B_r, info, stream, false, false, false, h ? h->compact(false) : false);
 }
 
 int finrom_rom_set_gradient(finrom_rom_t h, int32_t npairs, const int32_t* pair_p, const int32_t* pair_i, const double* G) {
@@ -629,9 +655,10 @@ int finrom_solve_pairs(finrom_fom_t fom, finrom_rom_t rom, const double* Sop, co
   // the mask is bounded from BELOW by the benchmark's contract (0.662 ms at 4096 samples; with the short waits the step measured
   // 0.660 and 0.678 ms there, with the fixed ones 0.69).  The batches whose sweep is masked BY DEFAULT eliminate their block rows in
   // place (round 15: no U_kk^-T; qoi_r differs at rounding level) at the basis widths where that measured faster -- also where
-  // FINROM_FOM_CUS, a blocking stream or the overlap switch then keep the mask away: same bits wherever the kernels run.
+  // FINROM_FOM_CUS, a blocking stream or the overlap switch then keep the mask away: same bits wherever the kernels run.  The same
+  // batches offer the COMPACT list (round 16, DESIGN 4b'') in the short list's place, for the same reason: other bits, at rounding level.
   if ((rc = rom_solve_impl(rom, theta, S, w_r, qoi_r, nullptr, nullptr, info, rst, half_plan && !rom->no_roomy, rom->short_waits(fst != st),
-                           rom->block_row(mask_by_default))))
+                           rom->block_row(mask_by_default), rom->compact(mask_by_default))))
     return fail(rc);
   // With a masked FOM stream only the SWEEP runs on it: pack + assembly go to an unmasked stream (they take 0.1 ms there against
   // 2.0 ms on 96 CUs beside the projection's start, and since the grouped projection loop the FOM half is the one that ends

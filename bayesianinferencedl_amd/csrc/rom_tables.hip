@@ -3,6 +3,7 @@
 #include "rom_tables.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
@@ -320,6 +321,49 @@ std::vector<KStep> mirror_ksteps(const finrom_rom_desc* a, const double* row_wei
 bool env_rom_short_grouped() { return getenv("FINROM_ROM_SHORT_GROUPED") != nullptr; }
 bool short_scale_free(const finrom_rom_desc* a, bool short_grouped) { return !short_grouped && (int)rows_by_term_count(a).size() < a->n; }
 
+// ---- the compact list (finrom_rom_set_mirror_compact, DESIGN 4b''): the rows of a pattern class rotated onto their singular directions
+// One-sided Jacobi on the ROWS of M [m x w] (Hestenes): plane rotations of row pairs until every pair is orthogonal to rounding,
+// relative to the two rows' own sizes -- so directions 1e-10 of the largest come out with their digits, which the class Gram
+// matrix (1e-20, below rounding) could not give.  Q [m x m] takes the same rotations from the identity: M_out = Q M_in.  Then
+// rows by size, descending: sigma[i] = |row i|.
+static void jacobi_rows(std::vector<double>& M, int m, int w, std::vector<double>& Q, std::vector<double>& sigma) {
+  Q.assign((size_t)m * m, 0.0);
+  for (int i = 0; i < m; ++i) Q[(size_t)i * m + i] = 1.0;
+  auto dot = [&](const double* x, const double* y) { double s = 0.0; for (int k = 0; k < w; ++k) s += x[k] * y[k]; return s; };
+  auto rotate = [](double* x, double* y, int len, double c, double s) {
+    for (int k = 0; k < len; ++k) { const double a = x[k], b = y[k]; x[k] = c * a - s * b; y[k] = s * a + c * b; }
+  };
+  constexpr double kTol = 4.0 * 2.220446049250313e-16;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    bool any = false;
+    for (int i = 0; i < m; ++i)
+      for (int j = i + 1; j < m; ++j) {
+        double* x = &M[(size_t)i * w]; double* y = &M[(size_t)j * w];
+        const double a = dot(x, x), b = dot(y, y), g = dot(x, y);
+        if (g == 0.0 || std::fabs(g) <= kTol * std::sqrt(a) * std::sqrt(b)) continue;
+        any = true;
+        const double zeta = (b - a) / (2.0 * g), t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+        rotate(x, y, w, c, s);
+        rotate(&Q[(size_t)i * m], &Q[(size_t)j * m], m, c, s);
+      }
+    if (!any) break;
+  }
+  std::vector<double> nrm(m);
+  for (int i = 0; i < m; ++i) nrm[i] = std::sqrt(dot(&M[(size_t)i * w], &M[(size_t)i * w]));
+  std::vector<int> ord(m);
+  for (int i = 0; i < m; ++i) ord[i] = i;
+  std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return nrm[x] > nrm[y]; });
+  std::vector<double> Ms(M.size()), Qs(Q.size());
+  sigma.resize(m);
+  for (int i = 0; i < m; ++i) {
+    std::memcpy(&Ms[(size_t)i * w], &M[(size_t)ord[i] * w], w * sizeof(double));
+    std::memcpy(&Qs[(size_t)i * m], &Q[(size_t)ord[i] * m], m * sizeof(double));
+    sigma[i] = nrm[ord[i]];
+  }
+  M.swap(Ms); Q.swap(Qs);
+}
+
 }  // namespace finrom
 
 using namespace finrom;
@@ -381,6 +425,64 @@ int finrom_rom_mirror_counts(const finrom_rom_desc* a, const double* row_weight,
   *live_rows = 0; *ksteps = 0; *fma_ksteps = 0;
   if (NB > 5 || !build_grouped_tables(a, ks, rp, g, &kclass, 0, 0, short_scale_free(a, env_rom_short_grouped()))) return 0;
   *live_rows = (int32_t)rows_by_term_count(a).size(); *ksteps = g.live; *fma_ksteps = g.fma_ksteps;
+  return 0;
+}
+
+// Host only: the rows of the COMPACT list from a short descriptor (DESIGN 4b'').  Every row's terms are multiplied by sqrt(weight)
+// and its load divided by it (desc->rhs is weight F: psi^T rhs stays what it was), so the result has no weight classes.  The
+// unloaded rows with terms form a class per pattern; a class's stacked tables [T_p1 | T_p2 | ..] are orthogonalised by
+// jacobi_rows, and where leaving out the rotated rows below tau x (the largest singular value over all classes) saves a k-step
+// of four rows the class's rows are REPLACED by the rotated ones, largest first, in the class's row positions.  Out: term_val
+// [nterms x r] and rhs [n] of the compact descriptor (same row_ptr / term_p), row_class [n] (-1: loaded or term-less), row_sigma
+// [n] (the singular values of the row's class in its row positions, largest first, rotated or not; 0 outside classes),
+// row_keep [n] (0: a rotated row below the threshold -- the caller gives it no terms), Q (optional, [n x q_ld], q_ld >= the
+// largest class): row i of a ROTATED class is  sum_j Q[i][j] sqrt(w_j) (member j's row),  members in ascending row order.
+int finrom_rom_compact_rows(const finrom_rom_desc* a, const double* row_weight, double tau, double* term_val, double* rhs,
+                            int32_t* row_class, double* row_sigma, int32_t* row_keep, double* Q, int32_t q_ld, double* sigma_max) {
+  if (!a || !row_weight || !term_val || !rhs || !row_class || !row_sigma || !row_keep || !sigma_max) { set_error("rom_compact_rows: null argument"); return FINROM_ERR_ARG; }
+  if (int rc = validate_rom_desc(a)) return rc;
+  if (int rc = validate_row_weights(a, row_weight)) return rc;
+  if (!a->rhs || !(tau >= 0.0 && tau < 1.0)) { set_error("rom_compact_rows: need the load and 0 <= tau < 1"); return FINROM_ERR_ARG; }
+  const int r = a->r, n = a->n;
+  for (int i = 0; i < n; ++i) {
+    const double sw = std::sqrt(row_weight[i]);
+    rhs[i] = a->rhs[i] / sw; row_class[i] = -1; row_sigma[i] = 0.0; row_keep[i] = 1;
+    for (int t = a->row_ptr[i]; t < a->row_ptr[i + 1]; ++t)
+      for (int col = 0; col < r; ++col) term_val[(size_t)t * r + col] = sw * a->term_val[(size_t)t * r + col];
+  }
+  std::map<std::vector<int>, std::vector<int>> classes;      // pattern -> its unloaded rows, ascending
+  for (int i = 0; i < n; ++i)
+    if (a->row_ptr[i + 1] > a->row_ptr[i] && a->rhs[i] == 0.0)
+      classes[std::vector<int>(a->term_p + a->row_ptr[i], a->term_p + a->row_ptr[i + 1])].push_back(i);
+  struct Rot { const std::vector<int>* rows; int nt; std::vector<double> M, Qc, sigma; };
+  std::vector<Rot> rots;
+  *sigma_max = 0.0;
+  for (const auto& c : classes) {
+    Rot x{&c.second, (int)c.first.size(), {}, {}, {}};
+    const int m = (int)c.second.size(), w = x.nt * r;
+    if (Q && m > q_ld) { set_error("rom_compact_rows: q_ld is smaller than the largest class"); return FINROM_ERR_ARG; }
+    x.M.resize((size_t)m * w);
+    for (int j = 0; j < m; ++j) std::memcpy(&x.M[(size_t)j * w], term_val + (size_t)a->row_ptr[c.second[j]] * r, w * sizeof(double));
+    jacobi_rows(x.M, m, w, x.Qc, x.sigma);
+    *sigma_max = std::max(*sigma_max, x.sigma[0]);
+    rots.push_back(std::move(x));
+  }
+  if (Q) std::fill(Q, Q + (size_t)n * q_ld, 0.0);
+  for (size_t ci = 0; ci < rots.size(); ++ci) {
+    const Rot& x = rots[ci];
+    const std::vector<int>& rows = *x.rows;
+    const int m = (int)rows.size(), w = x.nt * r;
+    int kept = 0;
+    for (int j = 0; j < m; ++j) kept += x.sigma[j] >= tau * *sigma_max;
+    const bool rotate = (kept + 3) / 4 < (m + 3) / 4;      // (only where it saves a k-step: the rotated rows are dense in the class)
+    for (int j = 0; j < m; ++j) {
+      row_class[rows[j]] = (int32_t)ci; row_sigma[rows[j]] = x.sigma[j];
+      if (!rotate) continue;
+      row_keep[rows[j]] = x.sigma[j] >= tau * *sigma_max;
+      std::memcpy(term_val + (size_t)a->row_ptr[rows[j]] * r, &x.M[(size_t)j * w], w * sizeof(double));
+      if (Q) std::memcpy(Q + (size_t)rows[j] * q_ld, &x.Qc[(size_t)j * m], m * sizeof(double));
+    }
+  }
   return 0;
 }
 

@@ -520,6 +520,7 @@ class RomEngine:
         self.mirror_eps_all_rows = None                   # ... and the value without dropped rows
         self.mirror_dropped = 0                           # rows the installed half list leaves out (mirror_skip_rows)
         self.mirror_dropped_max = 0.0                     # ... and the largest of them, relative to the largest row
+        self.mirror_eps_compact = None                    # ... and the gate's value of the compact list, if installed
         self.mirror = False
 
     # ---- the half form of a mirror-symmetric reduced model (DESIGN 4b', finrom_rom_set_mirror) ----------------------------------
@@ -530,14 +531,17 @@ class RomEngine:
     MIRROR_PROBE_RANGE = (0.1, 10.0)       # the dataset's range: where the probes lie, and where the short list is offered
 
     @staticmethod
-    def mirror_probe_eps(tables, perm, theta_twin, nprobe=16, seed=0, low=MIRROR_PROBE_RANGE[0], high=MIRROR_PROBE_RANGE[1], drop=None):
+    def mirror_probe_eps(tables, perm, theta_twin, nprobe=16, seed=0, low=MIRROR_PROBE_RANGE[0], high=MIRROR_PROBE_RANGE[1], drop=None,
+                         rotated=None):
         """How far from mirror-symmetric is the basis, in the metric that matters?  tables[p] = A_p Phi (p = 0: the constant
         term); with perm the mesh's mirror permutation and theta_twin the parameters' (0-based), A_p Phi_s = (tables[p] +
         tables[twin p][perm]) / 2 and A_p Phi_a is the rest.  For mirror-symmetric theta psi^T psi = A_s + D with A_s = psi_s^T psi_s
         and D = psi_a^T psi_a (the cross terms vanish); dropping D changes w_r by at most eps = lambda_max(D, A_s) relative in the
         energy norm.  -> the largest eps over `nprobe` seeded probes, log-uniform over [low, high] per mirror pair.
         drop (bool per row of the FULL mesh, closed under perm): rows of psi_s the half list leaves out as well (mirror_skip_rows);
-        their sum joins D and leaves A_s: eps = lambda_max(psi_a^T psi_a + psi_s[drop]^T psi_s[drop], psi_s[kept]^T psi_s[kept])."""
+        their sum joins D and leaves A_s: eps = lambda_max(psi_a^T psi_a + psi_s[drop]^T psi_s[drop], psi_s[kept]^T psi_s[kept]).
+        rotated (the compact list, mirror_compact_rows): (kept, truncated), each the tables [P + 1][rows, r] of weighted rows that
+        stand for psi_s[kept]; the kept ones form A_s, the truncated ones join D as well."""
         import scipy.linalg as sla
         P = len(theta_twin)
         tw1 = np.concatenate([[0], np.asarray(theta_twin) + 1])
@@ -554,6 +558,9 @@ class RomEngine:
             if drop is not None:
                 D = D + ps[drop].T @ ps[drop]
                 ps = ps[~drop]
+            if rotated is not None:
+                ps = sum(th1[p] * rotated[0][p] for p in range(P + 1)); pt = sum(th1[p] * rotated[1][p] for p in range(P + 1))
+                D = D + pt.T @ pt
             try:
                 L = np.linalg.cholesky(ps.T @ ps)
             except np.linalg.LinAlgError:                   # psi_s alone is rank-deficient: nothing like a symmetric basis
@@ -614,6 +621,65 @@ class RomEngine:
                 return cand, eps, tau, float(rn[cand].max() / rn.max())
         return none, None, None, 0.0
 
+    MIRROR_COMPACT_TAUS = (1e-8, 1e-9, 1e-10)      # singular-value thresholds tried in this order (mirror_compact_rows)
+
+    @staticmethod
+    def compact_rows(desc, keep, tau, with_q=False):
+        """finrom_rom_compact_rows on a short descriptor (mirror_descriptor's pair) -> dict(tv [nterms, r], rhs [n], cls [n], sigma
+        [n], keep [n], sigma_max, Q [n, n] or None): the rows times sqrt(weight), rotated per pattern class where that saves a
+        k-step at this tau."""
+        n, r = desc.n, desc.r
+        out = {"tv": np.zeros((desc.nterms, r)), "rhs": np.zeros(n), "cls": np.zeros(n, np.int32), "sigma": np.zeros(n),
+               "keep": np.zeros(n, np.int32), "Q": np.zeros((n, n)) if with_q else None}
+        smax = C.c_double()
+        ptr = lambda a, t: a.ctypes.data_as(t)
+        check(lib().finrom_rom_compact_rows(C.byref(desc), keep[5][1], float(tau), ptr(out["tv"], _ffi.c_f64p), ptr(out["rhs"], _ffi.c_f64p),
+                                            ptr(out["cls"], _ffi.c_i32p), ptr(out["sigma"], _ffi.c_f64p), ptr(out["keep"], _ffi.c_i32p),
+                                            ptr(out["Q"], _ffi.c_f64p) if with_q else None, n if with_q else 0, C.byref(smax)),
+              "finrom_rom_compact_rows")
+        out["sigma_max"] = smax.value
+        return out
+
+    @staticmethod
+    def compact_tables(desc, keep, out, P):
+        """(kept, truncated): the compact rows of compact_rows as tables [P + 1][rows, r] (mirror_probe_eps's `rotated`)."""
+        row_ptr, term_p = np.asarray(keep[0][0]), np.asarray(keep[1][0])
+        T = np.zeros((P + 1, desc.n, desc.r))
+        T[term_p, np.repeat(np.arange(desc.n), np.diff(row_ptr))] = out["tv"]
+        kept = out["keep"] != 0
+        return T[:, kept], T[:, ~kept]
+
+    @staticmethod
+    def mirror_compact_rows(tables, perm, theta_twin, rows, dropped_rows, desc, keep):
+        """The compact list of a short descriptor (DESIGN 4b'', finrom_rom_compact_rows): per pattern class the rows rotated onto the
+        singular directions of the class's stacked tables, the rotated rows below tau x the largest singular value over all classes
+        without terms.  The first tau of MIRROR_COMPACT_TAUS whose combined probe value -- mirror_probe_eps with psi_a^T psi_a, the
+        short list's dropped rows and the truncated rotated rows together in D -- is at most MIRROR_EPS_GATE decides.
+        -> dict(desc, keep (as mirror_descriptor's, weights of 1), tau, eps, rows: with terms, truncated, out: compact_rows's) or
+        None when no tau passes or none leaves a row out."""
+        rows = np.asarray(rows, np.int64)
+        drop = np.zeros(np.asarray(perm).shape[0], bool)
+        drop[rows[dropped_rows]] = True
+        drop[np.asarray(perm)[rows[dropped_rows]]] = True
+        P = len(theta_twin)
+        row_ptr, term_p = np.asarray(keep[0][0]), np.asarray(keep[1][0])
+        for tau in RomEngine.MIRROR_COMPACT_TAUS:
+            out = RomEngine.compact_rows(desc, keep, tau)
+            kept = out["keep"] != 0
+            if kept.all():
+                continue
+            eps = RomEngine.mirror_probe_eps(tables, perm, theta_twin, nprobe=RomEngine.MIRROR_PROBES, drop=drop,
+                                             rotated=RomEngine.compact_tables(desc, keep, out, P))[0]
+            if eps <= RomEngine.MIRROR_EPS_GATE:
+                sel = np.repeat(kept, np.diff(row_ptr))
+                new_ptr = np.concatenate([[0], np.cumsum(np.diff(row_ptr) * kept)])
+                k = [i32(new_ptr), i32(term_p[sel]), f64(out["tv"][sel]), f64(out["rhs"]), keep[4], f64(np.ones(desc.n)), keep[6]]
+                d = RomDesc(n=desc.n, r=desc.r, P=desc.P, n_obs=0, nterms=int(sel.sum()), row_ptr=k[0][1], term_p=k[1][1],
+                            term_val=k[2][1], rhs=k[3][1], obs_phi=None)
+                return {"desc": d, "keep": k, "tau": tau, "eps": eps, "rows": int(np.count_nonzero(np.diff(new_ptr))),
+                        "truncated": int((~kept).sum()), "out": out}
+        return None
+
     @staticmethod
     def mirror_form(r, P, tables, rhs, perm, rows, weight, theta_twin):
         """Host only.  The half form of one reduced model, gated: (b) r <= 80 (the grouped one-wave kernel), (c) the probes' eps at
@@ -623,7 +689,9 @@ class RomEngine:
         inside that range walk the short list, every other mirror-symmetric sample the half list with all rows.
         -> dict(eps: the gated value with the dropped rows counted, eps_all_rows: without them, dropped: their number, dropped_rows,
         tau, dropped_max: the largest dropped row's size relative to the largest row, installs, and when it installs: desc, keep,
-        with dropped rows also desc_short, keep_short) or None ((b) / (d))."""
+        with dropped rows also desc_short, keep_short, and where mirror_compact_rows finds a threshold that passes the gate
+        desc_compact, keep_compact, tau_compact, eps_compact, compact_rows, compact_truncated, compact_out; FINROM_ROM_NO_COMPACT=1:
+        none of these) or None ((b) / (d))."""
         if _os.environ.get("FINROM_ROM_NO_MIRROR") is not None or r > 80:
             return None
         eps, Ts = RomEngine.mirror_probe_eps(tables, perm, theta_twin, nprobe=RomEngine.MIRROR_PROBES)
@@ -639,6 +707,13 @@ class RomEngine:
             if form["dropped"]:
                 form["desc_short"], form["keep_short"] = RomEngine.mirror_descriptor(n, r, P, Ts, rows, weight, theta_twin, rhs,
                                                                                  form["dropped_rows"])
+                # ... and a COMPACT descriptor, the short one's rows rotated per pattern class (FINROM_ROM_NO_COMPACT=1: none)
+                if _os.environ.get("FINROM_ROM_NO_COMPACT") is None:
+                    c = RomEngine.mirror_compact_rows(tables, perm, theta_twin, rows, form["dropped_rows"], form["desc_short"],
+                                                      form["keep_short"])
+                    if c is not None:
+                        form.update(desc_compact=c["desc"], keep_compact=c["keep"], tau_compact=c["tau"], eps_compact=c["eps"],
+                                    compact_rows=c["rows"], compact_truncated=c["truncated"], compact_out=c["out"])
         return form
 
     def set_mirror(self, form):
@@ -664,16 +739,23 @@ class RomEngine:
                 check(rc, "finrom_rom_set_mirror_short")
                 self.mirror_dropped = form["dropped"]
                 self.mirror_dropped_max = form["dropped_max"]
+                if "desc_compact" in form:                # ... and the launches that offer it, the rotated rows (DESIGN 4b'')
+                    rc = lib().finrom_rom_set_mirror_compact(self._h, C.byref(form["desc_compact"]), form["keep_compact"][5][1])
+                    if rc != _ffi.ERR_UNSUPPORTED:
+                        check(rc, "finrom_rom_set_mirror_compact")
+                        self.mirror_eps_compact = form["eps_compact"]
         return True
 
-    def mirror_info(self, short=None):
+    def mirror_info(self, short=None, compact=False):
         """(rows with terms, k-steps, k-steps with vector arithmetic) of a list on the handle as the native builder counts them
         (finrom_rom_mirror_info): short=True the short list, False the half list with all rows, None the one in-range samples
-        walk (the short list if installed, else the half list); zeros where none is installed."""
+        walk (the short list if installed, else the half list); compact=True: the compact list; zeros where none is installed."""
         def get(which):
             o = [C.c_int32() for _ in range(3)]
             check(lib().finrom_rom_mirror_info(self._h, which, *[C.byref(x) for x in o]), "finrom_rom_mirror_info")
             return tuple(x.value for x in o)
+        if compact:
+            return get(2)
         if short is None:
             s = get(1)
             return s if s[1] else get(0)

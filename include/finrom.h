@@ -447,9 +447,32 @@ int finrom_rom_mirror_tables(const finrom_rom_desc* desc, const double* row_weig
  * handle is created: no short descriptor is made).
  * The counts of what a list multiplies: rows with terms, k-steps before the padding to a multiple of three, k-steps that need a
  * multiply or multiply-add per block.  finrom_rom_mirror_counts: HOST ONLY, for a descriptor (zeros where it has no grouped
- * form); finrom_rom_mirror_info: of a list installed on a handle, which = 0 the half list, 1 the short list (zeros: not installed).
+ * form); finrom_rom_mirror_info: of a list installed on a handle, which = 0 the half list, 1 the short list, 2 the compact list
+ * (zeros: not installed).
  * (finrom_rom_mirror_tables keeps its signature: its nkg is the padded k-step count, these calls give the rest.) */
 int finrom_rom_set_mirror_short(finrom_rom_t h, const finrom_rom_desc* desc, const double* row_weight, double theta_lo, double theta_hi);
+/* The COMPACT list (DESIGN.md 4b''; additive): a FOURTH list, the short list's rows rotated inside each pattern class.  A_r does not
+ * change when the rows of a class -- the unloaded rows that share one list of theta indices -- are replaced by Q times those rows, Q
+ * orthogonal; with Q from the singular vectors of the class's stacked tables most rotated rows are zero up to rounding for every
+ * theta and get no terms, like the rows the short list leaves out, under the same gate (engine.py: RomEngine.mirror_compact_rows).
+ * finrom_rom_compact_rows, HOST ONLY: from a short descriptor and its weights the compact descriptor's term_val [nterms x r] and rhs
+ * [n] (row_ptr and term_p stay): every row times sqrt(weight), its load (desc->rhs = weight F) divided by it -- the compact list
+ * has no weight classes, the caller passes it with weights of 1 --; per pattern class a one-sided Jacobi SVD of the stacked
+ * tables' rows (never the class Gram matrix); a class is rotated only where leaving out its rotated rows below tau x (the largest
+ * singular value over all classes, *sigma_max) saves a k-step of four rows, and then holds the rotated rows, largest first, in
+ * its row positions.  row_class [n]: the row's class, -1 for loaded and term-less rows; row_sigma [n]: the class's singular
+ * values, largest first, in its row positions (rotated or not); row_keep [n]: 0 for a rotated row below the threshold (the
+ * caller gives it no terms); Q, optional [n x q_ld]: row i of a rotated class = sum_j Q[i][j] sqrt(w_j) (row of member j),
+ * members in ascending row order.
+ * finrom_rom_set_mirror_compact: after finrom_rom_set_mirror_short, same checks; the samples that would walk the short list (mirror
+ * test passed, every parameter in its [theta_lo, theta_hi]) walk this one instead in a launch that OFFERS it: finrom_solve_pairs
+ * for the batches whose sweep it masks by default (S >= 16 384 beside the band sweep, r <= 80; whatever FINROM_FOM_CUS, the stream or
+ * the overlap switch then do) -- qoi_r differs from the short list's at rounding level there --, every launch that offers the short
+ * list on a handle created under FINROM_ROM_COMPACT=1 (tests), none under FINROM_ROM_NO_COMPACT=1 (A/B).  finrom_rom_solve on a
+ * default handle keeps the short list.  The kernels are the short list's, unchanged: the launch hands them the other records. */
+int finrom_rom_compact_rows(const finrom_rom_desc* desc, const double* row_weight, double tau, double* term_val, double* rhs,
+                            int32_t* row_class, double* row_sigma, int32_t* row_keep, double* Q, int32_t q_ld, double* sigma_max);
+int finrom_rom_set_mirror_compact(finrom_rom_t h, const finrom_rom_desc* desc, const double* row_weight);
 int finrom_rom_mirror_counts(const finrom_rom_desc* desc, const double* row_weight, int32_t* live_rows, int32_t* ksteps,
                              int32_t* fma_ksteps);
 int finrom_rom_mirror_info(finrom_rom_t h, int32_t which, int32_t* live_rows, int32_t* ksteps, int32_t* fma_ksteps);
